@@ -2,7 +2,7 @@
 """Headline benchmark: images/sec of one Show-and-Tell training step (the reference's hot-loop window
 `/root/reference/train.py:123-149`: forward, CE, backward, elementwise clamp, Adam) on synthetic data.
 
-    python bench.py --gpus N --steps K --warmup W [--workload train|inception|decode]
+    python bench.py --gpus N --steps K --warmup W [--workload train|inception|decode] [--dump-outputs DIR] [--full]
 
 N > 1: when not already running under torch.distributed.run, this process starts the N ranks itself (a child
 `python -m torch.distributed.run --nproc-per-node N`, spawned BEFORE anything here touches the GPU) and passes their
@@ -17,7 +17,12 @@ Workloads (BASELINE.json `configs`):
   decode     configs[4]: beam_size=5 decode (`--beam 1`: greedy, models.py:56-67) of 64 images per GPU, eval-mode ResNet-152
              encoder included (eval.py:93-99); captions/sec; shards by image across ranks with no exchange step
 Conv stack in bf16 MFMA (f32 accumulate).  Inputs are resident in HBM when the timed region starts.  Weak scaling: the per-GPU
-batch is fixed.  Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+batch is fixed.  Prints ONE JSON line on rank 0 (contract in the task statement).
+
+A plain run sets up, warms up, times exactly K steps once, writes the last step's outputs when --dump-outputs is given, and prints
+the line.  --full adds everything else on top of that line: the `roofline` object (per-launch conv timing, PMC traffic), the f32
+parity mode, the sequential schedule, the LSTM / decode-step rooflines, the decode breakdown and feature check, the `cpu_baseline`
+object, and the median of 5 timed regions.
 """
 import argparse
 import importlib
@@ -65,11 +70,19 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="train")
     ap.add_argument("--beam", type=int, default=5, help="--workload decode: beam width (1 = greedy, models.py:56-67)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the K-step timed region (barrier + synchronize on both sides, MAX over ranks) is run this many times; "
-                         "`value` / `ms_per_step` are the MEDIAN repetition, min and max ride along as extra fields")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-f32-mode", action="store_true", help="skip the secondary measurements (f32 parity mode, sequential schedule, LSTM roofline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the conv roofline (and its PMC traffic), the CPU "
+                         "baseline, the f32 parity mode, the sequential schedule, the LSTM / decode-step rooflines, the decode "
+                         "breakdown and feature check; the timed region is repeated 5 times unless --repeats says otherwise")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float32 / "
+                         "float64): train: the loss and the updated trainable parameters (tensors above 2^20 elements as a fixed, "
+                         "seeded sample of 2^20); decode: the caption ids")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the K-step timed region (barrier + synchronize on both sides, MAX over ranks) is run this many times "
+                         "(default 1, 5 with --full); `value` / `ms_per_step` are the MEDIAN repetition, min and max ride along as extra fields")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-f32-mode", action="store_true", help="with --full: skip the secondary measurements (f32 parity mode, sequential schedule, LSTM roofline)")
     ap.add_argument("--no-lookahead", dest="lookahead", action="store_false",
                     help="run the frozen conv stack of batch i+1 strictly after batch i's optimizer step (no side-stream overlap)")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the bucket all-reduces even with one rank")
@@ -77,7 +90,10 @@ def parse_args():
                     help="CPU-only check of the rank plumbing (spawn, rendezvous, barrier, max-over-ranks, one JSON line): gloo, no GPU work")
     ap.add_argument("--selftest-fail-rank", type=int, default=-1,
                     help="with --selftest-launch: this rank exits with code 7 (the launcher must hand a rank's failure on)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def spawn_ranks(args):
@@ -101,6 +117,29 @@ def synth_batch(torch, B, V, T, H, device, seed):
     caps = torch.randint(4, V, (B, T), generator=g)
     caps[:, 0], caps[:, T - 1] = 1, 2
     return images.to(device), caps.to(device), [T] * B
+
+
+DUMP_SAMPLE = 1 << 20              # --dump-outputs: larger tensors are written as this many elements at fixed, seeded positions
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: `arrays` = [(name, tensor)], written as dirname/<name>.npy -- floating tensors as float32, integer ones as
+    float64 (exact) -- flattened to a fixed, seeded sample of DUMP_SAMPLE elements when larger, so two builds compare element for
+    element"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in arrays:
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit("--dump-outputs: more than %d MB" % (DUMP_LIMIT_BYTES >> 20))
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def conv_in_sequence_us(torch, model, images, reps=3, groups=1):
@@ -601,6 +640,11 @@ def main():
     dt = sorted(dts)[len(dts) // 2]
     final_loss = float(last["loss"].item())
     ts.check_ids()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives: the last step's loss and the trainable parameters it updated (the flat buffer Adam writes)
+        fp = ts.flat
+        dump_outputs(args.dump_outputs, [("loss", last["loss"])] +
+                     [("param." + name, fp.params[o:o + n].view(shape)) for name, (o, n, shape) in fp.slices.items()])
 
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
@@ -627,39 +671,40 @@ def main():
                        "lookahead_groups": groups if args.lookahead else 0,
                        "backend": (backend if backend != "nccl" else "nccl (RCCL)") if use_dist else None,
                        "final_loss": round(final_loss, 4)},
-            "roofline": conv_roofline(torch, sat, model, images, wl, "step", groups if args.lookahead else 1),
         }
-        if groups > 1 and args.lookahead:
-            # the same figure for the ungrouped program (one batch per launch: what a strictly sequential step runs)
-            seq = conv_roofline(torch, sat, model, images, wl, "step", 1)
-            out["roofline"]["one_batch_per_launch"] = {k: seq[k] for k in ("achieved", "frac", "avg_launch_us", "ms_per_step_in_kernel")}
-        if args.workload == "train":
-            attach_traffic(out)
-        else:
-            attach_traffic(out, os.path.join(ROOT, "profiles", "r05_cfg3_pmc_traffic.json"))      # the same passes on configs[3]
-        if world == 1 and args.lookahead and not args.no_f32_mode:
-            # the same K steps with strictly sequential steps (what --no-lookahead times), for comparison in the same process
-            def seq_steps(n):
-                o = None
-                for i in range(n):
-                    o = dp.step((batches[i % nb], caps, lengths), global_tokens)
-                return o
-            seq_steps(2)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            seq_steps(args.steps)
-            torch.cuda.synchronize()
-            dts_ = time.perf_counter() - t0
-            out["sequential_schedule"] = {"value": round(wl["batch"] * args.steps / dts_, 1), "unit": "images/sec",
-                                          "ms_per_step": round(dts_ / args.steps * 1e3, 3),
-                                          "note": "same engine, no look-ahead: batch i+1's conv stack starts after batch i's optimizer step"}
-        if world == 1 and not args.no_f32_mode:
-            del dp, ts, model
-            torch.cuda.empty_cache()
-            out["roofline_lstm"] = lstm_roofline(torch, sat, wl)
-            out["f32_parity_mode"] = f32_mode_rate(torch, sat, dev, wl, images, caps, lengths, lookahead=args.lookahead)
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(torch, 123, wl, args.workload)
+        if args.full:
+            out["roofline"] = conv_roofline(torch, sat, model, images, wl, "step", groups if args.lookahead else 1)
+            if groups > 1 and args.lookahead:
+                # the same figure for the ungrouped program (one batch per launch: what a strictly sequential step runs)
+                seq = conv_roofline(torch, sat, model, images, wl, "step", 1)
+                out["roofline"]["one_batch_per_launch"] = {k: seq[k] for k in ("achieved", "frac", "avg_launch_us", "ms_per_step_in_kernel")}
+            if args.workload == "train":
+                attach_traffic(out)
+            else:
+                attach_traffic(out, os.path.join(ROOT, "profiles", "r05_cfg3_pmc_traffic.json"))      # the same passes on configs[3]
+            if world == 1 and args.lookahead and not args.no_f32_mode:
+                # the same K steps with strictly sequential steps (what --no-lookahead times), for comparison in the same process
+                def seq_steps(n):
+                    o = None
+                    for i in range(n):
+                        o = dp.step((batches[i % nb], caps, lengths), global_tokens)
+                    return o
+                seq_steps(2)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                seq_steps(args.steps)
+                torch.cuda.synchronize()
+                dts_ = time.perf_counter() - t0
+                out["sequential_schedule"] = {"value": round(wl["batch"] * args.steps / dts_, 1), "unit": "images/sec",
+                                              "ms_per_step": round(dts_ / args.steps * 1e3, 3),
+                                              "note": "same engine, no look-ahead: batch i+1's conv stack starts after batch i's optimizer step"}
+            if world == 1 and not args.no_f32_mode:
+                del dp, ts, model
+                torch.cuda.empty_cache()
+                out["roofline_lstm"] = lstm_roofline(torch, sat, wl)
+                out["f32_parity_mode"] = f32_mode_rate(torch, sat, dev, wl, images, caps, lengths, lookahead=args.lookahead)
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(torch, 123, wl, args.workload)
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.barrier()
@@ -731,11 +776,15 @@ def run_decode(args, torch, dist, sat, wl, dev, rank, world, use_dist, backend):
                 ids = decode(model.encoder(batches[i % nb]))
         return ids
 
-    ids = run_steps(max(args.warmup, 1))
-    dts = timed_regions(args, torch, dist, dev, use_dist, lambda: run_steps(args.steps))
+    run_steps(max(args.warmup, 1))
+    last = {}
+    dts = timed_regions(args, torch, dist, dev, use_dist, lambda: last.__setitem__("ids", run_steps(args.steps)))
     dt = sorted(dts)[len(dts) // 2]
-    ids = run_steps(1)
-    finite = bool(torch.isfinite(model.encoder(batches[0])).all().item())
+    ids = last["ids"]                  # the captions of the last timed step
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [("ids", ids)])
+    if args.full:
+        finite = bool(torch.isfinite(model.encoder(batches[0])).all().item())
     if rank == 0:
         out = {"metric": "captions/sec (beam_size=%d decode, encoder included)" % beam if beam > 1 else "captions/sec (greedy decode, encoder included)",
                "value": round(world * B * args.steps / dt, 2), "unit": "captions/sec", "n_gpus": world, "steps": args.steps,
@@ -750,28 +799,30 @@ def run_decode(args, torch, dist, sat, wl, dev, rank, world, use_dist, backend):
                           "schedule": ("encoder look-ahead depth %d: the conv stacks of batches i+1..i+%d run on side streams under batch i's decode loop, %d batches per program run (eval mode: the batches of a run concatenate)" % (depth, depth, model.encoder.lookahead_groups))
                                       if args.lookahead else "strictly sequential batches",
                           "backend": (backend if backend != "nccl" else "nccl (RCCL)") if use_dist else None,
-                          "features_finite": finite, "ids_shape": list(ids.shape)},
-               "roofline": conv_roofline(torch, sat, model, batches[0], wl, "batch", model.encoder.lookahead_groups if args.lookahead else 1)}
-        out["roofline"]["traffic_note"] = "null: the PMC traffic passes of this round were taken on the headline workload (profiles/r05_pmc_traffic.json)"
-        if world == 1 and not args.no_f32_mode:
-            feats = model.encoder(batches[0]).clone()
+                          "ids_shape": list(ids.shape)}}
+        if args.full:
+            out["config"]["features_finite"] = finite
+            out["roofline"] = conv_roofline(torch, sat, model, batches[0], wl, "batch", model.encoder.lookahead_groups if args.lookahead else 1)
+            out["roofline"]["traffic_note"] = "null: the PMC traffic passes of this round were taken on the headline workload (profiles/r05_pmc_traffic.json)"
+            if world == 1 and not args.no_f32_mode:
+                feats = model.encoder(batches[0]).clone()
 
-            def t_of(fn, n=10):
-                fn()
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(n):
+                def t_of(fn, n=10):
                     fn()
-                torch.cuda.synchronize()
-                return (time.perf_counter() - t0) / n * 1e3
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(n):
+                        fn()
+                    torch.cuda.synchronize()
+                    return (time.perf_counter() - t0) / n * 1e3
 
-            with torch.no_grad():
-                out["breakdown_ms"] = {"encoder_eval": round(t_of(lambda: model.encoder(batches[0])), 3),
-                                       "greedy_decode_20_steps": round(t_of(lambda: model.decoder.sample(feats)), 3),
-                                       "beam%d_decode_20_steps" % max(beam, 2): round(t_of(lambda: model.decoder.sample_beam(feats, max(beam, 2), end_id=2)), 3)}
-            out["roofline_decode"] = vocab_step_roofline(torch, sat, wl, B * beam)
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(torch, 123, wl, "decode")
+                with torch.no_grad():
+                    out["breakdown_ms"] = {"encoder_eval": round(t_of(lambda: model.encoder(batches[0])), 3),
+                                           "greedy_decode_20_steps": round(t_of(lambda: model.decoder.sample(feats)), 3),
+                                           "beam%d_decode_20_steps" % max(beam, 2): round(t_of(lambda: model.decoder.sample_beam(feats, max(beam, 2), end_id=2)), 3)}
+                out["roofline_decode"] = vocab_step_roofline(torch, sat, wl, B * beam)
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(torch, 123, wl, "decode")
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.barrier()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generate tests/golden/G*.npz by running the REFERENCE's own `models.DecoderRNN` (imported from
-/root/reference, build container only) plus train.py's loss / clamp / Adam arithmetic.
+oracle/_ref, the bytecode `__graft_entry__.build()` makes where the reference checkout is present) plus train.py's loss / clamp / Adam arithmetic.
 
     python tests/golden/make_goldens.py [out_dir]  # rewrites G1, G2, G3, G5, G8, G9 (default: tests/golden)
 
@@ -22,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 from oracle import decoder as OD  # noqa: E402
 
-REF = "/root/reference"
+REF = os.path.join(ROOT, "oracle", "_ref")       # oracle/build_ref.py
 
 
 def import_reference_models():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generate tests/golden/G6_attend_*.npz from the REFERENCE's own `model2.ShowAttendTellModel` (imported from
-/root/reference, build container only).
+oracle/_ref, the bytecode `__graft_entry__.build()` makes where the reference checkout is present).
 
     python tests/golden/make_goldens_attend.py
 
@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 from oracle import attend as OA  # noqa: E402
 
-REF = "/root/reference"
+REF = os.path.join(ROOT, "oracle", "_ref")       # oracle/build_ref.py
 
 
 def import_model2():

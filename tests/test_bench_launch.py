@@ -42,3 +42,28 @@ def test_a_failing_rank_makes_the_launcher_exit_non_zero_and_print_no_result_lin
     r = _run(["--gpus", "2", "--selftest-launch", "--selftest-fail-rank", "1"])
     assert r.returncode != 0, (r.returncode, r.stdout, r.stderr[-500:])
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_of_large_tensors(tmp_path):
+    """`--dump-outputs`: floating tensors as float32, integer ones as float64 (exact), tensors above DUMP_SAMPLE elements as the same
+    seeded sample on every call, and never more than 64 MB in all"""
+    import importlib.util
+    import numpy as np
+    import pytest
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = bench.DUMP_SAMPLE
+    big = torch.arange(n + 7, dtype=torch.float64).view(-1, 1)
+    arrays = [("loss", torch.tensor([2.5])), ("w", big), ("ids", torch.arange(6).view(2, 3))]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    assert sorted(os.listdir(tmp_path / "a")) == ["ids.npy", "loss.npy", "w.npy"]
+    loss, w, ids = (np.load(tmp_path / "a" / (k + ".npy")) for k in ("loss", "w", "ids"))
+    assert loss.dtype == np.float32 and loss.tolist() == [2.5]
+    assert ids.dtype == np.float64 and ids.tolist() == [[0, 1, 2], [3, 4, 5]]
+    assert w.dtype == np.float32 and w.shape == (n,) and (np.diff(w) > 0).all() and w.max() <= n + 6    # distinct positions, in order
+    assert np.array_equal(w, np.load(tmp_path / "b" / "w.npy"))
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "c"), [("t%d" % i, torch.zeros(n)) for i in range(17)])      # 17 x 4 MB

@@ -303,7 +303,7 @@ def test_bench_py_gpus2_runs_its_real_multi_rank_branch_on_one_device():
     (SAT_BENCH_BACKEND / SAT_BENCH_SHARE_DEVICE; RCCL refuses two ranks on one device).  Everything but the transport is the
     code the 8-GPU run executes (train.py:43-44's nn.DataParallel replaced by one process per GPU)."""
     import math
-    out = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline"],
+    out = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--full"],
                  {"SAT_BENCH_BACKEND": "gloo", "SAT_BENCH_SHARE_DEVICE": "1"})
     assert out["n_gpus"] == 2 and out["steps"] == 2 and out["warmup"] == 1
     cfg = out["config"]
@@ -325,7 +325,7 @@ def test_bench_py_gpus4_rehearsal_on_one_device(workload):
     device over gloo.  FOUR ranks, not eight: this pool kills a job with more than six processes on its GPU (the test session is
     one of them), so N = 8 itself can only run on the driver's node.  One run, no loops.  train.py:43-44"""
     import math
-    out = _bench(["--gpus", "4", "--workload", workload, "--steps", "2", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline"],
+    out = _bench(["--gpus", "4", "--workload", workload, "--steps", "2", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--full"],
                  {"SAT_BENCH_BACKEND": "gloo", "SAT_BENCH_SHARE_DEVICE": "1"}, timeout=1100)
     assert out["n_gpus"] == 4 and out["config"]["global_batch"] == 256 and out["config"]["parallelism"].startswith("dp4")
     assert out["config"]["backend"] == "gloo" and out["value"] > 0
@@ -340,7 +340,7 @@ def test_bench_py_gpus4_rehearsal_on_one_device(workload):
 def test_bench_py_decode_workload_shards_by_image_over_two_ranks():
     """configs[4] at N = 2 on the one device: every rank decodes its own 64 images (no collective inside the decode), captions/sec
     is the whole job's"""
-    out = _bench(["--gpus", "2", "--workload", "decode", "--steps", "2", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline"],
+    out = _bench(["--gpus", "2", "--workload", "decode", "--steps", "2", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--full"],
                  {"SAT_BENCH_BACKEND": "gloo", "SAT_BENCH_SHARE_DEVICE": "1"})
     assert out["n_gpus"] == 2 and out["unit"] == "captions/sec" and out["config"]["global_batch"] == 128
     assert out["config"]["beam_size"] == 5 and out["config"]["features_finite"] is True
@@ -349,10 +349,10 @@ def test_bench_py_decode_workload_shards_by_image_over_two_ranks():
 
 @pytest.mark.timeout(1200)
 def test_bench_py_single_gpu_line_carries_every_contract_key():
-    """the line the driver parses at N = 1 (`python bench.py --gpus 1 --steps K --warmup W`): contract keys, the `roofline` object of
+    """the line of `python bench.py --gpus 1 --steps K --warmup W --full`: contract keys, the `roofline` object of
     the dominant kernel (achieved / peak / frac consistent, traffic either null or measured on this very library build) and the
     `cpu_baseline` object (oracle port on the host's cores, rank 0, bounded sample)"""
-    out = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--repeats", "1"], {})
+    out = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--repeats", "1", "--full"], {})
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):
         assert k in out, k
@@ -367,3 +367,31 @@ def test_bench_py_single_gpu_line_carries_every_contract_key():
     c = out["cpu_baseline"]
     assert c["kind"] == "port" and c["unit"] == "images/sec" and c["value"] > 0 and c["cores"] >= 1 and c["threads"] >= 1 and c["sample"]
     assert out["roofline_lstm"]["frac_of_f32_mfma_peak"] > 0 and out["f32_parity_mode"]["value"] > 0 and out["sequential_schedule"]["value"] > 0
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("workload", ["train", "decode"])
+def test_bench_py_plain_line_times_exactly_k_steps_and_dumps_the_last_one(workload, tmp_path):
+    """a plain run (no --full): the contract keys, ONE timed region of exactly `steps` steps, none of the --full extras, and
+    --dump-outputs writes the last timed step's outputs as float32 / float64 .npy files within 64 MB"""
+    import math
+    d = tmp_path / "out"
+    out = _bench(["--gpus", "1", "--workload", workload, "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)], {})
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert k in out, k
+    assert out["steps"] == 3 and out["repeats"]["n"] == 1 and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    assert abs(out["value"] - 64 / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-2
+    for k in ("roofline", "cpu_baseline", "f32_parity_mode", "sequential_schedule", "roofline_lstm", "roofline_decode", "breakdown_ms"):
+        assert k not in out, k
+    files = sorted(os.listdir(d))
+    assert files and all(f.endswith(".npy") for f in files)
+    arrays = {f[:-4]: np.load(d / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    if workload == "train":
+        assert arrays["loss"].shape == (1,) and math.isclose(float(arrays["loss"][0]), out["config"]["final_loss"], abs_tol=1e-4)
+        assert arrays["param.decoder.linear.weight"].shape == (1 << 20,)              # 10000 x 512: the seeded sample
+        assert arrays["param.decoder.linear.bias"].shape == (10000,)
+    else:
+        ids = arrays["ids"]
+        assert ids.shape == (64, 20) and ids.dtype == np.float64 and (ids == np.round(ids)).all() and ids.min() >= 0 and ids.max() < 10000
