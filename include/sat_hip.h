@@ -537,6 +537,31 @@ int sat_beam_decode(const float* features /*[B,E]*/, const float* embed /*[V,E]*
 int sat_greedy_decode(const float* features, const float* embed, const float* const* lstm_w /*[host]*/, int num_layers,
                       const float* lin_w, const float* lin_b, int B, int E, int H, int V, int steps, float* h, float* c, float* h_tmp,
                       float* x_tmp, int64_t* ids, int64_t ids_stride, float* workspace, int64_t ws_bytes, sat_stream_t stream);
+/* Scheduled sampling (the reference's DecoderRNN.ss_prob, models.py:38, and its schedule, train.py:109-113) in the training forward.
+ * Random numbers: Philox4x32-10, key (seed & 0xffffffff, seed >> 32), u = ((x >> 8) + 0.5) * 2^-24.  The draw for row b of step t is
+ * s(b, t) = first argmax_v (logit[b][v] + G(b, t, v)), G = -log(-log u) of counter (v >> 2, b, t, 2*rank), word v & 3 (Gumbel-max: an
+ * exact draw from softmax(logits)); mask(b, t) = u < ss_prob of counter (0, b, t, 2*rank + 1), word 0.
+ * sat_vocab_sample: ONE step over B rows: logits = h lin_w^T + lin_b (stored when `logits` != NULL); ids[b*ids_stride] = mask(b, t) ?
+ *   s(b, t) : teacher[b*teacher_stride] (teacher NULL: s(b, t) for every row); where a draw was taken and embed / x are given,
+ *   x[b*E..] = embed[ids[b]] (other rows of x are not written).  workspace: sat_ss_decoder_fwd_ws_bytes(B, V).
+ * sat_ss_decoder_fwd: the whole decoder forward (models.py:47-53) with scheduled sampling, as ONE call: captions [B][cap_stride] are
+ *   the teacher's inputs (train.py's captions[:, :-1]), step t = 0..T-1 feeds features (t = 0), embed[used[b][t-1]] after, with
+ *   used[b][0] = captions[b][0] and, for t >= 2, used[b][t-1] = mask(b, t) ? s(b, t) from the logits of step t-1 : captions[b][t-1];
+ *   used [B][used_stride] (>= T-1 columns) out, the teacher's tokens in every column a row does not reach.  lstm_w: HOST array of
+ *   4 * num_layers device pointers (w_ih, w_hh, b_ih, b_hh per layer); tapes: HOST array of 5 * num_layers device pointers per
+ *   layer (GA [N,4H], CS [N,H], HS [N,H], HP [N,H], c_state [B,H]) that receive exactly what sat_lstm_fwd leaves there, so
+ *   sat_lstm_bwd / sat_lstm_bwd_bf16 and sat_embed_concat_bwd (on `used`) are its backward; X [N,E] the layer-0 input out; logits
+ *   [N,ldl] (exact f32) or NULL (draws only; the caller projects all rows afterwards, e.g. sat_vocab_ce_fwd_bf16).  ss_prob and
+ *   seed are kernel arguments: no host synchronisation.  workspace: sat_ss_decoder_fwd_ws_bytes(batch_sizes[0], V). */
+int64_t sat_ss_decoder_fwd_ws_bytes(int B, int V);
+int sat_vocab_sample(const float* h /*[B,H]*/, const float* lin_w, const float* lin_b, int B, int H, int V, float* logits, int64_t ldl,
+                     float ss_prob, uint64_t seed, int t, int rank, const int64_t* teacher, int64_t teacher_stride, int64_t* ids,
+                     int64_t ids_stride, const float* embed, int E, float* x, float* workspace, int64_t ws_bytes, sat_stream_t stream);
+int sat_ss_decoder_fwd(const float* features /*[B,E]*/, const float* embed /*[V,E]*/, const int64_t* captions, int64_t cap_stride,
+                       const int32_t* batch_sizes /*[host] T*/, const int32_t* prefix /*[T+1] device*/, int T, int E, int V,
+                       const float* const* lstm_w /*[host]*/, int num_layers, int H, const float* lin_w, const float* lin_b,
+                       float* const* tapes /*[host]*/, float* X, float* logits, int64_t ldl, float ss_prob, uint64_t seed, int rank,
+                       int64_t* used, int64_t used_stride, float* workspace, int64_t ws_bytes, sat_stream_t stream);
 /* The truncation rule of the reference's id -> word loop (`evaluation`, eval.py:103-109: `if word == '<end>': break`):
  * kept[b] = number of ids of row b in front of the first end_id (T when the row has none).  ids: [B] rows of T int64 with
  * `stride` elements between rows (model.sample's [B,20], or one hypothesis plane of the beam ids). */

@@ -22,4 +22,4 @@ from .optim import FusedClampAdam  # noqa: F401
 from .pack import PackInfo, pack_targets  # noqa: F401
 from .resnet import RESNET152, conv_flops  # noqa: F401
 from .trainer import (DataParallelStep, FlatParams, TrainStep, decode_shard, dp_shard, gather_decoded,  # noqa: F401
-                      lr_for_epoch)
+                      lr_for_epoch, ss_prob_for_epoch)

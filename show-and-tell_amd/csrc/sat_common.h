@@ -57,3 +57,29 @@ template <> __device__ __forceinline__ float to_f32<bf16_t>(bf16_t v) { return (
 template <typename T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return (bf16_t)v; }
+
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 / rocRAND / torch generator): 4 x u32 of a counter -> 4 random u32 words.
+// Scheduled sampling keys every decision by (token group, row, step, stream) so that a draw does not depend on launch geometry.
+__device__ __forceinline__ u32x4 sat_philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (unsigned)p1;
+        c3 = (unsigned)p0;
+        c0 = n0;
+        c2 = n2;
+    }
+    return (u32x4){c0, c1, c2, c3};
+}
+
+// Gumbel(0,1) noise -log(-log u) of the uniform u = ((x >> 8) + 0.5) * 2^-24 in (0, 1).  u itself is exact in f32 below 1/2 and
+// 1 - u is exact at and above it, so -log u is taken as -log1p(-(1 - u)) there: the large noise values (u -> 1) that decide a
+// Gumbel-max draw keep full f32 accuracy instead of collapsing to +inf at the top uniform.
+__device__ __forceinline__ float sat_gumbel(unsigned x) {
+    const unsigned m = x >> 8;
+    const float nl = m < (1u << 23) ? -logf(((float)m + 0.5f) * 0x1p-24f)
+                                    : -log1pf(-(((float)((1u << 24) - 1u - m) + 0.5f) * 0x1p-24f));
+    return -logf(nl);
+}

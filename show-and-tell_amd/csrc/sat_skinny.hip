@@ -1,6 +1,6 @@
 // Skinny (M <= 64 rows per workgroup) f32 GEMMs for the serial parts of the decoder: the recurrent LSTM
-// step (models.py:52), its backward dh chain, the encoder fc (models.py:27) and the greedy-decode vocab
-// projection + argmax (models.py:61-63).
+// step (models.py:52), its backward dh chain, the encoder fc (models.py:27), the greedy-decode vocab
+// projection + argmax (models.py:61-63) and the scheduled-sampling projection + Gumbel-max draw.
 //
 // A weight element is used by exactly one workgroup, once, so weights and activations go straight from
 // L2 to VGPRs in MFMA operand layout (no LDS round trip): v_mfma_f32_16x16x4_f32 (exact f32), lane
@@ -12,7 +12,7 @@
 
 namespace {
 
-enum { EPI_STORE = 0, EPI_LSTM = 1, EPI_ARGMAX = 2, EPI_LSTM_BWD = 3 };
+enum { EPI_STORE = 0, EPI_LSTM = 1, EPI_ARGMAX = 2, EPI_LSTM_BWD = 3, EPI_SAMPLE = 4 };
 
 struct SkinnyArgs {
     // operand pair 1 (required) and 2 (optional): out += A[M,K] * Wsel[16,K]^T
@@ -31,7 +31,7 @@ struct SkinnyArgs {
     float* cs;                                // [M,H] cell-state tape (nullable)
     float* h_out;                             // [M,H]
     float* h_out2; int m2;                    // second copy for rows < m2 (next step's h_prev rows), nullable
-    // EPI_ARGMAX
+    // EPI_ARGMAX, EPI_SAMPLE
     float* pmax; int* pidx;                   // [M][gridDim.x]
     // EPI_LSTM_BWD: out columns are hidden units j; acc = (DG_{t+1} W_hh)[row][j] for rows < m2 (the rows that have a step
     // t+1); the epilogue is the pointwise LSTM backward of step t for (row, j):
@@ -39,6 +39,9 @@ struct SkinnyArgs {
     const float* dhs;                         // [M][H]   d(loss)/d(h_t) from above
     const float* cs_prev;                     // [M][H] c_{t-1} or NULL (zeros)
     float* dg;                                // [M][4H] out
+    // EPI_SAMPLE: per row the first maximal column of s + G, s = logit (stored to out[row*ldo + col] when out != NULL) and G the
+    // Gumbel noise of Philox counter (col >> 2, row, ss_t, ss_ctr3), key (key0, key1), word col & 3
+    unsigned key0, key1, ss_t, ss_ctr3;
 };
 
 constexpr int NWV = 8;   // waves per workgroup: K is split 8 ways (x gridDim.z), partial tiles reduced through LDS
@@ -233,18 +236,42 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const SkinnyArgs p) {
             p.h_out[(long)grow * H + j] = h_new;
             if (p.h_out2 && grow < p.m2) p.h_out2[(long)grow * H + j] = h_new;
         }
-    } else {  // EPI_ARGMAX: first maximal column of this 16-column group per row
+    } else {  // EPI_ARGMAX: first maximal column of this 16-column group per row; EPI_SAMPLE: the same of logit + Gumbel noise
         float best = -INFINITY;
         int bidx = 0x7fffffff;
+        if constexpr (EPI == EPI_SAMPLE) {
+            if (grow < p.M) {
+                // this lane's 4 columns are one Philox counter's 4 words: col >> 2 = cg*4 + q, word e
+                const u32x4 r = sat_philox4x32_10((unsigned)(cg * 4 + q), (unsigned)grow, p.ss_t, p.ss_ctr3, p.key0, p.key1);
+                f32x4 v = *(const f32x4*)&red[0][row][q * 4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int col = cg * 16 + q * 4 + e;
-            if (col < p.N) {
-                float s = 0.0f;
+                for (int w = 1; w < NWV; ++w) {
+                    const f32x4 t = *(const f32x4*)&red[w][row][q * 4];
+                    v += t;
+                }
 #pragma unroll
-                for (int w = 0; w < NWV; ++w) s += red[w][row][q * 4 + e];
-                if (p.bias) s += p.bias[col];
-                if (s > best) { best = s; bidx = col; }
+                for (int e = 0; e < 4; ++e) {
+                    const int col = cg * 16 + q * 4 + e;
+                    if (col < p.N) {
+                        float s = v[e];
+                        if (p.bias) s += p.bias[col];
+                        if (p.out) p.out[(long)grow * p.ldo + col] = s;
+                        const float sg = s + sat_gumbel(r[e]);
+                        if (sg > best) { best = sg; bidx = col; }
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int col = cg * 16 + q * 4 + e;
+                if (col < p.N) {
+                    float s = 0.0f;
+#pragma unroll
+                    for (int w = 0; w < NWV; ++w) s += red[w][row][q * 4 + e];
+                    if (p.bias) s += p.bias[col];
+                    if (s > best) { best = s; bidx = col; }
+                }
             }
         }
 #pragma unroll
@@ -334,6 +361,21 @@ extern "C" int sat_vocab_argmax(const float* h, const float* w, const float* b, 
     hipLaunchKernelGGL((skinny_kernel<EPI_ARGMAX, false>), grid, dim3(NWV * 64), 0, s, a);
     SAT_LAUNCH_CHECK();
     hipLaunchKernelGGL(argmax_reduce_kernel, dim3(B), dim3(256), 0, s, a.pmax, a.pidx, ncg, ids, ids_stride);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
+// Gumbel-max draw per row of one sampling step (sat_ss_decoder_fwd): partials [M][cdiv(V,16)] of (best s + G, column) in pmax /
+// pidx; the logits s = h w^T + b are stored to out[row*ldo + col] when out != NULL
+int sat_skinny_sample(const float* h, const float* w, const float* b, int M, int H, int V, float* out, long ldo, unsigned key0,
+                      unsigned key1, unsigned t, unsigned ctr3, float* pmax, int* pidx, hipStream_t s) {
+    if (H & 3) return SAT_ERR_ARG;
+    SkinnyArgs a = {};
+    a.A = h; a.lda = H; a.W = w; a.ldw = H; a.K = H; a.M = M; a.N = V; a.nz = 1; a.bias = b;
+    a.out = out; a.ldo = ldo; a.pmax = pmax; a.pidx = pidx;
+    a.key0 = key0; a.key1 = key1; a.ss_t = t; a.ss_ctr3 = ctr3;
+    dim3 grid(sat_cdiv(V, 16), sat_cdiv(M, 64), 1);
+    hipLaunchKernelGGL((skinny_kernel<EPI_SAMPLE, false>), grid, dim3(NWV * 64), 0, s, a);
     SAT_LAUNCH_CHECK();
     return SAT_OK;
 }

@@ -1,0 +1,164 @@
+// Scheduled sampling (Bengio et al. 2015) for the Show-and-Tell decoder's training forward: with probability ss_prob the input of
+// step t >= 2 is a token DRAWN from softmax(logits of step t-1) instead of the teacher's captions[b][t-1] (the reference keeps
+// `DecoderRNN.ss_prob`, models.py:38, and the schedule in train.py:109-113).  Step t+1's input then depends on step t's logits,
+// so the teacher-forced forward's batched x-gates GEMM, persistent recurrence and one-shot vocab projection give way to a loop
+// of, per step: one fused LSTM step per layer (both products + gates, sat_skinny_lstm), the vocab projection with the Gumbel-max
+// draw in its epilogue (skinny_kernel<EPI_SAMPLE>), and one select + embedding-gather launch.  The tapes are exactly those of
+// sat_lstm_fwd, so the teacher-forced backward runs unchanged on the tokens actually fed.
+//
+// Randomness: Philox4x32-10, key (seed lo, seed hi).  Noise of token v for row b of step t: counter (v >> 2, b, t, 2*rank),
+// word v & 3, G = -log(-log u); mask: counter (0, b, t, 2*rank + 1), word 0; u = ((x >> 8) + 0.5) * 2^-24.  Every decision is a
+// function of (seed, rank, b, t, v) alone, whatever the launch geometry.
+#include "sat_internal.h"
+
+int sat_skinny_sample(const float* h, const float* w, const float* b, int M, int H, int V, float* out, long ldo, unsigned key0,
+                      unsigned key1, unsigned t, unsigned ctr3, float* pmax, int* pidx, hipStream_t s);
+
+namespace {
+
+// one workgroup per row b: mask(b, t) = u < ss_prob; if set, the arg-max of the Gumbel-max partials is the token fed to step t
+// (its embedding row goes to x[b]), else the teacher's token (x[b] already holds its row).  teacher == NULL: every row samples.
+__global__ __launch_bounds__(256) void ss_select_kernel(const float* __restrict__ pmax, const int* __restrict__ pidx, int ncg,
+                                                        unsigned t, unsigned ctr3, unsigned key0, unsigned key1, float ss_prob,
+                                                        const int64_t* __restrict__ teacher, long teacher_stride, int64_t* ids,
+                                                        long ids_stride, const float* __restrict__ embed, int E, int V,
+                                                        float* __restrict__ x) {
+    __shared__ float sb[256];
+    __shared__ int si[256];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    if (teacher) {
+        const unsigned u = sat_philox4x32_10(0u, (unsigned)row, t, ctr3, key0, key1)[0] >> 8;
+        // compared in f64: exact for every 24-bit u, so the decision is reproducible bit for bit off the device
+        if (!(((double)u + 0.5) * 0x1p-24 < (double)ss_prob)) {
+            if (tid == 0) ids[(long)row * ids_stride] = teacher[(long)row * teacher_stride];
+            return;
+        }
+    }
+    float best = -INFINITY;
+    int bidx = 0x7fffffff;
+    for (int c = tid; c < ncg; c += 256) {
+        const float v = pmax[(long)row * ncg + c];
+        const int i = pidx[(long)row * ncg + c];
+        if (v > best || (v == best && i < bidx)) { best = v; bidx = i; }
+    }
+    sb[tid] = best; si[tid] = bidx;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) {
+            const float ob = sb[tid + s];
+            const int oi = si[tid + s];
+            if (ob > sb[tid] || (ob == sb[tid] && oi < si[tid])) { sb[tid] = ob; si[tid] = oi; }
+        }
+        __syncthreads();
+    }
+    int tok = si[0];
+    tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);       // memory safety only (a NaN logit row has no arg-max)
+    if (tid == 0) ids[(long)row * ids_stride] = tok;
+    if (embed && x) {
+        const float* src = embed + (long)tok * E;
+        float* dst = x + (long)row * E;
+        for (int e = tid; e < E; e += 256) dst[e] = src[e];
+    }
+}
+
+// used[b][j] = captions[b][j] for j < cols: the teacher's tokens wherever no draw replaces them
+__global__ __launch_bounds__(256) void ss_init_used_kernel(const int64_t* __restrict__ captions, long cap_stride, int B, int cols,
+                                                           int64_t* __restrict__ used, long used_stride) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)B * cols) return;
+    const long b = i / cols, j = i % cols;
+    used[b * used_stride + j] = captions[b * cap_stride + j];
+}
+
+// one sampling step: projection of M rows (+ optional logits store) and the draw for the first m_sel <= M of them
+int sample_step(const float* h, const float* lin_w, const float* lin_b, int M, int m_sel, int H, int V, float* logits, long ldl,
+                float ss_prob, uint64_t seed, int t, int rank, const int64_t* teacher, long teacher_stride, int64_t* ids,
+                long ids_stride, const float* embed, int E, float* x, float* workspace, hipStream_t s) {
+    const int ncg = sat_cdiv(V, 16);
+    float* pmax = workspace;
+    int* pidx = (int*)(workspace + (long)M * ncg);
+    const unsigned k0 = (unsigned)(seed & 0xffffffffu), k1 = (unsigned)(seed >> 32);
+    SAT_TRY(sat_skinny_sample(h, lin_w, lin_b, M, H, V, logits, ldl, k0, k1, (unsigned)t, 2u * (unsigned)rank, pmax, pidx, s));
+    if (m_sel < 1) return SAT_OK;
+    hipLaunchKernelGGL(ss_select_kernel, dim3(m_sel), dim3(256), 0, s, pmax, pidx, ncg, (unsigned)t, 2u * (unsigned)rank + 1u, k0,
+                       k1, ss_prob, teacher, teacher_stride, ids, ids_stride, embed, E, V, x);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t sat_ss_decoder_fwd_ws_bytes(int B, int V) { return (int64_t)B * sat_cdiv(V, 16) * 8; }
+
+extern "C" int sat_vocab_sample(const float* h, const float* lin_w, const float* lin_b, int B, int H, int V, float* logits,
+                                int64_t ldl, float ss_prob, uint64_t seed, int t, int rank, const int64_t* teacher,
+                                int64_t teacher_stride, int64_t* ids, int64_t ids_stride, const float* embed, int E, float* x,
+                                float* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    if (!h || !lin_w || !lin_b || !ids || !workspace || B < 1 || H < 4 || (H & 3) || V < 1 || t < 0 || rank < 0) return SAT_ERR_ARG;
+    if ((logits && ldl < V) || (x && (!embed || E < 1))) return SAT_ERR_ARG;
+    if (ws_bytes < sat_ss_decoder_fwd_ws_bytes(B, V)) return SAT_ERR_WORKSPACE;
+    return sample_step(h, lin_w, lin_b, B, B, H, V, logits, ldl, ss_prob, seed, t, rank, teacher, teacher_stride, ids, ids_stride,
+                       embed, E, x, workspace, (hipStream_t)stream);
+}
+
+extern "C" int sat_ss_decoder_fwd(const float* features, const float* embed, const int64_t* captions, int64_t cap_stride,
+                                  const int32_t* batch_sizes, const int32_t* prefix, int T, int E, int V,
+                                  const float* const* lstm_w, int num_layers, int H, const float* lin_w, const float* lin_b,
+                                  float* const* tapes, float* X, float* logits, int64_t ldl, float ss_prob, uint64_t seed, int rank,
+                                  int64_t* used, int64_t used_stride, float* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    if (!features || !embed || !batch_sizes || !prefix || !lstm_w || !lin_w || !lin_b || !tapes || !X || !workspace) return SAT_ERR_ARG;
+    if (T < 1 || E < 4 || (E & 3) || H < 4 || (H & 3) || V < 1 || num_layers < 1 || num_layers > 8 || rank < 0) return SAT_ERR_ARG;
+    if (T > 1 && (!captions || cap_stride < T - 1 || !used || used_stride < T - 1)) return SAT_ERR_ARG;
+    if (logits && ldl < V) return SAT_ERR_ARG;
+    for (int l = 0; l < num_layers; ++l)
+        for (int k = 0; k < 5; ++k)
+            if (!tapes[5 * l + k] || !lstm_w[4 * l + (k & 3)]) return SAT_ERR_ARG;
+    const int B = batch_sizes[0];
+    long N = 0;
+    for (int t = 0; t < T; ++t) {
+        if (batch_sizes[t] < 1 || (t > 0 && batch_sizes[t] > batch_sizes[t - 1])) return SAT_ERR_ARG;
+        N += batch_sizes[t];
+    }
+    if (ws_bytes < sat_ss_decoder_fwd_ws_bytes(B, V)) return SAT_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    // the teacher-forced inputs of every step (features, then embed[captions[b][t-1]]); draws overwrite rows step by step
+    SAT_TRY(sat_embed_concat_fwd(features, embed, T > 1 ? captions : nullptr, cap_stride, prefix, T, (int)N, B, E, V, X, stream));
+    if (T > 1) {
+        hipLaunchKernelGGL(ss_init_used_kernel, dim3(sat_cdiv((long)B * (T - 1), 256)), dim3(256), 0, s, captions, (long)cap_stride, B,
+                           T - 1, used, (long)used_stride);
+        SAT_LAUNCH_CHECK();
+    }
+    for (int l = 0; l < num_layers; ++l) {                      // h_{-1} = c_{-1} = 0
+        hipError_t e = hipMemsetAsync(tapes[5 * l + 3], 0, (size_t)B * H * sizeof(float), s);
+        if (e == hipSuccess) e = hipMemsetAsync(tapes[5 * l + 4], 0, (size_t)B * H * sizeof(float), s);
+        if (e != hipSuccess) return (int)e;
+    }
+    long off = 0;
+    for (int t = 0; t < T; ++t) {
+        const int n = batch_sizes[t];
+        const int n_next = (t + 1 < T) ? batch_sizes[t + 1] : 0;
+        const float* inp = X + off * E;
+        int In = E;
+        for (int l = 0; l < num_layers; ++l) {
+            float* GA = tapes[5 * l], *CS = tapes[5 * l + 1], *HS = tapes[5 * l + 2], *HP = tapes[5 * l + 3], *cst = tapes[5 * l + 4];
+            // gates = h_{t-1} W_hh^T + x_t W_ih^T + b_ih + b_hh and the cell update in one launch; tapes GA (activated), CS, HS at
+            // the rows of step t and h_t into HP's rows of step t+1, as sat_lstm_fwd's per-step form leaves them
+            SAT_TRY(sat_skinny_lstm(HP + off * H, lstm_w[4 * l + 1], inp, lstm_w[4 * l], In, lstm_w[4 * l + 2], lstm_w[4 * l + 3],
+                                    nullptr, 0, n, H, cst, GA + off * 4 * H, 4L * H, CS + off * H, HS + off * H,
+                                    n_next ? HP + (off + n) * H : nullptr, n_next, s));
+            inp = HS + off * H;
+            In = H;
+        }
+        float* lg = logits ? logits + off * ldl : nullptr;
+        if (t >= 1 && t + 1 < T) {
+            // the input of step t+1 >= 2: a draw from this step's logits where mask(b, t+1) holds, the teacher's token elsewhere
+            SAT_TRY(sample_step(inp, lin_w, lin_b, n, n_next, H, V, lg, ldl, ss_prob, seed, t + 1, rank, captions + t, cap_stride,
+                                used + t, used_stride, embed, E, X + (off + n) * E, workspace, s));
+        } else if (lg) {
+            // step 0 (its successor's input, <start>, is never replaced) and the last step: logits only
+            SAT_TRY(sat_skinny_store(inp, H, lin_w, H, 0, n, V, H, 1, lg, ldl, 0, lin_b, s));
+        }
+        off += n;
+    }
+    return SAT_OK;
+}

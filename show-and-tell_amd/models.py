@@ -579,6 +579,65 @@ def decoder_forward_tapes(lib, features, embed_w, lstm_layers, lin_w, lin_b, cap
     return logits, tapes
 
 
+def draw_ss_seed():
+    """The 63-bit seed of one scheduled-sampling forward, from torch's CPU default generator (`torch.manual_seed` reproduces a run)"""
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+
+
+def decoder_forward_ss_tapes(lib, features, embed_w, lstm_layers, lin_w, lin_b, captions, pi, ss_prob, seed, rank=0,
+                             store_logits=True, logits=None, ce=None, lstm_ws=None):
+    """decoder_forward_tapes with scheduled sampling (models.py:38 `ss_prob`, train.py:109-113): the input of step t >= 2 is, with
+    probability ss_prob, a token drawn from softmax(logits of step t-1) instead of captions[:, t-1] (`sat_ss_decoder_fwd`, one
+    library call for the whole loop; the draws are functions of (seed, rank, row, step, token), include/sat_hip.h).
+    Returns (logits, tapes, used): `used` [B, T-1] int64 the tokens actually fed; tapes["captions"] is `used`, so
+    decoder_backward_tapes is the backward unchanged.  store_logits=False: draws only, no f32 logits (the bf16 throughput mode,
+    `ce`, projects every row afterwards with sat_vocab_ce_fwd_bf16 into `logits`).  `lstm_ws`: as decoder_forward_tapes (only the
+    forward status words are touched: the loop has no persistent recurrence, they report a clean run)."""
+    dev = features.device
+    E = embed_w.shape[1]
+    V = lin_w.shape[0]
+    N, T, B = pi.N, pi.T, pi.B
+    st = L.stream()
+    if captions.dtype != torch.int64 or captions.stride(1) != 1:
+        captions = captions.long().contiguous()
+    if captions.shape[1] < T - 1:
+        raise ValueError("captions has %d columns but lengths need %d" % (captions.shape[1], T - 1))
+    X = torch.empty(N, E, device=dev)
+    used = torch.empty(B, max(T - 1, 1), dtype=torch.int64, device=dev)[:, :T - 1]
+    tapes = {"X": [X], "layers": [], "captions": used}
+    ptrs = []
+    for (w_ih, w_hh, b_ih, b_hh) in lstm_layers:
+        H = w_hh.shape[1]
+        GA, CS, HS, HP = (torch.empty(N, 4 * H, device=dev), torch.empty(N, H, device=dev), torch.empty(N, H, device=dev),
+                          torch.empty(N, H, device=dev))
+        cst = torch.empty(B, H, device=dev)
+        tapes["layers"].append((GA, CS, HP))
+        tapes["X"].append(HS)
+        ptrs += [GA.data_ptr(), CS.data_ptr(), HS.data_ptr(), HP.data_ptr(), cst.data_ptr()]
+    import ctypes as _C
+    wflat = [t.data_ptr() for layer in lstm_layers for t in layer]
+    H = lstm_layers[0][1].shape[1]
+    if logits is None:
+        logits = torch.zeros(N, (V + 3) // 4 * 4, device=dev) if V % 4 else torch.empty(N, V, device=dev)
+    wsb = lib.sat_ss_decoder_fwd_ws_bytes(B, V)
+    ws = torch.empty(max(wsb // 4, 4), device=dev)
+    L.check(lib.sat_ss_decoder_fwd(L.ptr(features), L.ptr(embed_w), captions.data_ptr() if T > 1 else None, captions.stride(0),
+                                   pi.bs_c, L.ptr(pi.prefix_dev), T, E, V, (_C.c_void_p * len(wflat))(*wflat), len(lstm_layers), H,
+                                   L.ptr(lin_w), L.ptr(lin_b), (_C.c_void_p * len(ptrs))(*ptrs), L.ptr(X),
+                                   L.ptr(logits) if store_logits else None, logits.stride(0), float(ss_prob), int(seed), int(rank),
+                                   used.data_ptr() if T > 1 else None, used.stride(0), L.ptr(ws), wsb, st), "sat_ss_decoder_fwd")
+    if lstm_ws is not None:
+        for li, (w_ih, w_hh, _, _) in enumerate(lstm_layers):
+            soff = lib.sat_lstm_fwd_status_offset(B, w_hh.shape[1])
+            if soff >= 0 and lib.sat_lstm_fwd_ws_bytes(B, w_hh.shape[1]) > 0:
+                lstm_ws[li][0][soff:soff + 64].zero_()
+    if ce is not None and ce.get("kind") == "bf16":
+        L.check(lib.sat_vocab_ce_fwd_bf16(L.ptr(tapes["X"][-1]), L.ptr(lin_w), L.ptr(lin_b), L.ptr(ce["targets"]), N, lin_w.shape[1],
+                                          V, float(ce["inv_denom"]), L.ptr(logits), logits.stride(0), L.ptr(ce["row_loss"]),
+                                          L.ptr(ce["loss_out"]), L.ptr(ce["ws"]), ce["ws"].numel(), st), "sat_vocab_ce_fwd_bf16")
+    return logits, tapes, used
+
+
 def decoder_backward_tapes(lib, dlogits, tapes, embed_w, lstm_layers, lin_w, pi, grads_out, on_stage=None, ce=None, mixed_ws=None,
                            lstm_ws=None):
     """Backward of decoder_forward_tapes.  `dlogits`: f32 [N, ld] with ld = V rounded up to 4 and zero pad columns.  grads_out: dict name -> preallocated f32 tensor to fill:
@@ -637,10 +696,14 @@ def decoder_backward_tapes(lib, dlogits, tapes, embed_w, lstm_layers, lin_w, pi,
 
 class _DecoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, features, captions, pi, num_layers, embed_w, lin_w, lin_b, *lstm_flat):
+    def forward(ctx, features, captions, pi, ss, num_layers, embed_w, lin_w, lin_b, *lstm_flat):
         lib = L.load()
         layers = [tuple(lstm_flat[4 * l:4 * l + 4]) for l in range(num_layers)]
-        logits, tapes = decoder_forward_tapes(lib, features, embed_w, layers, lin_w, lin_b, captions, pi)
+        if ss is not None:              # scheduled sampling: ss = dict(prob, seed, rank); receives "used"
+            logits, tapes, ss["used"] = decoder_forward_ss_tapes(lib, features, embed_w, layers, lin_w, lin_b, captions, pi,
+                                                                 ss["prob"], ss["seed"], ss["rank"])
+        else:
+            logits, tapes = decoder_forward_tapes(lib, features, embed_w, layers, lin_w, lin_b, captions, pi)
         ctx.tapes, ctx.pi, ctx.layers = tapes, pi, layers
         ctx.embed_w, ctx.lin_w = embed_w, lin_w
         V = lin_w.shape[0]
@@ -668,7 +731,7 @@ class _DecoderFn(torch.autograd.Function):
         flat = []
         for l in range(len(layers)):
             flat += [g[("w_ih", l)], g[("w_hh", l)], g[("b_ih", l)], g[("b_hh", l)]]
-        return (g["features"], None, None, None, g["embed"], g["lin_w"], g["lin_b"], *flat)
+        return (g["features"], None, None, None, None, g["embed"], g["lin_w"], g["lin_b"], *flat)
 
 
 class DecoderRNN(nn.Module):
@@ -680,7 +743,9 @@ class DecoderRNN(nn.Module):
         self.lstm = _LSTMParams(embed_size, hidden_size, num_layers)     # nn.LSTM(batch_first) (models.py:36)
         self.linear = _Weight(vocab_size, hidden_size, bias=vocab_size)  # nn.Linear (models.py:37)
         self.embed_size, self.hidden_size, self.vocab_size, self.num_layers = embed_size, hidden_size, vocab_size, num_layers
-        self.ss_prob = 0                                                 # inert in the reference too (models.py:38)
+        self.ss_prob = 0                  # scheduled sampling (models.py:38; schedule: trainer.ss_prob_for_epoch), training mode only
+        self.ss_rank = 0                  # data-parallel rank: a stream of draws of its own per rank
+        self.last_ss_inputs = self.last_ss_seed = None   # tokens fed [B, T-1] and seed of the last sampled forward
         self._id_guard = None
         self.init_weights()
 
@@ -704,7 +769,9 @@ class DecoderRNN(nn.Module):
 
     def forward(self, features, captions, lengths):
         """Decode image feature vectors and generate caption logits (models.py:47-54): f32 [sum(lengths), V],
-        rows in time-major packed order."""
+        rows in time-major packed order.  In training mode with ss_prob > 0 the input of step t >= 2 is, with probability
+        ss_prob, a token drawn from softmax(logits of step t-1) (scheduled sampling; seed drawn from torch's CPU generator);
+        the tokens fed and the seed are kept as `last_ss_inputs` / `last_ss_seed`."""
         features = _f32c(features, "features")
         L.require_gpu(captions, "captions")
         if len(lengths) != features.shape[0]:
@@ -716,8 +783,14 @@ class DecoderRNN(nn.Module):
             captions = captions.long().contiguous()
         if pi.T > 1:
             self.id_guard().submit(captions, pi.T - 1, self.vocab_size, "captions")
-        return _DecoderFn.apply(features, captions, pi, self.num_layers, self.embed.weight, self.linear.weight,
-                                self.linear.bias, *self._lstm_flat())
+        ss = None
+        if self.training and self.ss_prob > 0:
+            ss = dict(prob=float(self.ss_prob), seed=draw_ss_seed(), rank=int(self.ss_rank))
+        out = _DecoderFn.apply(features, captions, pi, ss, self.num_layers, self.embed.weight, self.linear.weight,
+                               self.linear.bias, *self._lstm_flat())
+        if ss is not None:
+            self.last_ss_inputs, self.last_ss_seed = ss["used"], ss["seed"]
+        return out
 
     @torch.no_grad()
     def sample(self, features, states=None):

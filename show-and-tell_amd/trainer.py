@@ -16,7 +16,8 @@ as each bucket's gradients become final and overlapped with the rest of the back
 import torch
 
 from . import _lib as L
-from .models import BN1D_MOMENTUM, BN_EPS, ShowAndTell, decoder_backward_tapes, decoder_forward_tapes
+from .models import (BN1D_MOMENTUM, BN_EPS, ShowAndTell, decoder_backward_tapes, decoder_forward_ss_tapes, decoder_forward_tapes,
+                     draw_ss_seed)
 from .pack import PackInfo
 
 
@@ -33,6 +34,14 @@ def lr_for_epoch(epoch, learning_rate=1e-3, decay_start=1, decay_every=3, decay_
     if epoch > decay_start and decay_start >= 1:
         return learning_rate * decay_rate ** ((epoch - decay_start) // decay_every)
     return learning_rate
+
+
+def ss_prob_for_epoch(epoch, start=-1, increase_every=5, increase_prob=0.05, max_prob=0.25):
+    """Scheduled-sampling probability of an epoch: the reference trainer's commented-out schedule (train.py:109-113; defaults
+    config.py:50-57).  Before `start` (and with start < 0, the default: off) the probability is the initial 0."""
+    if epoch > start and start >= 0:
+        return min(increase_prob * ((epoch - start) // increase_every), max_prob)
+    return 0.0
 
 
 def _pad4(n):
@@ -247,9 +256,19 @@ class TrainStep:
                 need = max(lib.sat_lstm_mixed_ws_bytes(N, E if l == 0 else dec.hidden_size, dec.hidden_size) for l in range(dec.num_layers))
                 bufs["lstm_mixed_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
             mixed_ws = bufs["lstm_mixed_ws"]
-        logits, tapes = decoder_forward_tapes(lib, feats_in, dec.embed.weight, layers, dec.linear.weight,
-                                              dec.linear.bias, captions[:, :-1], pi, logits=bufs["logits"], ce=ce, mixed_ws=mixed_ws,
-                                              lstm_ws=bufs["lstm_ws"])
+        if dec.ss_prob > 0:
+            # scheduled sampling (model.training is required above): the step loop with its draws; exact-f32 logits for sat_ce_rows,
+            # or in the bf16 mode draws only and the mode's projection + CE over every row (`ce`)
+            seed = draw_ss_seed()
+            logits, tapes, used = decoder_forward_ss_tapes(lib, feats_in, dec.embed.weight, layers, dec.linear.weight, dec.linear.bias,
+                                                           captions[:, :-1], pi, dec.ss_prob, seed, rank=dec.ss_rank,
+                                                           store_logits=ce is None, logits=bufs["logits"], ce=ce,
+                                                           lstm_ws=bufs["lstm_ws"])
+            dec.last_ss_inputs, dec.last_ss_seed = used, seed
+        else:
+            logits, tapes = decoder_forward_tapes(lib, feats_in, dec.embed.weight, layers, dec.linear.weight,
+                                                  dec.linear.bias, captions[:, :-1], pi, logits=bufs["logits"], ce=ce, mixed_ws=mixed_ws,
+                                                  lstm_ws=bufs["lstm_ws"])
         if ce is None:
             # ---- loss + d(loss)/d(logits) in place (train.py:143) ----
             L.check(lib.sat_ce_rows(L.ptr(logits), logits.stride(0), L.ptr(bufs["targets"]), N, V, float(inv_denom), 1,
@@ -471,6 +490,9 @@ class DataParallelStep:
         self.engine = engine
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
+        dec = getattr(getattr(engine, "model", None), "decoder", None)
+        if dec is not None and hasattr(dec, "ss_rank"):       # scheduled sampling: every rank draws from a stream of its own
+            dec.ss_rank = dist.get_rank(process_group) if dist.is_initialized() else 0
         # The bucket all-reduces overlap the rest of the backward: c10d `async_op=True` as each bucket's gradients become final,
         # `wait()` before clamp + Adam.  (Measured on ONE rank, where RCCL launches no kernel -- bench.py --force-dist, round 3: any
         # DEFERRED wait costs 0.4-0.5 ms of a 4.5 ms step, whatever the form -- a communication stream of our own, one bucket or
