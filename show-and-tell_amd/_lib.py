@@ -37,7 +37,8 @@ class SatBnRunningItem(C.Structure):
 
 
 class SatOp(C.Structure):
-    """mirror of `struct sat_op` (include/sat_hip.h)"""
+    """mirror of `struct sat_op` (include/sat_hip.h); no instance attributes besides the fields, so a misspelt field raises"""
+    __slots__ = ()
     _fields_ = [
         ("kind", C.c_int32), ("dtype", C.c_int32),
         ("in0", _vp), ("in1", _vp), ("out", _vp), ("w", _vp),
@@ -56,6 +57,11 @@ class SatOp(C.Structure):
         ("reserved1", C.c_int32 * 2),
         ("pad_w", C.c_int32), ("groups", C.c_int32), ("ldc", C.c_int64), ("out1", C.c_void_p),
     ]
+
+
+def op(kind, dtype, **fields):
+    """one `SatOp`: tensors given for pointer fields stand for their `data_ptr()`; a name that is not a field raises"""
+    return SatOp(kind=kind, dtype=dtype, **{k: v.data_ptr() if hasattr(v, "data_ptr") else v for k, v in fields.items()})
 
 
 # name -> (restype, argtypes): every symbol include/sat_hip.h declares

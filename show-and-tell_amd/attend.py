@@ -26,6 +26,7 @@ from . import _lib as L
 from . import tune as T
 from .models import IdGuard
 from .pack import PackInfo
+from .program import act_op, avgpool, conv_op, image_prep, tdtype
 
 VGG16_FEATURES = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512]    # vgg16.features[:-3]
 
@@ -67,7 +68,7 @@ class VggProgram:
 
     def __init__(self, stack, N, H, W, dtype, device):
         self.N, self.H, self.W, self.dtype, self.stack = N, H, W, dtype, stack
-        td = torch.bfloat16 if dtype == L.SAT_BF16 else torch.float32
+        td = tdtype(dtype)
         ch = 8 if dtype == L.SAT_BF16 else 4
         self.keep, ops = [], []
 
@@ -79,11 +80,7 @@ class VggProgram:
         # 3-channel input: zero-bordered NHWC image with the channels padded to one 16-byte chunk per pixel
         cpad = ch
         self.img_pad = alloc((N, H + 2, W + 2, cpad), zero=True)
-        o = L.SatOp()
-        o.kind, o.dtype = L.OP_IMAGE_PREP, dtype
-        o.out = self.img_pad.data_ptr()
-        o.N, o.Hin, o.Win, o.Hout, o.Wout, o.pad, o.Cout = N, H, W, H + 2, W + 2, 1, cpad
-        ops.append(o)
+        ops += image_prep(dtype, self.img_pad, N, H, W, 1, cout=cpad)
         x, h, w, c = self.img_pad, H, W, cpad
         first = True
         self.layers, self.run_id = [], 0            # (kind, ...) in forward order: the tapes of the backward
@@ -93,11 +90,7 @@ class VggProgram:
         for v in stack.cfg:
             if v == "M":
                 out = alloc((N, h // 2, w // 2, c))
-                o = L.SatOp()
-                o.kind, o.dtype = L.OP_MAXPOOL2, dtype
-                o.in0, o.out = x.data_ptr(), out.data_ptr()
-                o.N, o.Hin, o.Win, o.Cout = N, h, w, c
-                ops.append(o)
+                ops.append(L.op(L.OP_MAXPOOL2, dtype, in0=x, out=out, N=N, Hin=h, Win=w, Cout=c))
                 self.layers.append(("pool", x, out, h, w, c))
                 x, h, w = out, h // 2, w // 2
                 continue
@@ -112,42 +105,24 @@ class VggProgram:
             self.keep += [wk, bias]
             self.wcopies.append((conv, wk, bias, 3 if first else c))
             out = alloc((N, h, w, v))
-            o = L.SatOp()
-            o.kind, o.dtype = L.OP_CONV, dtype
-            o.in0, o.w, o.out = x.data_ptr(), wk.data_ptr(), out.data_ptr()
-            cin = c
-            o.N, o.Cin, o.Hout, o.Wout, o.Cout, o.KH, o.KW, o.stride = N, cin, h, w, v, 3, 3, 1
-            if first:                                    # the border is in the image: no padding arithmetic in the kernel
-                o.Hin, o.Win, o.pad = h + 2, w + 2, 0
-                o.sN, o.sH, o.sW = (h + 2) * (w + 2) * cin, (w + 2) * cin, cin
-            else:
-                o.Hin, o.Win, o.pad = h, w, 1
-                o.sN, o.sH, o.sW = h * w * cin, w * cin, cin
             if v not in ones:
                 ones[v] = alloc((v,), torch.float32)
                 ones[v].fill_(1.0)
+            cin = c
+            # the first conv's border is in the image: no padding arithmetic in the kernel
+            hin, win, pad = (h + 2, w + 2, 0) if first else (h, w, 1)
             if dtype == L.SAT_BF16:                      # bias + ReLU ride in the conv epilogue (out = relu(acc*1 + bias))
-                o.scale1, o.shift1, o.flags = ones[v].data_ptr(), bias.data_ptr(), 1
-                ops.append(o)
+                ops.append(conv_op(dtype, x, wk, out, N, hin, win, cin, h, w, v, 3, 3, 1, pad, scale1=ones[v], shift1=bias, flags=1))
             else:                                        # f32 parity mode: conv, then the elementwise affine + ReLU kernel
                 raw = alloc((N, h, w, v))
-                o.out = raw.data_ptr()
-                ops.append(o)
-                a = L.SatOp()
-                a.kind, a.dtype = L.OP_BN_RELU, dtype
-                a.in0, a.out, a.scale0, a.shift0 = raw.data_ptr(), out.data_ptr(), ones[v].data_ptr(), bias.data_ptr()
-                a.N, a.Hout, a.Wout, a.Cout = N, h, w, v
-                ops.append(a)
+                ops.append(conv_op(dtype, x, wk, raw, N, hin, win, cin, h, w, v, 3, 3, 1, pad))
+                ops.append(act_op(L.OP_BN_RELU, dtype, raw, out, N, h, w, v, scale0=ones[v], shift0=bias))
             self.layers.append(("conv", conv, x, out, h, w, cin, v, first))
             x, c, first = out, v, False
         self.P, self.C = h * w, c
         self.fmap = x
         self.fmean = alloc((N, c), torch.float32)
-        ap = L.SatOp()
-        ap.kind, ap.dtype = L.OP_AVGPOOL, dtype
-        ap.in0, ap.out = x.data_ptr(), self.fmean.data_ptr()
-        ap.N, ap.Hin, ap.Win, ap.Cout = N, h, w, c
-        ops.append(ap)
+        ops.append(avgpool(dtype, x, self.fmean, h, w))
         self.features = self.fmap.view(N, self.P, c) if dtype == L.SAT_F32 else alloc((N, self.P, c), torch.float32)
         self.ops = (L.SatOp * len(ops))(*ops)
         self.n_ops = len(ops)

@@ -7,16 +7,14 @@ Every BasicConv2d = implicit-GEMM conv (asymmetric 1x7 / 7x1 / 1x3 / 3x1 kernels
 statistics in its epilogue + one normalise/ReLU launch that writes straight into the channel slice of the block's
 concatenated output (sat_op.ldc); 3x3 max / average pools are their own small kernels.  Train-mode batch statistics
 (nothing calls .eval() in train.py), integer-atomic statistics in bf16 as on the ResNet path; eval uses the running ones."""
-import os
-
 import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .resnet import _BN, _Conv, ConvStackProgram
+from .program import OpProgram, act_op, avgpool, conv_op, image_prep
+from .resnet import _BN, _Conv
 
 BN_EPS = 1e-3
-BN_MOMENTUM = 0.1
 
 BLOCKS = [("Mixed_5b", "A", 192, 32, 256), ("Mixed_5c", "A", 256, 64, 288), ("Mixed_5d", "A", 288, 64, 288),
           ("Mixed_6a", "B", 288, None, 768), ("Mixed_6b", "C", 768, 128, 768), ("Mixed_6c", "C", 768, 160, 768),
@@ -106,51 +104,24 @@ class InceptionStack(nn.Module):
         return InceptionProgram(self, N, H, W, dtype, training, device, groups=groups, signatures=signatures)
 
 
-class InceptionProgram(ConvStackProgram):
-    """op program of the Inception-v3 stack for one (batch, H, W, dtype, training); `run` / `run_timed` / hipGraph replay are
-    the ResNet program's."""
+class InceptionProgram(OpProgram):
+    """op program of the Inception-v3 stack for one (batch, H, W, dtype, training); groups = G > 1 (bf16): G look-ahead batches
+    per launch, as in the ResNet program -- train mode: `sat_op.groups` = G, every per-batch buffer G consecutive copies,
+    per-group BatchNorm statistics, deferred running statistics; eval mode: the batches concatenate into one program over
+    G * N images."""
+    BN_EPS = BN_EPS
 
     def __init__(self, stack, N, H, W, dtype, training, device, groups=1, signatures=None):
-        """groups = G > 1 (bf16): G look-ahead batches per launch, as in the ResNet program -- train mode: `sat_op.groups` = G, every
-        per-batch buffer G consecutive copies, per-group BatchNorm statistics, deferred running statistics; eval mode: the batches
-        concatenate into one program over G * N images."""
-        self.N, self.H, self.W, self.dtype, self.training, self.stack = N, H, W, dtype, training, stack
-        self.groups = int(groups)
-        self._n_prep = self.groups                         # ops[0 .. groups) are the image preps (ConvStackProgram.run)
-        if self.groups > 1 and dtype != L.SAT_BF16:
-            raise ValueError("grouped programs are for the bf16 stack")
-        Nb = N                                             # images per batch
-        if self.groups > 1 and not training:
-            N, G = self.groups * N, 1
-        else:
-            G = self.groups
+        super().__init__(stack, N, H, W, dtype, training, device, groups=groups, signatures=signatures)
+        N, G = self.n, self.G
         GN = G * N                                         # images every per-image op (pools, image prep, the final pool) sees
-        self.keep, self.bn_list, self.stat_accs, self._want_sigs = [], [], [], dict(signatures or {})
-        td = torch.bfloat16 if dtype == L.SAT_BF16 else torch.float32
         esz = 2 if dtype == L.SAT_BF16 else 4
-        ch = 16 // esz
-        lib = L.load()
-        ops = []
-
-        def alloc(shape, dt=td, zero=False):
-            t = (torch.zeros if zero else torch.empty)(shape, dtype=dt, device=device)
-            self.keep.append(t)
-            return t
-
-        bns = stack.bns()
-        flat = torch.stack([bn.num_batches_tracked.detach().to(device) for bn in bns])
-        for i, bn in enumerate(bns):
-            bn.num_batches_tracked = flat[i]
-        object.__setattr__(stack, "_nbt_flat", flat)
-        atomic = training and dtype == L.SAT_BF16
-        max_part = [0]
-        self.partial = None
-        part_users = []
+        alloc, ops = self.alloc, self.ops
 
         def basic(m, x, h, w, out=None, out_off=0, out_ld=0):
             """BasicConv2d: conv (+ statistics) -> normalise + ReLU into `out` (a dense tensor or a channel slice).
             x: dense NHWC tensor [N,h,w,cin].  Returns (activation tensor or None when sliced, ho, wo)."""
-            cv, bn = m.conv, m.bn
+            cv = m.conv
             cin = x.shape[3]
             ho, wo = (h + 2 * cv.ph - cv.kh) // cv.stride + 1, (w + 2 * cv.pw - cv.kw) // cv.stride + 1
             wt = cv.weight.detach().to(device=device, dtype=torch.float32)
@@ -158,100 +129,31 @@ class InceptionProgram(ConvStackProgram):
                 wp = torch.zeros(cv.cout, cin, cv.kh, cv.kw, device=device)
                 wp[:, :wt.shape[1]] = wt
                 wt = wp
-            wk = wt.permute(0, 2, 3, 1).contiguous().to(td).reshape(cv.cout, -1)
-            raw = alloc((GN, ho, wo, cv.cout))
+            wk = wt.permute(0, 2, 3, 1).contiguous().to(self.td).reshape(cv.cout, -1)
             self.keep.append(wk)
-            o = L.SatOp()
-            o.kind, o.dtype, o.groups = L.OP_CONV, dtype, G
-            o.in0, o.w, o.out = x.data_ptr(), wk.data_ptr(), raw.data_ptr()
-            o.N, o.Hin, o.Win, o.Cin, o.Hout, o.Wout, o.Cout = N, h, w, cin, ho, wo, cv.cout
-            o.KH, o.KW, o.stride, o.pad = cv.kh, cv.kw, cv.stride, cv.ph
-            if cv.ph != cv.pw:
-                o.flags, o.pad_w = L.CONV_PADW, cv.pw
-            o.sN, o.sH, o.sW = h * w * cin, w * cin, cin
-            M = N * ho * wo
-            tiles = lib.sat_conv_tiles_m(M)
-            a = L.SatOp()
-            a.kind, a.dtype, a.groups = L.OP_BN_RELU, dtype, G
-            a.in0 = raw.data_ptr()
-            a.N, a.Hout, a.Wout, a.Cout = N, ho, wo, cv.cout
-            if out is None:
-                act = alloc((GN, ho, wo, cv.cout))
-                a.out = act.data_ptr()
-            else:
-                act = None
-                a.out, a.ldc = out.data_ptr() + out_off * esz, out_ld
-            self.bn_list.append(bn)
-            if not training:                             # eval: running statistics -> (scale, shift) table
-                s, t = alloc((cv.cout,), torch.float32), alloc((cv.cout,), torch.float32)
-                f = L.SatOp()
-                f.kind, f.dtype = L.OP_BN_FINALIZE, dtype
-                f.gamma, f.beta = bn.weight.data_ptr(), bn.bias.data_ptr()
-                f.running_mean, f.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-                f.scale_out, f.shift_out = s.data_ptr(), t.data_ptr()
-                f.Cout, f.count, f.tiles_m, f.training, f.momentum, f.eps = cv.cout, M, 0, 0, BN_MOMENTUM, BN_EPS
-                a.scale0, a.shift0 = s.data_ptr(), t.data_ptr()
-                ops.extend([o, f, a])
-            elif atomic:
-                acc = alloc((G, 2, 2, cv.cout), torch.int64, zero=True)      # [G][2 parities][2][C]
-                self.stat_accs.append(acc)
-                if tiles <= 128:
-                    o.stat_acc = acc.data_ptr()
-                    ops.append(o)
-                else:                                    # many row tiles: per-tile slabs + the wide reducer into the same sums
-                    max_part[0] = max(max_part[0], G * tiles * 2 * cv.cout)
-                    o.tiles_m = tiles
-                    f = L.SatOp()
-                    f.kind, f.dtype, f.groups = L.OP_BN_FINALIZE, dtype, G
-                    f.stat_acc = acc.data_ptr()
-                    f.Cout, f.tiles_m, f.training = cv.cout, tiles, 1
-                    part_users.extend([o, f])
-                    ops.extend([o, f])
-                a.stat_acc = acc.data_ptr()
-                a.gamma, a.beta = bn.weight.data_ptr(), bn.bias.data_ptr()
-                a.running_mean, a.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-                a.count, a.momentum, a.eps = M, BN_MOMENTUM, BN_EPS
-                ops.append(a)
-            else:                                        # f32 training: slabs -> finalize (f64) -> table
-                max_part[0] = max(max_part[0], tiles * 2 * cv.cout)
-                o.tiles_m = tiles
-                s, t = alloc((cv.cout,), torch.float32), alloc((cv.cout,), torch.float32)
-                f = L.SatOp()
-                f.kind, f.dtype = L.OP_BN_FINALIZE, dtype
-                f.gamma, f.beta = bn.weight.data_ptr(), bn.bias.data_ptr()
-                f.running_mean, f.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-                f.scale_out, f.shift_out = s.data_ptr(), t.data_ptr()
-                f.Cout, f.count, f.tiles_m, f.training, f.momentum, f.eps = cv.cout, M, tiles, 1, BN_MOMENTUM, BN_EPS
-                part_users.extend([o, f])
-                a.scale0, a.shift0 = s.data_ptr(), t.data_ptr()
-                ops.extend([o, f, a])
+            raw = alloc((GN, ho, wo, cv.cout))
+            padw = dict(flags=L.CONV_PADW, pad_w=cv.pw) if cv.ph != cv.pw else {}
+            o = conv_op(dtype, x, wk, raw, N, h, w, cin, ho, wo, cv.cout, cv.kh, cv.kw, cv.stride, cv.ph, groups=G, **padw)
+            ops.append(o)
+            src = self.bn_stats(o, m.bn)
+            act = alloc((GN, ho, wo, cv.cout)) if out is None else None
+            dst = act if out is None else out.data_ptr() + out_off * esz
+            ops.append(src.attach(act_op(L.OP_BN_RELU, dtype, raw, dst, N, ho, wo, cv.cout, groups=G, ldc=out_ld)))
             return act, ho, wo
 
         def pool(kind, x, h, w, out=None, out_off=0, out_ld=0):
             c = x.shape[3]
             ho, wo = (h, w) if kind == L.OP_AVGPOOL3 else ((h - 3) // 2 + 1, (w - 3) // 2 + 1)
-            o = L.SatOp()
-            o.kind, o.dtype = kind, dtype
-            o.in0 = x.data_ptr()
-            o.N, o.Hin, o.Win, o.Cout, o.Hout, o.Wout = GN, h, w, c, ho, wo        # per image: the groups concatenate
-            if out is None:
-                res = alloc((GN, ho, wo, c))
-                o.out = res.data_ptr()
-            else:
-                res = None
-                o.out, o.ldc = out.data_ptr() + out_off * esz, out_ld
-            ops.append(o)
+            res = alloc((GN, ho, wo, c)) if out is None else None
+            dst = res if out is None else out.data_ptr() + out_off * esz
+            # per image: the groups concatenate
+            ops.append(L.op(kind, dtype, in0=x, out=dst, N=GN, Hin=h, Win=w, Cout=c, Hout=ho, Wout=wo, ldc=out_ld))
             return res, ho, wo
 
         # ---- program ----
-        cpad = ch
+        cpad = 16 // esz                                 # the 3 image channels padded to one 16-byte chunk per pixel
         self.img = alloc((GN, H, W, cpad), zero=True)
-        for g_ in range(self.groups):                    # one image prep per batch, each into its slice
-            o = L.SatOp()
-            o.kind, o.dtype = L.OP_IMAGE_PREP, dtype
-            o.out = self.img[g_ * Nb:].data_ptr()
-            o.N, o.Hin, o.Win, o.Hout, o.Wout, o.pad, o.Cout = Nb, H, W, H, W, 0, cpad
-            ops.append(o)
+        ops += image_prep(dtype, self.img, self.N, H, W, 0, groups=self.groups, cout=cpad)
         x, h, w = self.img, H, W
         for name in ("Conv2d_1a_3x3", "Conv2d_2a_3x3", "Conv2d_2b_3x3"):
             x, h, w = basic(getattr(stack, name), x, h, w)
@@ -314,24 +216,10 @@ class InceptionProgram(ConvStackProgram):
             assert off == cout, (name, off, cout)
             x, h, w = y, ho, wo
         self.pooled = alloc((GN, stack.feature_dim), torch.float32)
-        apo = L.SatOp()
-        apo.kind, apo.dtype = L.OP_AVGPOOL, dtype
-        apo.in0, apo.out = x.data_ptr(), self.pooled.data_ptr()
-        apo.N, apo.Hin, apo.Win, apo.Cout = GN, h, w, stack.feature_dim
-        ops.append(apo)
-        self.final_map = (x, GN, h, w, stack.feature_dim)
-        if max_part[0]:
-            self.partial = alloc((max_part[0],), torch.float32)
-            for o_ in part_users:
-                o_.stat_partial = self.partial.data_ptr()
-        self.ops = (L.SatOp * len(ops))(*ops)
-        self.n_ops = len(ops)
-        self._parity = 0
-        self._use_graph = os.environ.get("SAT_GRAPH", "1") != "0" and torch.device(device).type == "cuda"
-        self._runs, self._graphs = [0, 0], [None, None]
-        self._running_items = None
-        if self.groups > 1 and training:
-            self.defer_running_stats()
-        # per-geometry kernel selection, as on the ResNet path: the tuner's three fastest variants per geometry, the final choice by
-        # timing whole-program passes (ConvStackProgram._autotune; no activation buffer needs re-randomising: the tuner only times)
-        self._autotune(device, (), alloc)
+        ops.append(avgpool(dtype, x, self.pooled, h, w))
+        # per-geometry kernel selection, as on the ResNet path (no activation buffer needs re-randomising: the tuner only times)
+        self._finish()
+
+    def _eval_bn(self, bn, c, count):
+        """eval: one finalize launch per layer turns the running statistics into a (scale, shift) table"""
+        return self._bn_finalize(bn, c, count, 0, 0)[1]

@@ -53,6 +53,17 @@ int main(){printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(sat_op), offsetof(sat_
     assert [int(x) for x in out] == [C.sizeof(S), S.N.offset, S.sN.offset, S.count.offset, S.eps.offset, C.sizeof(E), E.C.offset]
 
 
+def test_op_constructor_rejects_unknown_fields():
+    """a misspelt sat_op field must raise, never become a Python attribute the kernel does not see"""
+    t = torch.zeros(4)
+    o = L.op(L.OP_CONV, L.SAT_BF16, in0=t, Cout=8, groups=2)
+    assert (o.kind, o.dtype, o.in0, o.Cout, o.groups) == (L.OP_CONV, L.SAT_BF16, t.data_ptr(), 8, 2)
+    with pytest.raises(AttributeError):
+        L.op(L.OP_CONV, L.SAT_BF16, stat_parital=t)
+    with pytest.raises(AttributeError):
+        o.stat_parital = 0
+
+
 def test_argument_errors_are_reported_not_computed():
     lib = L.load()
     # null pointers / bad shapes are rejected before any launch (works without a GPU)
