@@ -213,6 +213,28 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def pad4(n):
+    """n rounded up to 4: the row length of logits and their gradients (rows padded to 4 floats, zero pad columns)"""
+    return (n + 3) // 4 * 4
+
+
+def logits_buffer(N, V, device):
+    """f32 [N, pad4(V)] for N rows of V logits, the pad columns zero"""
+    import torch
+    return torch.zeros(N, pad4(V), device=device) if V % 4 else torch.empty(N, V, device=device)
+
+
+def pad_rows4(d):
+    """d f32 [N, V] as a contiguous [N, pad4(V)] with zero pad columns (an incoming d(loss)/d(logits))"""
+    import torch
+    V = d.shape[1]
+    if V % 4 == 0:
+        return d.contiguous()
+    out = torch.zeros(d.shape[0], pad4(V), device=d.device)
+    out[:, :V] = d
+    return out
+
+
 def require_gpu(t, name="tensor"):
     if not t.is_cuda:
         raise RuntimeError("show-and-tell_amd: %s must live on the MI355X (got a %s tensor); the HIP path has no CPU fallback"

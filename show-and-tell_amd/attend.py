@@ -24,9 +24,9 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import tune as T
-from .models import IdGuard
 from .pack import PackInfo
 from .program import act_op, avgpool, conv_op, image_prep, tdtype
+from .watch import IdGuard
 
 VGG16_FEATURES = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512]    # vgg16.features[:-3]
 
@@ -371,8 +371,8 @@ class _AttendFn(torch.autograd.Function):
         L.check(lib.sat_rows_copy(L.ptr(m.hidden2tout.weight), H, None, 0, E, E, H, Wz.data_ptr() + C * 4, C + H, st), "sat_rows_copy")
         Z = torch.empty(N, E, device=dev)
         _gemm(lib, 0, 0, Zin, C + H, Wz, C + H, Z, E, N, E, C + H, m.context2out.bias, m.hidden2tout.bias)
-        ldl = (V + 3) // 4 * 4
-        logits = torch.zeros(N, ldl, device=dev) if V % 4 else torch.empty(N, V, device=dev)
+        logits = L.logits_buffer(N, V, dev)
+        ldl = logits.shape[1]
         _gemm(lib, 0, 0, Z, E, m.classifier.weight, E, logits, ldl, N, V, E, m.classifier.bias)
         ctx.m, ctx.pi, ctx.captions = m, pi, captions
         ctx.tapes = dict(f2=f2, fmean=fmean, ctx_enc=ctx_enc, h0=h0, c0=c0, PROJ=PROJ, HS=HS, X=X, GATES=GATES, CS=CS, ALPHA=ALPHA,
@@ -652,7 +652,7 @@ def _sample_beam_features(self, features, beam_size=5, states=None, end_id=None,
     Wz = torch.empty(E, C + H, device=dev)
     L.check(lib.sat_rows_copy(L.ptr(m.context2out.weight), C, None, 0, E, E, C, L.ptr(Wz), C + H, st), "sat_rows_copy")
     L.check(lib.sat_rows_copy(L.ptr(m.hidden2tout.weight), H, None, 0, E, E, H, Wz.data_ptr() + C * 4, C + H, st), "sat_rows_copy")
-    ldl = (V + 3) // 4 * 4
+    ldl = L.pad4(V)
     logits = torch.zeros(R, ldl, device=dev)
     scores = torch.full((B, K), float("-inf"), device=dev)
     scores[:, 0] = 0.0

@@ -23,11 +23,8 @@ def attend_backward(m, pi, captions, tp, dlogits, want_dfeat=False):
     P = ALPHA.shape[1]
     C, H, E, V = PROJ.shape[1], HS.shape[1], Z.shape[1], m.vocab_size
     Hin = X.shape[1]
-    ldl = (V + 3) // 4 * 4
-    if dlogits.shape[1] != ldl or not dlogits.is_contiguous():          # rows padded to 4 floats, zero pad
-        pad = torch.zeros(N, ldl, device=dev)
-        pad[:, :V] = dlogits
-        dlogits = pad
+    dlogits = L.pad_rows4(dlogits)
+    ldl = dlogits.shape[1]
     g = {}
     # ---- output_layer (model2.py:80-85), batched over all packed rows ----
     g["classifier.weight"] = torch.empty(V, E, device=dev)

@@ -20,8 +20,9 @@ import torch.nn as nn
 
 from . import _lib as L
 from .pack import PackInfo
+from .decoder import decoder_backward, decoder_forward
 from .resnet import RESNET152, ConvStackProgram, ResNetStack, weights_signature
-from .watch import ResidencyWatch
+from .watch import IdGuard  # noqa: F401  (also imported from here by callers)
 
 BN1D_MOMENTUM = 0.01   # models.py:17
 BN_EPS = 1e-5
@@ -36,6 +37,22 @@ def _f32c(t, name):
 
 # ------------------------------------------------------------------------------------------------------
 # encoder
+def fc_bn1d_forward(lib, pooled, w_fc, b_fc, gamma, beta, running_mean, running_var, training, feats, xhat, rstd, ws):
+    """resnet.fc + BatchNorm1d (models.py:16-17,27-28), sat_fc_bn1d_fwd, into the caller's buffers: feats, xhat f32 [B, E], rstd
+    [E], ws f32 of at least sat_fc_bn1d_ws_bytes"""
+    B, F = pooled.shape
+    L.check(lib.sat_fc_bn1d_fwd(L.ptr(pooled), L.ptr(w_fc), L.ptr(b_fc), L.ptr(gamma), L.ptr(beta), L.ptr(running_mean),
+                                L.ptr(running_var), BN1D_MOMENTUM, BN_EPS, 1 if training else 0, B, F, w_fc.shape[0], L.ptr(feats),
+                                L.ptr(xhat), L.ptr(rstd), L.ptr(ws), ws.numel() * 4, L.stream()), "sat_fc_bn1d_fwd")
+
+
+def fc_bn1d_backward(lib, dy, pooled, xhat, rstd, gamma, dw, db, dg, dbe, ws):
+    """its backward (sat_fc_bn1d_bwd, batch statistics) into the caller's gradient buffers; ws f32 of at least B * E"""
+    B, F = pooled.shape
+    L.check(lib.sat_fc_bn1d_bwd(L.ptr(dy), L.ptr(pooled), L.ptr(xhat), L.ptr(rstd), L.ptr(gamma), B, F, gamma.shape[0], L.ptr(dw),
+                                L.ptr(db), L.ptr(dg), L.ptr(dbe), L.ptr(ws), ws.numel() * 4, L.stream()), "sat_fc_bn1d_bwd")
+
+
 class _HeadFn(torch.autograd.Function):
     """resnet.fc + BatchNorm1d (models.py:16-17,27-28) -- sat_fc_bn1d_fwd / sat_fc_bn1d_bwd."""
 
@@ -45,15 +62,9 @@ class _HeadFn(torch.autograd.Function):
         B, F = pooled.shape
         E = w_fc.shape[0]
         dev = pooled.device
-        feats = torch.empty(B, E, device=dev)
-        xhat = torch.empty(B, E, device=dev)
-        rstd = torch.empty(E, device=dev)
-        wsb = lib.sat_fc_bn1d_ws_bytes(B, F, E)
-        ws = torch.empty(wsb // 4, device=dev)
-        L.check(lib.sat_fc_bn1d_fwd(L.ptr(pooled), L.ptr(w_fc), L.ptr(b_fc), L.ptr(gamma), L.ptr(beta),
-                                    L.ptr(running_mean), L.ptr(running_var), BN1D_MOMENTUM, BN_EPS,
-                                    1 if training else 0, B, F, E, L.ptr(feats), L.ptr(xhat), L.ptr(rstd),
-                                    L.ptr(ws), wsb, L.stream()), "sat_fc_bn1d_fwd")
+        feats, xhat, rstd = torch.empty(B, E, device=dev), torch.empty(B, E, device=dev), torch.empty(E, device=dev)
+        ws = torch.empty(lib.sat_fc_bn1d_ws_bytes(B, F, E) // 4, device=dev)
+        fc_bn1d_forward(lib, pooled, w_fc, b_fc, gamma, beta, running_mean, running_var, training, feats, xhat, rstd, ws)
         ctx.save_for_backward(pooled, xhat, rstd, gamma)
         ctx.training = training
         return feats
@@ -62,20 +73,12 @@ class _HeadFn(torch.autograd.Function):
     def backward(ctx, dy):
         if not ctx.training:
             raise RuntimeError("EncoderCNN backward is only defined in training mode (batch statistics)")
-        lib = L.load()
         pooled, xhat, rstd, gamma = ctx.saved_tensors
         B, F = pooled.shape
         E = gamma.shape[0]
         dev = pooled.device
-        dy = dy.contiguous()
-        dw = torch.empty(E, F, device=dev)
-        db = torch.empty(E, device=dev)
-        dg = torch.empty(E, device=dev)
-        dbe = torch.empty(E, device=dev)
-        ws = torch.empty(B * E, device=dev)
-        L.check(lib.sat_fc_bn1d_bwd(L.ptr(dy), L.ptr(pooled), L.ptr(xhat), L.ptr(rstd), L.ptr(gamma), B, F, E,
-                                    L.ptr(dw), L.ptr(db), L.ptr(dg), L.ptr(dbe), L.ptr(ws), B * E * 4, L.stream()),
-                "sat_fc_bn1d_bwd")
+        dw, db, dg, dbe = torch.empty(E, F, device=dev), torch.empty(E, device=dev), torch.empty(E, device=dev), torch.empty(E, device=dev)
+        fc_bn1d_backward(L.load(), dy.contiguous(), pooled, xhat, rstd, gamma, dw, db, dg, dbe, torch.empty(B * E, device=dev))
         return None, dw, db, dg, dbe, None, None, None
 
 
@@ -412,85 +415,6 @@ class EncoderCNN(nn.Module):
 
 # ------------------------------------------------------------------------------------------------------
 # decoder
-def _watch_lstm(dev, ws, offset):
-    """The persistent LSTM recurrence (`sat_lstm_persist.hip`) needs all its workgroups resident at once and bounds every
-    hand-off wait; when a wait runs out the kernel sets the STATUS WORD of its workspace and drains -- the tapes and `HS` of that
-    call are garbage.  `watch.ResidencyWatch` reads the word back behind every call and raises RuntimeError (at the latest one
-    call later) after switching the process to one launch per step (`sat_lstm_persist_enable(0)`), which needs no co-residency.
-    ws: the uint8 workspace the call just ran with; offset: sat_lstm_fwd_status_offset / sat_lstm_bwd_status_offset."""
-    ResidencyWatch.get(dev).submit(ws[offset:offset + 4].view(torch.int32), "the persistent LSTM recurrence",
-                                   lambda: L.load().sat_lstm_persist_enable(0))
-
-
-_WS_CACHE = {}
-
-
-def _persistent_ws(dev, nbytes, tag):
-    """A uint8 workspace that the same (device, stream, size, role) gets again on every call: the persistent backward recurrence tags
-    its exchange granules per call instead of clearing 17 MB per step.  The invariant behind that -- no foreign bit pattern in the
-    exchange region -- is the LIBRARY's (include/sat_hip.h, sat_lstm_bwd_ws_bytes_full: it clears a buffer the first time it sees
-    its address); all this side owes it is `sat_lstm_ws_release` when a buffer goes away."""
-    key = (str(dev), int(nbytes), tag, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _WS_CACHE.get(key)
-    if ws is None:
-        if len(_WS_CACHE) >= 16:
-            old = _WS_CACHE.pop(next(iter(_WS_CACHE)))
-            L.load().sat_lstm_ws_release(old.data_ptr())
-        ws = _WS_CACHE[key] = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-    return ws
-
-
-class IdGuard:
-    """Out-of-range caption ids.  `nn.Embedding` (models.py:49) and `nn.CrossEntropyLoss` (train.py:143) raise on an id
-    outside [0, V); the gather / CE kernels here clamp such ids for memory safety only, so every batch is range-checked
-    on the device (`sat_validate_ids`, one tiny launch) and the verdict is read back WITHOUT stalling the stream: the
-    status word is copied to pinned host memory behind the check and looked at when the next batch is submitted (or
-    at once with `poll(block=True)`).  A corrupt caption therefore raises at the latest one step later."""
-
-    DEPTH = 4     # verdicts in flight: the host may run this many submits ahead of the GPU without waiting
-
-    def __init__(self, device):
-        self.status = torch.zeros(1, dtype=torch.int32, device=device)       # sticky: only a raise clears it
-        self.host = torch.zeros(self.DEPTH, dtype=torch.int32).pin_memory()
-        self.pending = []           # (slot, event, description), oldest first
-        self.slot = 0
-
-    def submit(self, ids, ncols, V, what):
-        self.poll(block=False)
-        if ids.dim() != 2 or ids.dtype != torch.int64 or ids.stride(1) != 1:
-            raise TypeError("%s must be an int64 matrix with contiguous rows" % what)
-        while len(self.pending) >= self.DEPTH:
-            self._retire(block=True)
-        L.check(L.load().sat_validate_ids(ids.data_ptr(), ids.stride(0), ids.shape[0], min(int(ncols), ids.shape[1]), 0, int(V),
-                                          self.status.data_ptr(), L.stream()), "sat_validate_ids")
-        slot = self.slot
-        self.slot = (slot + 1) % self.DEPTH
-        self.host[slot:slot + 1].copy_(self.status, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.pending.append((slot, ev, "%s: id outside [0, %d)" % (what, V)))
-
-    def _retire(self, block):
-        slot, ev, what = self.pending[0]
-        if block:
-            ev.synchronize()
-        elif not ev.query():
-            return False
-        self.pending.pop(0)
-        if int(self.host[slot]) != 0:
-            torch.cuda.current_stream().synchronize()
-            self.status.zero_()
-            self.host.zero_()
-            self.pending.clear()
-            raise IndexError("show-and-tell_amd: %s (nn.Embedding / CrossEntropyLoss would raise here: "
-                             "models.py:49, train.py:143)" % what)
-        return True
-
-    def poll(self, block=False):
-        while self.pending and self._retire(block):
-            pass
-
-
 class _LSTMParams(nn.Module):
     """Parameter holder with nn.LSTM's names and default init U(-1/sqrt(H), 1/sqrt(H)) (models.py:36)."""
 
@@ -516,222 +440,29 @@ class _Weight(nn.Module):
             self.bias = nn.Parameter(torch.zeros(bias))
 
 
-def decoder_forward_tapes(lib, features, embed_w, lstm_layers, lin_w, lin_b, captions, pi, logits=None, ce=None, mixed_ws=None,
-                          lstm_ws=None):
-    """embed+cat+pack -> L x LSTM -> vocab logits (models.py:49-53).  Returns (logits, tapes).
-    `ce` = dict(kind="bf16", targets, inv_denom, row_loss, loss_out, ws): the projection on the bf16 matrix pipe and the cross
-    entropy (train.py:143) as one call (`sat_vocab_ce_fwd_bf16`), d(loss)/d(logits) left in `ws` for the backward.
-    `lstm_ws`: per layer (forward workspace, backward workspace) uint8 tensors the CALLER owns and watches (`TrainStep`: it
-    folds their status words into its step's fault flag); None: workspaces of this module, each call's status word handed to
-    `watch.ResidencyWatch`."""
-    dev = features.device
-    E = embed_w.shape[1]
-    V = lin_w.shape[0]
-    N, T, B = pi.N, pi.T, pi.B
-    st = L.stream()
-    X = torch.empty(N, E, device=dev)
-    cap_ptr, cap_stride = (None, 0)
-    if T > 1:
-        if captions.dtype != torch.int64 or captions.stride(1) != 1:
-            captions = captions.long().contiguous()
-        if captions.shape[1] < T - 1:
-            raise ValueError("captions has %d columns but lengths need %d" % (captions.shape[1], T - 1))
-        cap_ptr, cap_stride = captions.data_ptr(), captions.stride(0)
-    L.check(lib.sat_embed_concat_fwd(L.ptr(features), L.ptr(embed_w), cap_ptr, cap_stride, L.ptr(pi.prefix_dev),
-                                     T, N, B, E, embed_w.shape[0], L.ptr(X), st), "sat_embed_concat_fwd")
-    tapes = {"X": [X], "layers": [], "captions": captions}
-    inp = X
-    for (w_ih, w_hh, b_ih, b_hh) in lstm_layers:
-        H = w_hh.shape[1]
-        In = w_ih.shape[1]
-        GA = torch.empty(N, 4 * H, device=dev)
-        CS = torch.empty(N, H, device=dev)
-        HS = torch.empty(N, H, device=dev)
-        HP = torch.empty(N, H, device=dev)
-        cst = torch.empty(B, H, device=dev)
-        wsb = lib.sat_lstm_fwd_ws_bytes(B, H)            # hidden-state exchange of the persistent recurrence
-        li = len(tapes["layers"])
-        ws = lstm_ws[li][0] if lstm_ws is not None else torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-        if mixed_ws is not None:          # bf16 throughput mode: the x-gates GEMM on the bf16 matrix pipe
-            L.check(lib.sat_lstm_fwd_bf16(L.ptr(inp), L.ptr(w_ih), L.ptr(w_hh), L.ptr(b_ih), L.ptr(b_hh), pi.bs_c, T, In, H,
-                                          L.ptr(GA), L.ptr(CS), L.ptr(HS), L.ptr(HP), L.ptr(cst), L.ptr(ws), wsb, L.ptr(mixed_ws),
-                                          mixed_ws.numel(), st), "sat_lstm_fwd_bf16")
-        else:
-            L.check(lib.sat_lstm_fwd(L.ptr(inp), L.ptr(w_ih), L.ptr(w_hh), L.ptr(b_ih), L.ptr(b_hh), pi.bs_c, T, In, H,
-                                     L.ptr(GA), L.ptr(CS), L.ptr(HS), L.ptr(HP), L.ptr(cst), L.ptr(ws), wsb, st), "sat_lstm_fwd")
-        soff = lib.sat_lstm_fwd_status_offset(B, H)
-        if soff >= 0 and wsb > 0 and lstm_ws is None:
-            _watch_lstm(dev, ws, soff)                   # the recurrence's status word: raises (at the latest one call later)
-        tapes["layers"].append((GA, CS, HP))
-        tapes["X"].append(HS)
-        inp = HS
-    if logits is None:
-        logits = torch.zeros(N, (V + 3) // 4 * 4, device=dev) if V % 4 else torch.empty(N, V, device=dev)
-    if ce is not None and ce.get("kind") == "bf16":
-        # bf16 throughput mode: the projection on the bf16 matrix pipe (f32 accumulate, f32 logits), CE in f32 from them,
-        # d(loss)/d(logits) left as bf16 in the workspace for decoder_backward_tapes
-        L.check(lib.sat_vocab_ce_fwd_bf16(L.ptr(inp), L.ptr(lin_w), L.ptr(lin_b), L.ptr(ce["targets"]), N, lin_w.shape[1], V,
-                                          float(ce["inv_denom"]), L.ptr(logits), logits.stride(0), L.ptr(ce["row_loss"]),
-                                          L.ptr(ce["loss_out"]), L.ptr(ce["ws"]), ce["ws"].numel(), st), "sat_vocab_ce_fwd_bf16")
-        return logits, tapes
-    L.check(lib.sat_vocab_logits_fwd(L.ptr(inp), L.ptr(lin_w), L.ptr(lin_b), N, lin_w.shape[1], V, L.ptr(logits),
-                                     logits.stride(0), st), "sat_vocab_logits_fwd")
-    return logits, tapes
-
-
 def draw_ss_seed():
     """The 63-bit seed of one scheduled-sampling forward, from torch's CPU default generator (`torch.manual_seed` reproduces a run)"""
     return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
 
 
-def decoder_forward_ss_tapes(lib, features, embed_w, lstm_layers, lin_w, lin_b, captions, pi, ss_prob, seed, rank=0,
-                             store_logits=True, logits=None, ce=None, lstm_ws=None):
-    """decoder_forward_tapes with scheduled sampling (models.py:38 `ss_prob`, train.py:109-113): the input of step t >= 2 is, with
-    probability ss_prob, a token drawn from softmax(logits of step t-1) instead of captions[:, t-1] (`sat_ss_decoder_fwd`, one
-    library call for the whole loop; the draws are functions of (seed, rank, row, step, token), include/sat_hip.h).
-    Returns (logits, tapes, used): `used` [B, T-1] int64 the tokens actually fed; tapes["captions"] is `used`, so
-    decoder_backward_tapes is the backward unchanged.  store_logits=False: draws only, no f32 logits (the bf16 throughput mode,
-    `ce`, projects every row afterwards with sat_vocab_ce_fwd_bf16 into `logits`).  `lstm_ws`: as decoder_forward_tapes (only the
-    forward status words are touched: the loop has no persistent recurrence, they report a clean run)."""
-    dev = features.device
-    E = embed_w.shape[1]
-    V = lin_w.shape[0]
-    N, T, B = pi.N, pi.T, pi.B
-    st = L.stream()
-    if captions.dtype != torch.int64 or captions.stride(1) != 1:
-        captions = captions.long().contiguous()
-    if captions.shape[1] < T - 1:
-        raise ValueError("captions has %d columns but lengths need %d" % (captions.shape[1], T - 1))
-    X = torch.empty(N, E, device=dev)
-    used = torch.empty(B, max(T - 1, 1), dtype=torch.int64, device=dev)[:, :T - 1]
-    tapes = {"X": [X], "layers": [], "captions": used}
-    ptrs = []
-    for (w_ih, w_hh, b_ih, b_hh) in lstm_layers:
-        H = w_hh.shape[1]
-        GA, CS, HS, HP = (torch.empty(N, 4 * H, device=dev), torch.empty(N, H, device=dev), torch.empty(N, H, device=dev),
-                          torch.empty(N, H, device=dev))
-        cst = torch.empty(B, H, device=dev)
-        tapes["layers"].append((GA, CS, HP))
-        tapes["X"].append(HS)
-        ptrs += [GA.data_ptr(), CS.data_ptr(), HS.data_ptr(), HP.data_ptr(), cst.data_ptr()]
-    import ctypes as _C
-    wflat = [t.data_ptr() for layer in lstm_layers for t in layer]
-    H = lstm_layers[0][1].shape[1]
-    if logits is None:
-        logits = torch.zeros(N, (V + 3) // 4 * 4, device=dev) if V % 4 else torch.empty(N, V, device=dev)
-    wsb = lib.sat_ss_decoder_fwd_ws_bytes(B, V)
-    ws = torch.empty(max(wsb // 4, 4), device=dev)
-    L.check(lib.sat_ss_decoder_fwd(L.ptr(features), L.ptr(embed_w), captions.data_ptr() if T > 1 else None, captions.stride(0),
-                                   pi.bs_c, L.ptr(pi.prefix_dev), T, E, V, (_C.c_void_p * len(wflat))(*wflat), len(lstm_layers), H,
-                                   L.ptr(lin_w), L.ptr(lin_b), (_C.c_void_p * len(ptrs))(*ptrs), L.ptr(X),
-                                   L.ptr(logits) if store_logits else None, logits.stride(0), float(ss_prob), int(seed), int(rank),
-                                   used.data_ptr() if T > 1 else None, used.stride(0), L.ptr(ws), wsb, st), "sat_ss_decoder_fwd")
-    if lstm_ws is not None:
-        for li, (w_ih, w_hh, _, _) in enumerate(lstm_layers):
-            soff = lib.sat_lstm_fwd_status_offset(B, w_hh.shape[1])
-            if soff >= 0 and lib.sat_lstm_fwd_ws_bytes(B, w_hh.shape[1]) > 0:
-                lstm_ws[li][0][soff:soff + 64].zero_()
-    if ce is not None and ce.get("kind") == "bf16":
-        L.check(lib.sat_vocab_ce_fwd_bf16(L.ptr(tapes["X"][-1]), L.ptr(lin_w), L.ptr(lin_b), L.ptr(ce["targets"]), N, lin_w.shape[1],
-                                          V, float(ce["inv_denom"]), L.ptr(logits), logits.stride(0), L.ptr(ce["row_loss"]),
-                                          L.ptr(ce["loss_out"]), L.ptr(ce["ws"]), ce["ws"].numel(), st), "sat_vocab_ce_fwd_bf16")
-    return logits, tapes, used
-
-
-def decoder_backward_tapes(lib, dlogits, tapes, embed_w, lstm_layers, lin_w, pi, grads_out, on_stage=None, ce=None, mixed_ws=None,
-                           lstm_ws=None):
-    """Backward of decoder_forward_tapes.  `dlogits`: f32 [N, ld] with ld = V rounded up to 4 and zero pad columns.  grads_out: dict name -> preallocated f32 tensor to fill:
-    'embed', ('w_ih',l), ('w_hh',l), ('b_ih',l), ('b_hh',l), 'lin_w', 'lin_b', 'features'.
-    on_stage(i) is called when gradient group i is final (0 vocab projection, 1 LSTM) -- the data-parallel
-    wrapper launches that bucket's all-reduce there, under the remaining backward kernels."""
-    dev = dlogits.device
-    st = L.stream()
-    N, T, B = pi.N, pi.T, pi.B
-    V, Hl = lin_w.shape
-    Xtop = tapes["X"][-1]
-    dH = torch.empty(N, Hl, device=dev)
-    if ce is not None and ce.get("kind") == "bf16":
-        L.check(lib.sat_vocab_ce_bwd_bf16(N, Hl, V, L.ptr(grads_out["lin_w"]), L.ptr(grads_out["lin_b"]), L.ptr(dH), L.ptr(ce["ws"]),
-                                          ce["ws"].numel(), st), "sat_vocab_ce_bwd_bf16")
-    else:
-        vwsb = lib.sat_vocab_ce_bwd_ws_bytes(N, Hl, V)
-        vws = torch.empty(max(vwsb // 4, 4), device=dev)
-        L.check(lib.sat_vocab_ce_bwd(L.ptr(dlogits), dlogits.stride(0), L.ptr(Xtop), L.ptr(lin_w), N, Hl, V, L.ptr(grads_out["lin_w"]),
-                                     L.ptr(grads_out["lin_b"]), L.ptr(dH), L.ptr(vws), vwsb, st), "sat_vocab_ce_bwd")
-    if on_stage is not None:
-        on_stage(0)
-    for l in reversed(range(len(lstm_layers))):
-        w_ih, w_hh, _, _ = lstm_layers[l]
-        H, In = w_hh.shape[1], w_ih.shape[1]
-        GA, CS, HP = tapes["layers"][l]
-        DG = torch.empty(N, 4 * H, device=dev)
-        dX = torch.empty(N, In, device=dev)
-        # the FULL workspace (split-K weight-gradient GEMMs + the persistent backward recurrence), sized for any N <= B * T so that
-        # batches of other lengths reuse it (its exchange region and status word sit at (B, H)-only offsets)
-        ws = lstm_ws[l][1] if lstm_ws is not None else _persistent_ws(dev, lib.sat_lstm_bwd_ws_bytes_max(B * T, B, In, H), ("lstm_bwd", l))
-        wsb = ws.numel()
-        if mixed_ws is not None:
-            L.check(lib.sat_lstm_bwd_bf16(L.ptr(dH), L.ptr(tapes["X"][l]), L.ptr(w_ih), L.ptr(w_hh), L.ptr(GA), L.ptr(CS),
-                                          L.ptr(HP), pi.bs_c, T, In, H, L.ptr(DG), L.ptr(grads_out[("w_ih", l)]),
-                                          L.ptr(grads_out[("w_hh", l)]), L.ptr(grads_out[("b_ih", l)]),
-                                          L.ptr(grads_out[("b_hh", l)]), L.ptr(dX), L.ptr(ws), wsb, L.ptr(mixed_ws), mixed_ws.numel(),
-                                          st), "sat_lstm_bwd_bf16")
-        else:
-            L.check(lib.sat_lstm_bwd(L.ptr(dH), L.ptr(tapes["X"][l]), L.ptr(w_ih), L.ptr(w_hh), L.ptr(GA), L.ptr(CS),
-                                     L.ptr(HP), pi.bs_c, T, In, H, L.ptr(DG), L.ptr(grads_out[("w_ih", l)]),
-                                     L.ptr(grads_out[("w_hh", l)]), L.ptr(grads_out[("b_ih", l)]),
-                                     L.ptr(grads_out[("b_hh", l)]), L.ptr(dX), L.ptr(ws), wsb, st), "sat_lstm_bwd")
-        if lstm_ws is None:                    # the backward recurrence may have run persistently: its status word
-            _watch_lstm(dev, ws, lib.sat_lstm_bwd_status_offset(N, B, In, H))
-        dH = dX
-    if on_stage is not None:
-        on_stage(1)
-    E = embed_w.shape[1]
-    caps = tapes["captions"]
-    cap_ptr, cap_stride = (None, 0) if T <= 1 else (caps.data_ptr(), caps.stride(0))
-    L.check(lib.sat_embed_concat_bwd(L.ptr(dH), cap_ptr, cap_stride, L.ptr(pi.prefix_dev), T, N, B, E,
-                                     embed_w.shape[0], L.ptr(grads_out["embed"]), L.ptr(grads_out["features"]), st),
-            "sat_embed_concat_bwd")
-
-
 class _DecoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, features, captions, pi, ss, num_layers, embed_w, lin_w, lin_b, *lstm_flat):
-        lib = L.load()
-        layers = [tuple(lstm_flat[4 * l:4 * l + 4]) for l in range(num_layers)]
-        if ss is not None:              # scheduled sampling: ss = dict(prob, seed, rank); receives "used"
-            logits, tapes, ss["used"] = decoder_forward_ss_tapes(lib, features, embed_w, layers, lin_w, lin_b, captions, pi,
-                                                                 ss["prob"], ss["seed"], ss["rank"])
-        else:
-            logits, tapes = decoder_forward_tapes(lib, features, embed_w, layers, lin_w, lin_b, captions, pi)
-        ctx.tapes, ctx.pi, ctx.layers = tapes, pi, layers
-        ctx.embed_w, ctx.lin_w = embed_w, lin_w
-        V = lin_w.shape[0]
+    def forward(ctx, features, captions, pi, ss, names, *tensors):
+        params = dict(zip(names, tensors))
+        sampling = None if ss is None else (ss["prob"], ss["seed"], ss["rank"])
+        logits, tapes = decoder_forward(L.load(), features, params, captions, pi, ss=sampling)
+        if ss is not None:              # scheduled sampling: ss = dict(prob, seed, rank) receives "used", the tokens fed
+            ss["used"] = tapes["captions"]
+        ctx.tapes, ctx.pi, ctx.names, ctx.params = tapes, pi, names, params
+        V = params["linear.weight"].shape[0]
         return logits if logits.shape[1] == V else logits[:, :V]
 
     @staticmethod
     def backward(ctx, dlogits):
-        lib = L.load()
-        dev = dlogits.device
-        V = ctx.lin_w.shape[0]
-        if V % 4:                                  # rows padded to 4 floats, zero pad (sat_vocab_ce_bwd's layout)
-            padded = torch.zeros(dlogits.shape[0], (V + 3) // 4 * 4, device=dev)
-            padded[:, :V] = dlogits
-            dlogits = padded
-        else:
-            dlogits = dlogits.contiguous()
-        layers = ctx.layers
-        g = {"embed": torch.empty_like(ctx.embed_w), "lin_w": torch.empty_like(ctx.lin_w),
-             "lin_b": torch.empty(ctx.lin_w.shape[0], device=dev),
-             "features": torch.empty(ctx.pi.B, ctx.embed_w.shape[1], device=dev)}
-        for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(layers):
-            g[("w_ih", l)], g[("w_hh", l)] = torch.empty_like(w_ih), torch.empty_like(w_hh)
-            g[("b_ih", l)], g[("b_hh", l)] = torch.empty_like(b_ih), torch.empty_like(b_hh)
-        decoder_backward_tapes(lib, dlogits, ctx.tapes, ctx.embed_w, layers, ctx.lin_w, ctx.pi, g)
-        flat = []
-        for l in range(len(layers)):
-            flat += [g[("w_ih", l)], g[("w_hh", l)], g[("b_ih", l)], g[("b_hh", l)]]
-        return (g["features"], None, None, None, None, g["embed"], g["lin_w"], g["lin_b"], *flat)
+        g = {n: torch.empty_like(p) for n, p in ctx.params.items()}
+        g["features"] = torch.empty(ctx.pi.B, ctx.params["embed.weight"].shape[1], device=dlogits.device)
+        decoder_backward(L.load(), L.pad_rows4(dlogits), ctx.tapes, ctx.params, ctx.pi, g, None)
+        return (g["features"], None, None, None, None, *(g[n] for n in ctx.names))
 
 
 class DecoderRNN(nn.Module):
@@ -761,12 +492,6 @@ class DecoderRNN(nn.Module):
         self.linear.weight.data.uniform_(-0.1, 0.1)
         self.linear.bias.data.fill_(0)
 
-    def _lstm_flat(self):
-        flat = []
-        for l in range(self.num_layers):
-            flat += list(self.lstm.layer(l))
-        return flat
-
     def forward(self, features, captions, lengths):
         """Decode image feature vectors and generate caption logits (models.py:47-54): f32 [sum(lengths), V],
         rows in time-major packed order.  In training mode with ss_prob > 0 the input of step t >= 2 is, with probability
@@ -786,8 +511,8 @@ class DecoderRNN(nn.Module):
         ss = None
         if self.training and self.ss_prob > 0:
             ss = dict(prob=float(self.ss_prob), seed=draw_ss_seed(), rank=int(self.ss_rank))
-        out = _DecoderFn.apply(features, captions, pi, ss, self.num_layers, self.embed.weight, self.linear.weight,
-                               self.linear.bias, *self._lstm_flat())
+        names, tensors = zip(*self.named_parameters())
+        out = _DecoderFn.apply(features, captions, pi, ss, names, *tensors)
         if ss is not None:
             self.last_ss_inputs, self.last_ss_seed = ss["used"], ss["seed"]
         return out

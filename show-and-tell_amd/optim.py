@@ -12,10 +12,6 @@ import torch
 from . import _lib as L
 
 
-def _pad4(n):
-    return (n + 3) // 4 * 4
-
-
 class FusedClampAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, clip=None):
         params = [p for p in params if p.requires_grad]
@@ -31,7 +27,7 @@ class FusedClampAdam(torch.optim.Optimizer):
         self._slices, off = [], 0
         for p in params:
             self._slices.append((off, p.numel()))
-            off += _pad4(p.numel())
+            off += L.pad4(p.numel())
         self.n = off
         self.flat = torch.zeros(off, device=dev)
         self.flat_grad = torch.zeros(off, device=dev)
@@ -74,7 +70,7 @@ class FusedClampAdam(torch.optim.Optimizer):
             o, n = self._slices[i]
             if o > start:
                 segs.append((start, o))
-            start = o + _pad4(n)
+            start = o + L.pad4(n)
         if start < self.n:
             segs.append((start, self.n))
         for a, b in segs:

@@ -16,9 +16,10 @@ as each bucket's gradients become final and overlapped with the rest of the back
 import torch
 
 from . import _lib as L
-from .models import (BN1D_MOMENTUM, BN_EPS, ShowAndTell, decoder_backward_tapes, decoder_forward_ss_tapes, decoder_forward_tapes,
-                     draw_ss_seed)
+from .decoder import LSTMWorkspaces, VocabCE, decoder_backward, decoder_forward
+from .models import ShowAndTell, draw_ss_seed, fc_bn1d_backward, fc_bn1d_forward
 from .pack import PackInfo
+from .watch import ResidencyWatch, StatusRing
 
 
 import os as _os
@@ -44,10 +45,6 @@ def ss_prob_for_epoch(epoch, start=-1, increase_every=5, increase_prob=0.05, max
     return 0.0
 
 
-def _pad4(n):
-    return (n + 3) // 4 * 4
-
-
 class FlatParams:
     """Trainable parameters re-homed into one flat f32 buffer, in gradient-completion order:
     bucket 0 = vocab projection, bucket 1 = LSTM (top layer first), bucket 2 = encoder head + embedding."""
@@ -68,7 +65,7 @@ class FlatParams:
             start = off
             for name, p in g:
                 self.slices[name] = (off, p.numel(), tuple(p.shape))
-                off += _pad4(p.numel())
+                off += L.pad4(p.numel())
             self.buckets.append((start, off))
         self.n = off
         # 4 trailing floats: slot 0 carries this rank's loss term through the last bucket's all-reduce, slot 1 the step's fault
@@ -113,13 +110,9 @@ class TrainStep:
         # up, cleared by the host once it has raised for it; while it is set every clamp + Adam launch drops its update
         self._fault_sticky = torch.zeros(1, device=self.flat.params.device)
         self.fault_slot = self.flat.grads[self.flat.loss_slot + 1:self.flat.loss_slot + 2]
-
-    def __del__(self):
-        try:                                     # the library remembers a backward workspace by address: tell it the memory is gone
-            for _, bws in getattr(self, "_lstm_ws", []):
-                self.lib.sat_lstm_ws_release(bws.data_ptr())
-        except Exception:
-            pass
+        # the LSTM workspaces this engine owns for good (their status words are folded into the step's fault flag)
+        self.lstm_ws = LSTMWorkspaces(self.flat.params.device, watch=False)
+        self._lag_ring = StatusRing(8)       # data-parallel steps: reduced fault flags in flight (_watch_fixed_lag)
 
     # -- encoder look-ahead ---------------------------------------------------------------------------
     def prefetch_encoder(self, images):
@@ -190,104 +183,61 @@ class TrainStep:
             F = enc.resnet.feature_dim
             wsb = lib.sat_fc_bn1d_ws_bytes(B, F, E)
             bufs = self._bufs[key] = dict(
-                targets=torch.empty(N, dtype=torch.int64, device=dev), logits=torch.zeros(N, (V + 3) // 4 * 4, device=dev),
+                targets=torch.empty(N, dtype=torch.int64, device=dev), logits=L.logits_buffer(N, V, dev),
                 row_loss=torch.empty(N, device=dev), feats=torch.empty(B, E, device=dev),
                 xhat=torch.empty(B, E, device=dev), rstd=torch.empty(E, device=dev),
                 head_ws=torch.empty(max(wsb // 4, B * E), device=dev), d_feat=torch.empty(B, E, device=dev),
                 pooled=torch.empty(B, F, device=dev))
-        # LSTM workspaces this engine owns for good, keyed by (B, caption width) -- NOT by N, which changes with almost every batch
-        # of real captions: sized for the longest batch of that width (sat_lstm_bwd_ws_bytes_max), the exchange region and the
-        # status words at offsets that depend on (B, H) only; their status words are folded into the step's fault flag below
-        wkey = (B, int(captions.shape[1]))
-        if getattr(self, "_lstm_ws_key", None) != wkey:
-            for _, old in getattr(self, "_lstm_ws", []):
-                lib.sat_lstm_ws_release(old.data_ptr())          # (the library forgets the address: a later buffer there is cleared again)
-            self._lstm_ws, words = [], []
-            n_max = B * (int(captions.shape[1]) - 1)
-            for l in range(dec.num_layers):
-                In = E if l == 0 else dec.hidden_size
-                fb, bb = lib.sat_lstm_fwd_ws_bytes(B, dec.hidden_size), lib.sat_lstm_bwd_ws_bytes_max(n_max, B, In, dec.hidden_size)
-                fws = torch.zeros(max(fb, 16), dtype=torch.uint8, device=dev)
-                bws = torch.empty(bb, dtype=torch.uint8, device=dev)
-                self._lstm_ws.append((fws, bws))
-                fo = lib.sat_lstm_fwd_status_offset(B, dec.hidden_size)
-                if fo >= 0 and fb > 0:
-                    words.append(fws.data_ptr() + fo)
-                so = lib.sat_lstm_bwd_status_offset(N, B, In, dec.hidden_size)
-                bws[so:so + 64].zero_()                          # (read by the fault flag even when the call below never runs persistently)
-                words.append(bws.data_ptr() + so)
-            if len(words) > 8:
-                raise ValueError("at most 4 LSTM layers (8 status words per step)")
-            import ctypes as _C
-            self._fault_words = ((_C.c_void_p * len(words))(*words), len(words))
-            self._lstm_ws_key = wkey
-        bufs["lstm_ws"], bufs["fault_words"] = self._lstm_ws, self._fault_words
         # targets = pack(captions[:,1:], lengths-1)                           train.py:135
         L.check(lib.sat_pack_targets(captions.data_ptr(), captions.stride(0), L.ptr(pi.prefix_dev), pi.T, N,
                                      L.ptr(bufs["targets"]), st), "sat_pack_targets")
         # ---- forward (train.py:139) ----
         cached_features = images.dim() == 2      # [B,E] precomputed encoder features: decoder-only training
+        fc, bn = enc.resnet.fc, enc.bn
         if cached_features:
             feats_in = images.contiguous()
             pooled = None
         else:
             pooled = self._encoder_pooled(images, bufs["pooled"], next_images)
-            F = pooled.shape[1]
-            fc, bn = enc.resnet.fc, enc.bn
-            L.check(lib.sat_fc_bn1d_fwd(L.ptr(pooled), L.ptr(fc.weight), L.ptr(fc.bias), L.ptr(bn.weight), L.ptr(bn.bias),
-                                        L.ptr(bn.running_mean), L.ptr(bn.running_var), BN1D_MOMENTUM, BN_EPS, 1, B, F, E,
-                                        L.ptr(bufs["feats"]), L.ptr(bufs["xhat"]), L.ptr(bufs["rstd"]),
-                                        L.ptr(bufs["head_ws"]), bufs["head_ws"].numel() * 4, st), "sat_fc_bn1d_fwd")
+            fc_bn1d_forward(lib, pooled, fc.weight, fc.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, True,
+                            bufs["feats"], bufs["xhat"], bufs["rstd"], bufs["head_ws"])
             L.counter_add(bn.num_batches_tracked)
             feats_in = bufs["feats"]
-        layers = [dec.lstm.layer(l) for l in range(dec.num_layers)]
+        params = dict(dec.named_parameters())
         loss_slot = flat.grads[flat.loss_slot:flat.loss_slot + 1]
-        ce = None
+        ce = mixed_ws = None
         if self.decoder_gemm_dtype == "bf16":
             wsb = lib.sat_vocab_bf16_ws_bytes(N, dec.hidden_size, V)
             if wsb > 0:
                 if "vocab_bf16_ws" not in bufs:
                     bufs["vocab_bf16_ws"] = torch.empty(wsb, dtype=torch.uint8, device=dev)
-                ce = dict(kind="bf16", targets=bufs["targets"], inv_denom=inv_denom, row_loss=bufs["row_loss"], loss_out=loss_slot,
-                          ws=bufs["vocab_bf16_ws"])
-        mixed_ws = None
-        if self.decoder_gemm_dtype == "bf16":          # the LSTM layers' batched GEMMs on the bf16 matrix pipe too
+                ce = VocabCE(bufs["targets"], inv_denom, bufs["row_loss"], loss_slot, bufs["vocab_bf16_ws"])
+            # the LSTM layers' batched GEMMs on the bf16 matrix pipe too
             if "lstm_mixed_ws" not in bufs:
                 need = max(lib.sat_lstm_mixed_ws_bytes(N, E if l == 0 else dec.hidden_size, dec.hidden_size) for l in range(dec.num_layers))
                 bufs["lstm_mixed_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
             mixed_ws = bufs["lstm_mixed_ws"]
+        ss = None
         if dec.ss_prob > 0:
             # scheduled sampling (model.training is required above): the step loop with its draws; exact-f32 logits for sat_ce_rows,
             # or in the bf16 mode draws only and the mode's projection + CE over every row (`ce`)
-            seed = draw_ss_seed()
-            logits, tapes, used = decoder_forward_ss_tapes(lib, feats_in, dec.embed.weight, layers, dec.linear.weight, dec.linear.bias,
-                                                           captions[:, :-1], pi, dec.ss_prob, seed, rank=dec.ss_rank,
-                                                           store_logits=ce is None, logits=bufs["logits"], ce=ce,
-                                                           lstm_ws=bufs["lstm_ws"])
-            dec.last_ss_inputs, dec.last_ss_seed = used, seed
-        else:
-            logits, tapes = decoder_forward_tapes(lib, feats_in, dec.embed.weight, layers, dec.linear.weight,
-                                                  dec.linear.bias, captions[:, :-1], pi, logits=bufs["logits"], ce=ce, mixed_ws=mixed_ws,
-                                                  lstm_ws=bufs["lstm_ws"])
+            ss = (dec.ss_prob, draw_ss_seed(), dec.ss_rank)
+        logits, tapes = decoder_forward(lib, feats_in, params, captions[:, :-1], pi, self.lstm_ws, logits=bufs["logits"], ce=ce,
+                                        mixed_ws=mixed_ws, ss=ss)
+        if ss is not None:
+            dec.last_ss_inputs, dec.last_ss_seed = tapes["captions"], ss[1]
         if ce is None:
             # ---- loss + d(loss)/d(logits) in place (train.py:143) ----
             L.check(lib.sat_ce_rows(L.ptr(logits), logits.stride(0), L.ptr(bufs["targets"]), N, V, float(inv_denom), 1,
                                     L.ptr(bufs["row_loss"]), L.ptr(loss_slot), st), "sat_ce_rows")
         # ---- backward (train.py:144): gradients land directly in the flat buffer ----
-        g = {"embed": flat.grad("decoder.embed.weight"), "lin_w": flat.grad("decoder.linear.weight"),
-             "lin_b": flat.grad("decoder.linear.bias"), "features": bufs["d_feat"]}
-        for l in range(dec.num_layers):
-            for short, n in (("w_ih", "weight_ih"), ("w_hh", "weight_hh"), ("b_ih", "bias_ih"), ("b_hh", "bias_hh")):
-                g[(short, l)] = flat.grad("decoder.lstm.%s_l%d" % (n, l))
-        decoder_backward_tapes(lib, logits, tapes, dec.embed.weight, layers, dec.linear.weight, pi, g,
-                               on_stage=on_bucket_ready, ce=ce, mixed_ws=mixed_ws, lstm_ws=bufs["lstm_ws"])
+        g = {name: flat.grad("decoder." + name) for name in params}
+        g["features"] = bufs["d_feat"]
+        decoder_backward(lib, logits, tapes, params, pi, g, self.lstm_ws, on_stage=on_bucket_ready, ce=ce, mixed_ws=mixed_ws)
         if not cached_features:
-            fc, bn = enc.resnet.fc, enc.bn
-            L.check(lib.sat_fc_bn1d_bwd(L.ptr(bufs["d_feat"]), L.ptr(pooled), L.ptr(bufs["xhat"]), L.ptr(bufs["rstd"]),
-                                        L.ptr(bn.weight), B, pooled.shape[1], E, L.ptr(flat.grad("encoder.resnet.fc.weight")),
-                                        L.ptr(flat.grad("encoder.resnet.fc.bias")), L.ptr(flat.grad("encoder.bn.weight")),
-                                        L.ptr(flat.grad("encoder.bn.bias")), L.ptr(bufs["head_ws"]),
-                                        bufs["head_ws"].numel() * 4, st), "sat_fc_bn1d_bwd")
+            fc_bn1d_backward(lib, bufs["d_feat"], pooled, bufs["xhat"], bufs["rstd"], bn.weight,
+                             flat.grad("encoder.resnet.fc.weight"), flat.grad("encoder.resnet.fc.bias"),
+                             flat.grad("encoder.bn.weight"), flat.grad("encoder.bn.bias"), bufs["head_ws"])
         self.last_d_features = bufs["d_feat"]
         # this step's encoder outputs (views of step-owned buffers, overwritten by the next step): the parity tests at the
         # benchmarked configuration read them
@@ -295,7 +245,7 @@ class TrainStep:
         # the step's fault flag (one 1-thread launch): OR of the status words of this step's persistent LSTM launches and of the
         # engine's sticky word, into slot 1 of the trailing floats -- it rides the last bucket's all-reduce, and clamp + Adam
         # read it on the device (optimizer_step): a step that any rank lost never reaches the parameters of any rank
-        words, nw = bufs["fault_words"]
+        words, nw = self.lstm_ws.fault_words
         L.check(lib.sat_step_fault_flag(words, nw, L.ptr(self._fault_sticky), L.ptr(self.fault_slot), st), "sat_step_fault_flag")
         if on_bucket_ready is not None:
             on_bucket_ready(2)   # encoder head + embedding gradients (and the loss slot) are final
@@ -306,7 +256,6 @@ class TrainStep:
         RuntimeError when a persistent LSTM recurrence gave up (`watch.ResidencyWatch`; see `optimizer_step`)."""
         self.model.decoder.id_guard().poll(block=True)
         self._retire_fixed_lag(0)          # data-parallel steps: every flag still in flight, oldest first (same order on every rank)
-        from .watch import ResidencyWatch
         ResidencyWatch.get(self.model.decoder.linear.weight.device).poll(block=True)
 
     FAULT_NOTE = ("the parameter update of that step and of every step submitted since was SKIPPED on the device (on every rank in "
@@ -336,31 +285,18 @@ class TrainStep:
         point in the loop, same decision on every rank.  While the faulted rank's sticky word is set, every rank's reduced flag is
         non-zero, so the steps between the fault and the raise are dropped everywhere; the raise rolls the step count back to the
         faulted step's on every rank and clears the sticky word."""
-        if getattr(self, "_dp_host", None) is None:
-            self._dp_host = torch.zeros(8, dtype=torch.int32).pin_memory()
-            self._dp_pending, self._dp_slot = [], 0
-        slot = self._dp_slot
-        self._dp_slot = (slot + 1) % 8
-        self._dp_host[slot:slot + 1].copy_(self.fault_slot.view(torch.int32), non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._dp_pending.append((slot, ev, before))
+        self._lag_ring.push(self.fault_slot.view(torch.int32), before)
         self._retire_fixed_lag(lag)
 
     def _retire_fixed_lag(self, keep):
-        pend = getattr(self, "_dp_pending", None)
-        while pend and len(pend) > keep:
-            slot, ev, before = pend.pop(0)
-            ev.synchronize()
-            code = int(self._dp_host[slot])
-            if code != 0:
-                torch.cuda.synchronize()
-                pend.clear()
-                self._dp_host.zero_()
-                self._on_fault(before)
-                raise RuntimeError("show-and-tell_amd: a persistent LSTM recurrence of a training step timed out waiting for its "
-                                   "workgroups to be resident together (reduced fault flag 0x%x: on this rank or another); %s.  "
-                                   "Later calls use the form without a device-wide wait" % (code & 0xffffffff, self.FAULT_NOTE))
+        fault = self._lag_ring.retire(block=True, keep=keep)
+        if fault is not None:
+            code, before = fault
+            torch.cuda.synchronize()
+            self._on_fault(before)
+            raise RuntimeError("show-and-tell_amd: a persistent LSTM recurrence of a training step timed out waiting for its "
+                               "workgroups to be resident together (reduced fault flag 0x%x: on this rank or another); %s.  "
+                               "Later calls use the form without a device-wide wait" % (code & 0xffffffff, self.FAULT_NOTE))
 
     def optimizer_step(self, lr=None, fixed_lag=None):
         """clip_gradient + Adam (train.py:145-146) as one launch over the flat buffers, GUARDED on the device by the step's
@@ -380,7 +316,6 @@ class TrainStep:
         if fixed_lag is not None:
             self._watch_fixed_lag(before, int(fixed_lag))
             return
-        from .watch import ResidencyWatch
         ResidencyWatch.get(f.params.device).submit(self.fault_slot.view(torch.int32), "a persistent LSTM recurrence of a training step",
                                                    lambda: self._on_fault(before), note=self.FAULT_NOTE)
 

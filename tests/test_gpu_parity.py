@@ -502,6 +502,38 @@ def test_checkpoint_resume_is_bit_exact_and_interchanges_with_torch_adam():
     assert ts2.step_count == 2
 
 
+def test_trainstep_lstm_workspaces_follow_the_batch_not_the_caption_width():
+    """Caption widths 12 -> 20 -> 12 at one batch size: every step's loss and gradients equal, bit for bit, those of a fresh
+    TrainStep (same parameters and Adam state) fed that batch alone, and the second width-12 batch runs on the LSTM workspaces
+    the width-20 one grew instead of allocating new ones.  B * (width - 1) > 4H: the backward workspace size depends on the width"""
+    E, H, V, Lh, B = 32, 64, 300, 2, 32
+    torch.manual_seed(5)
+    model = sat.ShowAndTell(E, H, V, Lh, arch=TINY).cuda().train()
+    ts = sat.TrainStep(model, lr=1e-3, grad_clip=0.1)
+    gen = torch.Generator().manual_seed(6)
+    held = []                   # the owner's buffers after each step, kept alive: a freed buffer's address could come back
+    for width in (12, 20, 12):
+        feats = torch.randn(B, E, generator=gen).cuda()                    # cached features: decoder-only steps
+        lengths = [width] + sorted(torch.randint(3, width + 1, (B - 1,), generator=gen).tolist(), reverse=True)
+        caps = torch.randint(4, V, (B, width), generator=gen).cuda()
+        inv = 1.0 / sum(l - 1 for l in lengths)
+        fresh = sat.ShowAndTell(E, H, V, Lh, arch=TINY)
+        fresh.load_state_dict(model.state_dict())
+        ts2 = sat.TrainStep(fresh.cuda().train())
+        ts2.load_optimizer_state_dict(ts.optimizer_state_dict())
+        loss = ts.forward_backward((feats, caps, lengths), inv).clone()
+        ref = ts2.forward_backward((feats, caps, lengths), inv).clone()
+        assert torch.equal(loss, ref) and torch.equal(ts.flat_grad, ts2.flat_grad), width
+        held.append(ts.lstm_ws.fwd + ts.lstm_ws.bwd)
+        if len(held) == 3:      # the last step ran on buffers larger than the fresh engine's
+            assert all(a.numel() > b.numel() for a, b in zip(ts.lstm_ws.bwd, ts2.lstm_ws.bwd))
+        ts.optimizer_step()
+        ts2.check_ids()
+    ts.check_ids()
+    assert all(b.numel() > a.numel() for a, b in zip(held[0][Lh:], held[1][Lh:]))      # width 20 grew the backward buffers
+    assert all(a is b for a, b in zip(held[2], held[1]))                                # width 12 again: nothing reallocated
+
+
 # ------------------------------------------------------------------------------------------------------
 # BASELINE cfg-2 size (B=64, 224x224, E=256, H=512, V=10000): size-independent properties
 def _cfg2(seed=123, B=64):

@@ -16,7 +16,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 sat = importlib.import_module("show-and-tell_amd")
-M = sat.models
+D = importlib.import_module("show-and-tell_amd.decoder")
 B, E, H, V, T, S = 64, 256, 512, 10000, 20, 224
 
 
@@ -54,13 +54,12 @@ def main():
     images, caps = synth(123)
     lengths = [T] * B
     feats = torch.randn(B, E, device="cuda")
-    layers = [dec.lstm.layer(0)]
+    params = dict(dec.named_parameters())
     pi = sat.PackInfo.get([T - 1] * B, "cuda")
 
     def ss_forward(n):
         for _ in range(n):
-            M.decoder_forward_ss_tapes(lib, feats, dec.embed.weight, layers, dec.linear.weight, dec.linear.bias, caps[:, :-1], pi,
-                                       args.ss_prob, 12345, store_logits=False)
+            D.decoder_forward(lib, feats, params, caps[:, :-1], pi, ss=(args.ss_prob, 12345, 0), store_logits=False)
 
     if args.forward_only:
         ss_forward(args.forward_only)
@@ -70,7 +69,7 @@ def main():
 
     def tf_forward(n):
         for _ in range(n):
-            M.decoder_forward_tapes(lib, feats, dec.embed.weight, layers, dec.linear.weight, dec.linear.bias, caps[:, :-1], pi)
+            D.decoder_forward(lib, feats, params, caps[:, :-1], pi)
 
     res = {"shape": dict(B=B, E=E, H=H, V=V, cap_len=T, image=S), "ss_prob": args.ss_prob, "steps": args.steps,
            "regions": args.regions}
