@@ -9,7 +9,7 @@ pids=()
 for f in sat_gemm sat_gemm_x3 sat_gemm_bf16 sat_conv_glds sat_lstm_persist sat_skinny sat_elementwise sat_attend sat_beam sat_ss sat_gram sat_host; do
   stale=0
   [ -f build/$f.o ] || stale=1
-  for d in $f.hip sat_common.h sat_internal.h ../../include/sat_hip.h sat_conv_*.inc; do [ $d -nt build/$f.o ] && stale=1; done
+  for d in $f.hip sat_*.h ../../include/sat_hip.h sat_conv_*.inc; do [ $d -nt build/$f.o ] && stale=1; done
   if [ $stale = 1 ]; then
     hipcc $FLAGS -c $f.hip -o build/$f.o &
     pids+=($!)

@@ -38,11 +38,9 @@ __global__ __launch_bounds__(256, 2) void conv_ap_kernel(const ConvArgs p_) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int W = nwg / p.tiles_n;                          // workers per column block
-    const int worker = swz / p.tiles_n, tile_n = swz - worker * p.tiles_n;      // the column blocks of a row tile share an XCD's L2
+    const int tile = xcd_tile();
+    const int W = gridDim.x / p.tiles_n;                          // workers per column block
+    const int worker = tile / p.tiles_n, tile_n = tile - worker * p.tiles_n;      // the column blocks of a row tile share an XCD's L2
     const int n0 = tile_n * BN;
     const int RT = (p.M + BM - 1) / BM;
     const int n_my = worker < RT ? (RT - worker + W - 1) / W : 0;               // row tiles worker, worker + W, ...
@@ -93,35 +91,7 @@ __global__ __launch_bounds__(256, 2) void conv_ap_kernel(const ConvArgs p_) {
     const f32x16 kZero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     if constexpr (AFF) {
-        const double inv = p.in_inv;                          // 1 / (2^22 * count), divided on the host
-        for (int c = tid; c < p.Cin; c += NT) {
-            float sc, sh;
-            if (p.in_acc) {
-                const long long s1 = p.in_acc[c], s2 = p.in_acc[p.Cin + c];
-                const double mean = (double)s1 * inv;
-                double var = (double)s2 * inv - mean * mean;
-                if (var < 0.0) var = 0.0;
-                const float invstd = 1.0f / sqrtf((float)var + p.in_eps);
-                sc = p.in_gamma[c] * invstd;
-                sh = p.in_beta[c] - (float)mean * sc;
-                if (bid == 0) {
-                    if (p.in_running_mean) {
-                        const double unbiased = p.in_count > 1.0 ? var * p.in_count / (p.in_count - 1.0) : var;
-                        p.in_running_mean[c] = (float)((1.0 - p.in_momentum) * p.in_running_mean[c] + p.in_momentum * (double)(float)mean);
-                        p.in_running_var[c] = (float)((1.0 - p.in_momentum) * p.in_running_var[c] + p.in_momentum * (double)(float)unbiased);
-                    }
-                    if (p.in_acc_clear) {
-                        p.in_acc_clear[c] = 0;
-                        p.in_acc_clear[p.Cin + c] = 0;
-                    }
-                }
-            } else {
-                sc = p.in_scale[c];
-                sh = p.in_shift[c];
-            }
-            in_tab[c] = sc;
-            in_tab[p.Cin + c] = sh;
-        }
+        conv_in_table<NT>(p, in_tab);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // (a raw barrier: __syncthreads would also wait for every load in flight)
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -218,8 +188,7 @@ __global__ __launch_bounds__(256, 2) void conv_ap_kernel(const ConvArgs p_) {
             if (p.stat_partial) {
                 const float s2 = s + __shfl_xor(s, 32, 64), q2 = q + __shfl_xor(q, 32, 64);
                 if (h == 0) {
-                    p.stat_partial[((long)tile_m * 2 + 0) * p.N + n0 + colw] = s2;
-                    p.stat_partial[((long)tile_m * 2 + 1) * p.N + n0 + colw] = q2;
+                    stat_slab_store(p.stat_partial, tile_m, p.N, s2, q2, n0, colw);
                 }
             }
             s_run += s;                                       // tiles of this worker in order
@@ -251,8 +220,7 @@ __global__ __launch_bounds__(256, 2) void conv_ap_kernel(const ConvArgs p_) {
     if (p.acc) {
         const float s2 = s_run + __shfl_xor(s_run, 32, 64), q2 = q_run + __shfl_xor(q_run, 32, 64);
         if (h == 0) {
-            atomicAdd((unsigned long long*)(p.acc + n0 + colw), (unsigned long long)__double2ll_rn((double)s2 * kStatScale));
-            atomicAdd((unsigned long long*)(p.acc + p.N + n0 + colw), (unsigned long long)__double2ll_rn((double)q2 * kStatScale));
+            stat_acc_add(p.acc, p.N, s2, q2, n0, colw);
         }
     }
 }
@@ -277,17 +245,5 @@ int ap_workers(const ConvArgs& a) {
 int launch_ap(ConvArgs& a, int groups, hipStream_t s) {
     if (!ap_ok(a)) return SAT_ERR_UNSUPPORTED;
     a.tiles_n = a.N / 128;
-    const dim3 grid(ap_workers(a) * a.tiles_n, groups), block(256);
-    hipEvent_t e0 = t_ev_start, e1 = t_ev_stop;
-    t_ev_start = t_ev_stop = nullptr;
-    a.in_inv = a.in_count > 0 ? 1.0 / (kStatScale * a.in_count) : 0.0;
-    if (a.in_affine) {
-        if (e0) hipExtLaunchKernelGGL((conv_ap_kernel<true>), grid, block, 0, s, e0, e1, 0, a);
-        else hipLaunchKernelGGL((conv_ap_kernel<true>), grid, block, 0, s, a);
-    } else {
-        if (e0) hipExtLaunchKernelGGL((conv_ap_kernel<false>), grid, block, 0, s, e0, e1, 0, a);
-        else hipLaunchKernelGGL((conv_ap_kernel<false>), grid, block, 0, s, a);
-    }
-    SAT_LAUNCH_CHECK();
-    return SAT_OK;
+    return launch_conv(a.in_affine ? conv_ap_kernel<true> : conv_ap_kernel<false>, dim3(ap_workers(a) * a.tiles_n, groups), dim3(256), 0, s, a);
 }

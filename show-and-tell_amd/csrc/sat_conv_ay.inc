@@ -40,10 +40,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ay_kernel(const ConvArgs p_) 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int tile_m = swz / p.tiles_n, tile_n = swz - tile_m * p.tiles_n;      // the column tiles of a row tile share an XCD's L2
+    const int tile = xcd_tile();
+    const int tile_m = tile / p.tiles_n, tile_n = tile - tile_m * p.tiles_n;      // the column tiles of a row tile share an XCD's L2
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int nk = p.Cin >> 6;                                // K-steps of 64 channels: a multiple of PDA, >= 2 PDA (ay_ok)
     const bool write_y = tile_n == 0;                         // (uniform per workgroup)
@@ -98,37 +96,9 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ay_kernel(const ConvArgs p_) 
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[i][e] = 0.0f;
 
-    // bn3's (scale, shift) of all Cin channels into LDS once (bn_table_from_acc's arithmetic, sat_elementwise.hip)
+    // bn3's (scale, shift) of all Cin channels into LDS once (bn_table's arithmetic, sat_bn_stats.h)
     {
-        const double inv = p.in_inv;                          // 1 / (2^22 * count), divided on the host
-        for (int c = tid; c < p.Cin; c += NT) {
-            float sc, sh;
-            if (p.in_acc) {
-                const long long s1 = p.in_acc[c], s2 = p.in_acc[p.Cin + c];
-                const double mean = (double)s1 * inv;
-                double var = (double)s2 * inv - mean * mean;
-                if (var < 0.0) var = 0.0;
-                const float invstd = 1.0f / sqrtf((float)var + p.in_eps);
-                sc = p.in_gamma[c] * invstd;
-                sh = p.in_beta[c] - (float)mean * sc;
-                if (bid == 0) {
-                    if (p.in_running_mean) {
-                        const double unbiased = p.in_count > 1.0 ? var * p.in_count / (p.in_count - 1.0) : var;
-                        p.in_running_mean[c] = (float)((1.0 - p.in_momentum) * p.in_running_mean[c] + p.in_momentum * (double)(float)mean);
-                        p.in_running_var[c] = (float)((1.0 - p.in_momentum) * p.in_running_var[c] + p.in_momentum * (double)(float)unbiased);
-                    }
-                    if (p.in_acc_clear) {
-                        p.in_acc_clear[c] = 0;
-                        p.in_acc_clear[p.Cin + c] = 0;
-                    }
-                }
-            } else {
-                sc = p.in_scale[c];
-                sh = p.in_shift[c];
-            }
-            in_tab[c] = sc;
-            in_tab[p.Cin + c] = sh;
-        }
+        conv_in_table<NT>(p, in_tab);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // (a raw barrier: __syncthreads would also wait for every load in flight)
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -239,12 +209,10 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ay_kernel(const ConvArgs p_) 
         const int col = n0 + colw;
         if (h == 0 && col < p.N) {
             if (p.acc) {
-                atomicAdd((unsigned long long*)(p.acc + col), (unsigned long long)__double2ll_rn((double)s * kStatScale));
-                atomicAdd((unsigned long long*)(p.acc + p.N + col), (unsigned long long)__double2ll_rn((double)q * kStatScale));
+                stat_acc_add(p.acc, p.N, s, q, col);
             }
             if (p.stat_partial) {
-                p.stat_partial[((long)tile_m * 2 + 0) * p.N + col] = s;
-                p.stat_partial[((long)tile_m * 2 + 1) * p.N + col] = q;
+                stat_slab_store(p.stat_partial, tile_m, p.N, s, q, col);
             }
         }
     }
@@ -283,13 +251,5 @@ template <int NW>
 int launch_ay(ConvArgs& a, int groups, hipStream_t s) {
     if (!ay_ok(a, NW)) return SAT_ERR_UNSUPPORTED;
     a.tiles_n = a.N / (NW * 32);
-    const dim3 grid(sat_cdiv(a.M, 128) * a.tiles_n, groups), block(NW * 64);
-    hipEvent_t e0 = t_ev_start, e1 = t_ev_stop;
-    t_ev_start = t_ev_stop = nullptr;
-    a.in_inv = a.in_count > 0 ? 1.0 / (kStatScale * a.in_count) : 0.0;
-    constexpr int PDA = NW == 8 ? 4 : 2;
-    if (e0) hipExtLaunchKernelGGL((conv_ay_kernel<NW, PDA>), grid, block, 0, s, e0, e1, 0, a);
-    else hipLaunchKernelGGL((conv_ay_kernel<NW, PDA>), grid, block, 0, s, a);
-    SAT_LAUNCH_CHECK();
-    return SAT_OK;
+    return launch_conv(conv_ay_kernel<NW, NW == 8 ? 4 : 2>, dim3(sat_cdiv(a.M, 128) * a.tiles_n, groups), dim3(NW * 64), 0, s, a);
 }

@@ -17,15 +17,15 @@
 //   * epilogue: f32 accumulators -> per-tile BatchNorm column sums (fixed order) and a bf16 tile staged through
 //     LDS so global stores are full 16-byte-per-lane rows;
 //   * blockIdx -> tile map is XCD-aware (tiles sharing an activation panel share an L2).
-#include "sat_internal.h"
+#include "sat_bn_stats.h"
 #include <hip/hip_ext.h>
 
 // diagnostics (sat_run_ops_timed): when armed, the NEXT conv launch of this thread records its own begin / end
-// timestamps into these events (hipExtLaunchKernelGGL: the dispatch packet's timestamps, what rocprofv3 reports)
+// timestamps into these events (the dispatch packet's timestamps, what rocprofv3 reports; launch_conv)
 static thread_local hipEvent_t t_ev_start = nullptr, t_ev_stop = nullptr;
 void sat_conv_arm_timer(hipEvent_t start, hipEvent_t stop) { t_ev_start = start; t_ev_stop = stop; }
-// the armed timer, consumed (the fused conv3 launch of sat_conv3_fused.hip reports its own span the same way)
-void sat_conv_take_timer(hipEvent_t* start, hipEvent_t* stop) {
+// the armed timer, consumed (by launch_conv, which every conv launch goes through)
+static void sat_conv_take_timer(hipEvent_t* start, hipEvent_t* stop) {
     *start = t_ev_start; *stop = t_ev_stop;
     t_ev_start = t_ev_stop = nullptr;
 }
@@ -65,7 +65,7 @@ struct ConvArgs {
     float* in_running_mean;
     float* in_running_var;
     double in_count;
-    double in_inv;           // 1 / (2^22 * in_count) (conv_xp_kernel / conv_pr_kernel: the division happens on the host)
+    double in_inv;           // sat_stat_inv(in_count): divided once, on the host
     float in_momentum, in_eps;
     int in_affine;
     // Output-side fusion (inference: BatchNorm is a fixed per-channel affine): out = [relu](acc*out_scale[n] +
@@ -85,9 +85,6 @@ struct ConvArgs {
     const bf16_t* in_res;
     bf16_t* Y;
 };
-// fixed-point scale of the atomic statistics is SAT_STAT_SCALE (sat_internal.h)
-constexpr double kStatScale = SAT_STAT_SCALE;
-
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -144,6 +141,43 @@ __device__ __forceinline__ ConvArgs group_args(const ConvArgs& q) {
     return p;
 }
 
+// XCD-aware block -> tile map: the dispatcher deals workgroups round-robin over the eight XCDs, so workgroup b runs on XCD b % 8.
+// Numbered this way, each XCD takes a contiguous run of tiles, and neighbouring tiles (which share an operand panel) share its L2.
+__device__ __forceinline__ int xcd_tile() {
+    const int nwg = gridDim.x, bid = blockIdx.x;
+    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+}
+
+// The operand's BatchNorm (scale, shift) for all Cin channels into tab[0, Cin) and tab[Cin, 2 Cin), NT threads per workgroup: from
+// the previous conv's integer sums (workgroup 0 also updates the running statistics and clears the other parity) or the precomputed
+// table.  Each kernel follows it with a barrier of its own.
+template <int NT>
+__device__ __forceinline__ void conv_in_table(const ConvArgs& p, float* tab) {
+    const BnSrc b = {p.in_scale, p.in_shift, p.in_acc, p.in_acc_clear, p.in_gamma, p.in_beta, p.in_running_mean, p.in_running_var};
+    bn_table<NT>(b, p.Cin, p.in_count, p.in_inv, p.in_momentum, p.in_eps, threadIdx.x, blockIdx.x == 0, tab, tab + p.Cin);
+}
+
+typedef void (*ConvKernel)(ConvArgs);
+
+// One conv launch.  It consumes the armed timer first, so that the timer never outlives the launch it was armed for, also when the
+// launch is refused (`k` null, or a dynamic-LDS limit that cannot be raised).  Armed, the launch records the dispatch packet's begin /
+// end timestamps into the timer's events.  More than 64 KB of dynamic LDS needs the kernel's limit raised to lds_max, once per kernel:
+// `raised` is that kernel's own flag.
+int launch_conv(ConvKernel k, dim3 grid, dim3 block, size_t lds, hipStream_t s, const ConvArgs& a, bool* raised = nullptr, int lds_max = 0) {
+    hipEvent_t e0, e1;
+    sat_conv_take_timer(&e0, &e1);
+    if (!k) return SAT_ERR_UNSUPPORTED;
+    if (raised && !*raised && lds > 64 * 1024) {
+        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) return SAT_ERR_UNSUPPORTED;
+        *raised = true;
+    }
+    if (e0) hipExtLaunchKernelGGL(k, grid, block, lds, s, e0, e1, 0, a);
+    else hipLaunchKernelGGL(k, grid, block, lds, s, a);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
 template <int BN, int S, int NW, bool UNIFORM, bool SPEC = false, bool PF = false, int BM = 128>
 __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
     const ConvArgs p = group_args(p_);
@@ -177,10 +211,8 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
     const int wm = cw / WGN, wn = cw % WGN;
     const int r = lane & 31, h = lane >> 5;
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int tile_m = swz / p.tiles_n, tile_n = swz - tile_m * p.tiles_n;
+    const int tile = xcd_tile();
+    const int tile_m = tile / p.tiles_n, tile_n = tile - tile_m * p.tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
     const bf16_t* zero = (const bf16_t*)&g_zero16;
@@ -341,37 +373,7 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
     }
 
     if (p.in_affine) {
-        // (scale, shift) of the input's BatchNorm for all Cin (= K) channels, into LDS
-        const double inv = 1.0 / (kStatScale * p.in_count);     // same arithmetic as bn_table_from_acc
-        for (int c = tid; c < p.Cin; c += NT) {
-            float sc, sh;
-            if (p.in_acc) {
-                const long long s1 = p.in_acc[c], s2 = p.in_acc[p.Cin + c];
-                const double mean = (double)s1 * inv;
-                double var = (double)s2 * inv - mean * mean;
-                if (var < 0.0) var = 0.0;
-                const float invstd = 1.0f / sqrtf((float)var + p.in_eps);
-                sc = p.in_gamma[c] * invstd;
-                sh = p.in_beta[c] - (float)mean * sc;
-                if (bid == 0) {
-                    if (p.in_running_mean) {
-                        const double unbiased = p.in_count > 1.0 ? var * p.in_count / (p.in_count - 1.0) : var;
-                        // the batch statistic enters as an f32 value: a deferred update (sat_bn_running_apply) is then bit-identical
-                        p.in_running_mean[c] = (float)((1.0 - p.in_momentum) * p.in_running_mean[c] + p.in_momentum * (double)(float)mean);
-                        p.in_running_var[c] = (float)((1.0 - p.in_momentum) * p.in_running_var[c] + p.in_momentum * (double)(float)unbiased);
-                    }
-                    if (p.in_acc_clear) {
-                        p.in_acc_clear[c] = 0;
-                        p.in_acc_clear[p.Cin + c] = 0;
-                    }
-                }
-            } else {
-                sc = p.in_scale[c];
-                sh = p.in_shift[c];
-            }
-            in_tab[c] = sc;
-            in_tab[p.Cin + c] = sh;
-        }
+        conv_in_table<NT>(p, in_tab);       // all Cin (= K) channels
         __syncthreads();          // nothing is in flight yet: a plain barrier (with its LDS wait) is fine here
     }
 
@@ -534,8 +536,7 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
                     s += red[(g * 2 + 0) * BN + c];
                     q += red[(g * 2 + 1) * BN + c];
                 }
-                atomicAdd((unsigned long long*)(p.acc + col), (unsigned long long)__double2ll_rn((double)s * kStatScale));
-                atomicAdd((unsigned long long*)(p.acc + p.N + col), (unsigned long long)__double2ll_rn((double)q * kStatScale));
+                stat_acc_add(p.acc, p.N, s, q, col);
             }
         }
     }
@@ -569,8 +570,7 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
                     s += red[(g * 2 + 0) * BN + c];
                     q += red[(g * 2 + 1) * BN + c];
                 }
-                p.stat_partial[((long)tile_m * 2 + 0) * p.N + col] = s;
-                p.stat_partial[((long)tile_m * 2 + 1) * p.N + col] = q;
+                stat_slab_store(p.stat_partial, tile_m, p.N, s, q, col);
             }
         }
     }
@@ -604,47 +604,9 @@ int launch_glds(ConvArgs& a, int groups, hipStream_t s) {
     const int tm = sat_cdiv(a.M, BM), tn = sat_cdiv(a.N, BN);
     a.tiles_n = tn;
     const bool uniform = (a.Cin % 64 == 0) && (a.KH * a.KW <= 32);
-    const dim3 grid(tm * tn, groups), block(NW * 64);
-    hipEvent_t e0 = t_ev_start, e1 = t_ev_stop;     // armed: timed diagnostic launch (same kernel, same grid, + the packet's timestamps)
-    t_ev_start = t_ev_stop = nullptr;
-    if (uniform) {
-        if (e0) hipExtLaunchKernelGGL((conv_glds_kernel<BN, S, NW, true, SPEC, PF, BM>), grid, block, 0, s, e0, e1, 0, a);
-        else hipLaunchKernelGGL((conv_glds_kernel<BN, S, NW, true, SPEC, PF, BM>), grid, block, 0, s, a);
-    } else {
-        if (e0) hipExtLaunchKernelGGL((conv_glds_kernel<BN, S, NW, false, SPEC, PF, BM>), grid, block, 0, s, e0, e1, 0, a);
-        else hipLaunchKernelGGL((conv_glds_kernel<BN, S, NW, false, SPEC, PF, BM>), grid, block, 0, s, a);
-    }
-    SAT_LAUNCH_CHECK();
-    return SAT_OK;
+    return launch_conv(uniform ? conv_glds_kernel<BN, S, NW, true, SPEC, PF, BM> : conv_glds_kernel<BN, S, NW, false, SPEC, PF, BM>,
+                       dim3(tm * tn, groups), dim3(NW * 64), 0, s, a);
 }
-
-// kernel variants: (tile width, ring stages, waves, wave specialisation, fragment prefetch, tile rows).
-// LDS = S * (BM/8 + BN/8) KB (+ the table) decides workgroups per CU.
-struct Variant { int bn, s, nw, spec, pf, bm, xp, pr, stem, pw, aw, ap, ay, rs; };  // xp: conv_xp_kernel with xp column tiles per workgroup; pr: conv_pr_kernel; stem: conv_stem_kernel; pw: conv_pw_kernel; aw: conv_aw_kernel
-constexpr Variant kVariants[] = {
-    {128, 4, 8, 0, 0, 128}, {128, 3, 8, 0, 0, 128}, {128, 2, 8, 0, 0, 128}, {64, 4, 8, 0, 0, 128}, {64, 3, 8, 0, 0, 128},
-    {64, 2, 8, 0, 0, 128}, {128, 4, 4, 0, 0, 128}, {128, 2, 4, 0, 0, 128}, {64, 3, 4, 0, 0, 128}, {64, 2, 4, 0, 0, 128},
-    {128, 4, 8, 1, 0, 128}, {128, 3, 8, 1, 0, 128}, {128, 2, 8, 1, 0, 128}, {64, 4, 8, 1, 0, 128}, {64, 3, 8, 1, 0, 128},   // 4 consumer + 4 loader waves
-    {128, 4, 8, 1, 1, 128}, {128, 4, 8, 0, 1, 128}, {128, 4, 4, 0, 1, 128}, {64, 4, 8, 1, 1, 128}, {64, 4, 8, 0, 1, 128},
-    {64, 4, 4, 0, 1, 128},                                                                                               // fragment prefetch
-    {256, 2, 8, 0, 0, 128}, {256, 3, 8, 0, 0, 128}, {256, 3, 8, 0, 0, 64},                                               // wide tiles
-    {128, 3, 8, 0, 0, 64}, {128, 2, 8, 0, 0, 64},                                                                        // 64-row tiles: 2 workgroups per CU on the N = 256 layers
-    {128, 5, 4, 0, 0, 128, 1}, {128, 5, 4, 0, 0, 128, 2}, {128, 5, 4, 0, 0, 128, 4},                                     // register-resident A panel (expansion 1x1 convs, sat_conv_xp.inc)
-    {128, 6, 8, 1, 0, 128, 0, 1},                                                                                        // LDS-resident input patch (3x3 / stride 1, sat_conv_pr.inc)
-    {64, 1, 4, 0, 0, 128, 0, 0, 1},                                                                                      // persistent stem kernel: weights in registers, input row segments in LDS (sat_conv_stem.inc)
-    {128, 1, 4, 0, 0, 128, 0, 0, 0, 1},                                                                                  // LDS-resident input patch + weights straight into registers from the fragment-ordered copy (3x3 / stride 1, sat_conv_pw.inc)
-    {128, 3, 4, 0, 0, 128, 0, 0, 0, 0, 1},                                                                               // 1x1: activations through registers into LDS, weights straight into registers (sat_conv_aw.inc)
-    {256, 3, 8, 0, 0, 128, 0, 0, 0, 0, 2},                                                                               // ... eight waves, 256-column tiles: the activations staged once per row tile
-    {128, 2, 4, 0, 0, 128, 0, 0, 0, 0, 0, 1},                                                                            // expansion 1x1 (K = 256): weights resident in registers, the workgroup persistent over row tiles (sat_conv_ap.inc)
-    {128, 2, 4, 0, 0, 128, 0, 0, 0, 0, 0, 0, 1},                                                                         // conv1 that also finishes the previous bottleneck: operand = relu(bn3(c3) + y), written out as it goes (sat_conv_ay.inc)
-    {256, 2, 8, 0, 0, 128, 0, 0, 0, 0, 0, 0, 2},                                                                         // ... eight waves, 256-column tiles
-    {64, 1, 4, 0, 0, 128, 0, 0, 0, 0, 0, 0, 0, 1},                                                                       // 3x3 / stride 1 over 32 channels on large maps (Inception stem): weights in registers, whole input rows in LDS (sat_conv_rs.inc)
-    {64, 1, 4, 0, 0, 128, 0, 0, 0, 0, 0, 0, 0, 2},                                                                       // ... 64 -> 64 channels on 56 x 56 maps (ResNet layer 1): two output rows per step, statistics per workgroup
-    {64, 1, 4, 0, 0, 128, 0, 0, 0, 0, 0, 0, 0, 3},                                                                       // ... 3 x 3 / stride 2 over the image's padded 8 channels -> 32 (the first conv of the Inception stem)
-    {64, 1, 4, 0, 0, 128, 0, 0, 0, 0, 0, 0, 0, 4},                                                                       // ... ResNet's 7 x 7 stem in the stem kernel's layout
-};
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
-constexpr int kVariantPr = 29;
 
 #include "sat_conv_xp.inc"
 #include "sat_conv_pr.inc"
@@ -655,51 +617,72 @@ constexpr int kVariantPr = 29;
 #include "sat_conv_ay.inc"
 #include "sat_conv_rs.inc"
 
-int launch_variant(int v, ConvArgs& a, int groups, hipStream_t s) {
-    switch (v) {
-        case 0: return launch_glds<128, 4, 8>(a, groups, s);
-        case 1: return launch_glds<128, 3, 8>(a, groups, s);
-        case 2: return launch_glds<128, 2, 8>(a, groups, s);
-        case 3: return launch_glds<64, 4, 8>(a, groups, s);
-        case 4: return launch_glds<64, 3, 8>(a, groups, s);
-        case 5: return launch_glds<64, 2, 8>(a, groups, s);
-        case 6: return launch_glds<128, 4, 4>(a, groups, s);
-        case 7: return launch_glds<128, 2, 4>(a, groups, s);
-        case 8: return launch_glds<64, 3, 4>(a, groups, s);
-        case 9: return launch_glds<64, 2, 4>(a, groups, s);
-        case 10: return launch_glds<128, 4, 8, true>(a, groups, s);
-        case 11: return launch_glds<128, 3, 8, true>(a, groups, s);
-        case 12: return launch_glds<128, 2, 8, true>(a, groups, s);
-        case 13: return launch_glds<64, 4, 8, true>(a, groups, s);
-        case 14: return launch_glds<64, 3, 8, true>(a, groups, s);
-        case 15: return launch_glds<128, 4, 8, true, true>(a, groups, s);
-        case 16: return launch_glds<128, 4, 8, false, true>(a, groups, s);
-        case 17: return launch_glds<128, 4, 4, false, true>(a, groups, s);
-        case 18: return launch_glds<64, 4, 8, true, true>(a, groups, s);
-        case 19: return launch_glds<64, 4, 8, false, true>(a, groups, s);
-        case 20: return launch_glds<64, 4, 4, false, true>(a, groups, s);
-        case 21: return launch_glds<256, 2, 8, false, false, 128>(a, groups, s);
-        case 22: return launch_glds<256, 3, 8, false, false, 128>(a, groups, s);
-        case 23: return launch_glds<256, 3, 8, false, false, 64>(a, groups, s);
-        case 24: return launch_glds<128, 3, 8, false, false, 64>(a, groups, s);
-        case 25: return launch_glds<128, 2, 8, false, false, 64>(a, groups, s);
-        case 26: return launch_xp(a, 1, groups, s);
-        case 27: return launch_xp(a, 2, groups, s);
-        case 28: return launch_xp(a, 4, groups, s);
-        case 29: return launch_pr(a, groups, s);
-        case 30: return launch_stem(a, groups, s);
-        case 31: return launch_pw(a, groups, s);
-        case 32: return launch_aw<4>(a, groups, s);
-        case 33: return launch_aw<8>(a, groups, s);
-        case 34: return launch_ap(a, groups, s);
-        case 35: return launch_ay<4>(a, groups, s);
-        case 36: return launch_ay<8>(a, groups, s);
-        case 37: return launch_rs(a, groups, s);
-        case 38: return launch_rs64(a, groups, s);
-        case 39: return launch_rs8(a, groups, s);
-        case 40: return launch_rs_stem(a, groups, s);
-        default: return SAT_ERR_ARG;
+// Kernel variants.  A row names its kernel family, the family's parameter and its launcher.
+enum Family { kRing, kXp, kPr, kStem, kPw, kAw, kAp, kAy, kRs, kRs64, kRs8, kRsStem };
+const char* const kFamilyName[] = {"ring", "xp", "pr", "stem", "pw", "aw", "ap", "ay", "rs", "rs64", "rs8", "rs_stem"};
+typedef int (*Launcher)(ConvArgs&, int, hipStream_t);
+struct Variant {
+    Family family;
+    int param;              // kXp: column tiles per workgroup; kAw, kAy: waves
+    int bn, s, nw, bm;      // kRing: tile width, ring stages, waves, tile rows
+    bool spec, pf;          // kRing: wave specialisation, fragment prefetch
+    Launcher launch;
+};
+// ring kernel: LDS = S * (BM/8 + BN/8) KB (+ the table) decides workgroups per CU
+template <int BN, int S, int NW, bool SPEC = false, bool PF = false, int BM = 128>
+constexpr Variant ring() { return {kRing, 0, BN, S, NW, BM, SPEC, PF, launch_glds<BN, S, NW, SPEC, PF, BM>}; }
+constexpr Variant row(Family f, Launcher launch, int param = 0) { return {f, param, 0, 0, 0, 0, false, false, launch}; }
+
+// sat_op.variant is a row number + 1, and saved tuning tables (tune/gfx950.json) store it: rows are appended, never reordered
+constexpr Variant kVariants[] = {
+    ring<128, 4, 8>(), ring<128, 3, 8>(), ring<128, 2, 8>(), ring<64, 4, 8>(), ring<64, 3, 8>(),
+    ring<64, 2, 8>(), ring<128, 4, 4>(), ring<128, 2, 4>(), ring<64, 3, 4>(), ring<64, 2, 4>(),
+    ring<128, 4, 8, true>(), ring<128, 3, 8, true>(), ring<128, 2, 8, true>(), ring<64, 4, 8, true>(), ring<64, 3, 8, true>(),   // 4 consumer + 4 loader waves
+    ring<128, 4, 8, true, true>(), ring<128, 4, 8, false, true>(), ring<128, 4, 4, false, true>(), ring<64, 4, 8, true, true>(),
+    ring<64, 4, 8, false, true>(), ring<64, 4, 4, false, true>(),                                                              // fragment prefetch
+    ring<256, 2, 8>(), ring<256, 3, 8>(), ring<256, 3, 8, false, false, 64>(),                                                 // wide tiles
+    ring<128, 3, 8, false, false, 64>(), ring<128, 2, 8, false, false, 64>(),        // 64-row tiles: 2 workgroups per CU on the N = 256 layers
+    row(kXp, launch_xp<1>, 1), row(kXp, launch_xp<2>, 2), row(kXp, launch_xp<4>, 4),      // register-resident A panel (expansion 1x1 convs, sat_conv_xp.inc)
+    row(kPr, launch_pr),             // LDS-resident input patch (3x3 / stride 1, sat_conv_pr.inc)
+    row(kStem, launch_stem),         // persistent stem kernel: weights in registers, input row segments in LDS (sat_conv_stem.inc)
+    row(kPw, launch_pw),             // LDS-resident input patch + weights straight into registers from the fragment-ordered copy (3x3 / stride 1, sat_conv_pw.inc)
+    row(kAw, launch_aw<4>, 4),       // 1x1: activations through registers into LDS, weights straight into registers (sat_conv_aw.inc)
+    row(kAw, launch_aw<8>, 8),       // ... eight waves, 256-column tiles: the activations staged once per row tile
+    row(kAp, launch_ap),             // expansion 1x1 (K = 256): weights resident in registers, the workgroup persistent over row tiles (sat_conv_ap.inc)
+    row(kAy, launch_ay<4>, 4),       // conv1 that also finishes the previous bottleneck: operand = relu(bn3(c3) + y), written out as it goes (sat_conv_ay.inc)
+    row(kAy, launch_ay<8>, 8),       // ... eight waves, 256-column tiles
+    row(kRs, launch_rs),             // 3x3 / stride 1 over 32 channels on large maps (Inception stem): weights in registers, whole input rows in LDS (sat_conv_rs.inc)
+    row(kRs64, launch_rs64),         // ... 64 -> 64 channels on 56 x 56 maps (ResNet layer 1): two output rows per step, statistics per workgroup
+    row(kRs8, launch_rs8),           // ... 3 x 3 / stride 2 over the image's padded 8 channels -> 32 (the first conv of the Inception stem)
+    row(kRsStem, launch_rs_stem),    // ... ResNet's 7 x 7 stem in the stem kernel's layout
+};
+constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
+
+constexpr int find_variant(Family f, int param = 0) {
+    for (int v = 0; v < kNumVariants; ++v)
+        if (kVariants[v].family == f && kVariants[v].param == param) return v;
+    return -1;
+}
+// a plain ring variant: unified waves, no fragment prefetch, 128-row tiles
+constexpr int find_ring(int bn, int s, int nw) {
+    for (int v = 0; v < kNumVariants; ++v) {
+        const Variant& k = kVariants[v];
+        if (k.family == kRing && k.bn == bn && k.s == s && k.nw == nw && !k.spec && !k.pf && k.bm == 128) return v;
     }
+    return -1;
+}
+// the variants heuristic_variant picks
+constexpr int kRing128 = find_ring(128, 4, 8), kRing128Short = find_ring(128, 2, 8), kRing64 = find_ring(64, 3, 8), kRing64Short = find_ring(64, 2, 8);
+constexpr int kVariantPr = find_variant(kPr), kVariantStem = find_variant(kStem), kVariantAy4 = find_variant(kAy, 4),
+              kVariantAy8 = find_variant(kAy, 8), kVariantRs = find_variant(kRs), kVariantRs64 = find_variant(kRs64),
+              kVariantRs8 = find_variant(kRs8), kVariantRsStem = find_variant(kRsStem);
+static_assert(kNumVariants == 41, "tune/gfx950.json (\"variants\": 41) and the tests number the variants");
+static_assert(kRing128 == 0 && kRing128Short == 2 && kRing64 == 4 && kRing64Short == 5 && kVariantPr == 29 && kVariantStem == 30 &&
+                  kVariantAy4 == 35 && kVariantAy8 == 36 && kVariantRs == 37 && kVariantRs64 == 38 && kVariantRs8 == 39 && kVariantRsStem == 40,
+              "the heuristic's variants keep their numbers");
+
+int launch_variant(int v, ConvArgs& a, int groups, hipStream_t s) {
+    return (v >= 0 && v < kNumVariants) ? kVariants[v].launch(a, groups, s) : SAT_ERR_ARG;
 }
 
 // What fixes the BITS of a variant's BatchNorm column sums (the conv output itself is bit-identical across ring variants and
@@ -708,19 +691,23 @@ int launch_variant(int v, ConvArgs& a, int groups, hipStream_t s) {
 // grouped launch and an ungrouped one on variants of one signature give a batch the same bits.
 // What fixes the bits of the conv OUTPUT: the order in which the K axis is walked.  0: tap major (ring kernel, conv_xp_kernel,
 // conv_aw_kernel, stem kernel: bit-identical outputs), 1: channel-block major (conv_pr_kernel, conv_pw_kernel: bit-identical to each other)
-int output_family(int v) { return (kVariants[v].pr || kVariants[v].pw) ? 1 : 0; }
+int output_family(int v) { return (kVariants[v].family == kPr || kVariants[v].family == kPw) ? 1 : 0; }
 constexpr int kFamilySig = 100000;          // signature constraints >= this one name an output family only (inference: no statistics)
-bool signature_matches(int v, int want);
 
 int stat_signature(int v) {
     const Variant& k = kVariants[v];
-    if (k.rs) return k.rs == 2 ? 7001 : (k.rs == 4 ? 7002 : 7000);       // (a wave's pixels of a row, then the four waves in order / of a workgroup's whole run of steps)
-    if (k.ap) return 6000;          // (a lane's 64 rows of a tile, the tiles of a worker in order, then the two halves)
-    if (k.aw || k.ay) return 5000;          // (a lane's 64 rows, then the two halves: the same for the four- and the eight-wave form)
-    if (k.pw) return 4000;
-    if (k.stem) return 3000;
-    if (k.pr) return 2000;
-    if (k.xp) return 1000;
+    switch (k.family) {
+        case kRs: case kRs8: return 7000;       // (a wave's pixels of a row, then the four waves in order
+        case kRs64: return 7001;
+        case kRsStem: return 7002;              //  / of a workgroup's whole run of steps)
+        case kAp: return 6000;                  // (a lane's 64 rows of a tile, the tiles of a worker in order, then the two halves)
+        case kAw: case kAy: return 5000;        // (a lane's 64 rows, then the two halves: the same for the four- and the eight-wave form)
+        case kPw: return 4000;
+        case kStem: return 3000;
+        case kPr: return 2000;
+        case kXp: return 1000;
+        case kRing: break;
+    }
     const int cw = k.spec ? k.nw / 2 : k.nw;
     const int wgm = (cw == 4) ? 2 : ((k.bm == 128 && k.bn == 64) ? 4 : 2);
     return k.bm * 8 + wgm;
@@ -745,6 +732,7 @@ ConvArgs make_args(const sat_op* op) {
         a.in_gamma = op->gamma1; a.in_beta = op->beta1;
         a.in_running_mean = op->running_mean1; a.in_running_var = op->running_var1;
         a.in_count = (double)op->count; a.in_momentum = op->momentum; a.in_eps = op->eps;
+        a.in_inv = a.in_count > 0 ? sat_stat_inv(a.in_count) : 0.0;
     }
     a.out_scale = op->scale1; a.out_shift = op->shift1;        // inference epilogue: affine (+ residual) (+ ReLU)
     a.residual = (const bf16_t*)op->in1;
@@ -778,15 +766,21 @@ int op_groups(const sat_op* op) { return op->groups > 1 ? op->groups : 1; }
 bool variant_ok(int v, const ConvArgs& a) {
     if (v < 0 || v >= kNumVariants) return false;
     const Variant& k = kVariants[v];
-    if (k.ay) return ay_ok(a, k.ay == 2 ? 8 : 4);
-    if (a.in_res) return false;
-    if (k.rs) return k.rs == 2 ? rs64_ok(a) : (k.rs == 3 ? rs8_ok(a) : (k.rs == 4 ? rs_stem_ok(a) : rs_ok(a)));                                      // only conv_ay_kernel builds its operand from two tensors
-    if (k.ap) return ap_ok(a);
-    if (k.aw) return aw_ok(a, k.aw == 2 ? 8 : 4);
-    if (k.pw) return pw_ok(a);
-    if (k.stem) return stem_ok(a);
-    if (k.pr) return pr_ok(a);
-    if (k.xp) return xp_ok(a, k.xp);
+    if (k.family == kAy) return ay_ok(a, k.param);
+    if (a.in_res) return false;                                      // only conv_ay_kernel builds its operand from two tensors
+    switch (k.family) {
+        case kRs: return rs_ok(a);
+        case kRs64: return rs64_ok(a);
+        case kRs8: return rs8_ok(a);
+        case kRsStem: return rs_stem_ok(a);
+        case kAp: return ap_ok(a);
+        case kAw: return aw_ok(a, k.param);
+        case kPw: return pw_ok(a);
+        case kStem: return stem_ok(a);
+        case kPr: return pr_ok(a);
+        case kXp: return xp_ok(a, k.param);
+        case kAy: case kRing: break;
+    }
     if (k.bn >= 128 && a.N <= 64) return false;
     if (k.bn == 256 && a.N <= 128) return false;
     if ((k.spec || k.pf) && a.in_affine) return false;               // the in-LDS input transform lives in the plain unified-wave loop
@@ -798,17 +792,17 @@ bool variant_ok(int v, const ConvArgs& a) {
 int heuristic_variant(const ConvArgs& a) {
     // 128x128 with a deep ring when it still leaves >= 2 tiles per CU and K is long enough to use the ring;
     // otherwise 128x64 with a shallower ring (more workgroups per CU to overlap prologue/epilogue phases)
-    if (a.in_res) return ay_ok(a, 4) ? 35 : 36;           // the operand built from the raw conv3 tensor and the residual: conv_ay_kernel
+    if (a.in_res) return ay_ok(a, 4) ? kVariantAy4 : kVariantAy8;      // the operand built from the raw conv3 tensor and the residual: conv_ay_kernel
     if (a.in_affine && !a.linear) return kVariantPr;      // 3x3 with a fused input BatchNorm: the LDS-resident patch (the builder fuses bn1 only where it can run)
-    if (stem_ok(a)) return 30;                            // the op program's stem layout: the persistent stem kernel
-    if (rs_ok(a)) return 37;                              // 3x3 over 32 channels on a large map (Inception stem): whole input rows in LDS
-    if (rs_stem_ok(a)) return 40;                         // ... the stem layout with an inference epilogue (conv_stem_kernel has none)
-    if (rs8_ok(a)) return 39;                             // ... the stem's first conv (stride 2 over the padded image)
-    if (rs64_ok(a)) return 38;                            // 3x3 64 -> 64 on ~56-pixel rows (ResNet layer 1): the same, two output rows per step
+    if (stem_ok(a)) return kVariantStem;                  // the op program's stem layout: the persistent stem kernel
+    if (rs_ok(a)) return kVariantRs;                      // 3x3 over 32 channels on a large map (Inception stem): whole input rows in LDS
+    if (rs_stem_ok(a)) return kVariantRsStem;             // ... the stem layout with an inference epilogue (conv_stem_kernel has none)
+    if (rs8_ok(a)) return kVariantRs8;                    // ... the stem's first conv (stride 2 over the padded image)
+    if (rs64_ok(a)) return kVariantRs64;                  // 3x3 64 -> 64 on ~56-pixel rows (ResNet layer 1): the same, two output rows per step
     const long t128 = (long)sat_cdiv(a.M, 128) * sat_cdiv(a.N, 128);
     const int nk = sat_cdiv(a.K, 64);
-    if (a.N > 64 && t128 >= 512) return nk <= 4 ? 2 : 0;
-    return nk <= 4 ? 5 : 4;
+    if (a.N > 64 && t128 >= 512) return nk <= 4 ? kRing128Short : kRing128;
+    return nk <= 4 ? kRing64Short : kRing64;
 }
 
 // argument checks + parity / group bookkeeping shared by the launch and the tuner
@@ -904,8 +898,14 @@ static int tune_one(const sat_op* op, int groups, int want_sig, int reps, float*
             if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { rc = SAT_ERR_UNSUPPORTED; break; }
             if (round >= 1 && ms / reps < tmin) tmin = ms / reps;      // per launch
         }
-        if (verbose) fprintf(stderr, "  tune M=%d N=%d K=%d G=%d v%d(%d,%d,%d,%s) %.2f us\n", a.M, a.N, a.K, groups, v, kVariants[v].bn,
-                             kVariants[v].s, kVariants[v].nw, kVariants[v].spec ? (kVariants[v].pf ? "spec+pf" : "spec") : (kVariants[v].pf ? "pf" : "-"), tmin * 1e3f);
+        if (verbose) {
+            const Variant& k = kVariants[v];
+            if (k.family == kRing)
+                fprintf(stderr, "  tune M=%d N=%d K=%d G=%d v%d(ring %dx%d,%d,%d,%s) %.2f us\n", a.M, a.N, a.K, groups, v, k.bm, k.bn, k.s, k.nw,
+                        k.spec ? (k.pf ? "spec+pf" : "spec") : (k.pf ? "pf" : "-"), tmin * 1e3f);
+            else
+                fprintf(stderr, "  tune M=%d N=%d K=%d G=%d v%d(%s %d) %.2f us\n", a.M, a.N, a.K, groups, v, kFamilyName[k.family], k.param, tmin * 1e3f);
+        }
         timed.emplace_back(tmin, v);
     }
     if (rc != SAT_OK) return rc;

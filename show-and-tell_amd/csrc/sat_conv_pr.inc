@@ -39,10 +39,8 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs p_) {
     const int wm = (wave >> 1) & 1, wn = wave & 1;           // consumers (waves 0-3): 2 x 2
     const int r = lane & 31, h = lane >> 5;
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int tile_m = swz / p.tiles_n, tile_n = swz - tile_m * p.tiles_n;
+    const int tile = xcd_tile();
+    const int tile_m = tile / p.tiles_n, tile_n = tile - tile_m * p.tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int W = p.Win;
     const int NCB = p.Cin >> 6;                               // 64-channel blocks
@@ -134,37 +132,7 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs p_) {
     // otherwise) -- 20-24 KB per channel block instead of the 16 KB per K-step (nine times more) an in-ring transform touches.
     // Zero padding stays zero: padded taps read the zero row, never the patch.
     float* in_tab = (float*)(smem + (AFF ? TAB : 0));
-    if constexpr (AFF) {
-        const double inv = p.in_inv;                          // 1 / (2^22 * count), divided on the host
-        for (int c = tid; c < p.Cin; c += NT) {
-            float sc, sh;
-            if (p.in_acc) {
-                const long long s1 = p.in_acc[c], s2 = p.in_acc[p.Cin + c];
-                const double mean = (double)s1 * inv;
-                double var = (double)s2 * inv - mean * mean;
-                if (var < 0.0) var = 0.0;
-                const float invstd = 1.0f / sqrtf((float)var + p.in_eps);
-                sc = p.in_gamma[c] * invstd;
-                sh = p.in_beta[c] - (float)mean * sc;
-                if (bid == 0) {
-                    if (p.in_running_mean) {
-                        const double unbiased = p.in_count > 1.0 ? var * p.in_count / (p.in_count - 1.0) : var;
-                        p.in_running_mean[c] = (float)((1.0 - p.in_momentum) * p.in_running_mean[c] + p.in_momentum * (double)(float)mean);
-                        p.in_running_var[c] = (float)((1.0 - p.in_momentum) * p.in_running_var[c] + p.in_momentum * (double)(float)unbiased);
-                    }
-                    if (p.in_acc_clear) {
-                        p.in_acc_clear[c] = 0;
-                        p.in_acc_clear[p.Cin + c] = 0;
-                    }
-                }
-            } else {
-                sc = p.in_scale[c];
-                sh = p.in_shift[c];
-            }
-            in_tab[c] = sc;
-            in_tab[p.Cin + c] = sh;
-        }
-    }
+    if constexpr (AFF) conv_in_table<NT>(p, in_tab);
     // loader lane ll = tid - 256 owns the 16-byte channel group lc = ll & 7 of rows (ll >> 3) + 32 j: (row >> 1) & 7 is the same for
     // all of them, so every address is one base plus an immediate
     auto xform_patch = [&](int buf, int cb) {
@@ -346,12 +314,10 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs p_) {
                 q += red[(g * 2 + 1) * BN + c];
             }
             if (p.acc) {
-                atomicAdd((unsigned long long*)(p.acc + col), (unsigned long long)__double2ll_rn((double)s * kStatScale));
-                atomicAdd((unsigned long long*)(p.acc + p.N + col), (unsigned long long)__double2ll_rn((double)q * kStatScale));
+                stat_acc_add(p.acc, p.N, s, q, col);
             }
             if (p.stat_partial) {
-                p.stat_partial[((long)tile_m * 2 + 0) * p.N + col] = s;
-                p.stat_partial[((long)tile_m * 2 + 1) * p.N + col] = q;
+                stat_slab_store(p.stat_partial, tile_m, p.N, s, q, col);
             }
         }
     }
@@ -375,21 +341,8 @@ bool pr_ok(const ConvArgs& a) {
 int launch_pr(ConvArgs& a, int groups, hipStream_t s) {
     if (!pr_ok(a)) return SAT_ERR_UNSUPPORTED;
     a.tiles_n = sat_cdiv(a.N, 128);
-    const dim3 grid(sat_cdiv(a.M, 128) * a.tiles_n, groups), block(512);
-    hipEvent_t e0 = t_ev_start, e1 = t_ev_stop;
-    t_ev_start = t_ev_stop = nullptr;
-    a.in_inv = a.in_count > 0 ? 1.0 / (kStatScale * a.in_count) : 0.0;
     const bool small = 128 + 2 * a.Win + 2 <= 160;      // the smaller patch leaves room for a seventh ring slot: one more weight stage in flight
-#define SAT_PR_LAUNCH(S_, P_, AFF_)                                                                                \
-    do {                                                                                                           \
-        if (e0) hipExtLaunchKernelGGL((conv_pr_kernel<S_, P_, AFF_>), grid, block, 0, s, e0, e1, 0, a);            \
-        else hipLaunchKernelGGL((conv_pr_kernel<S_, P_, AFF_>), grid, block, 0, s, a);                             \
-    } while (0)
-    if (small && a.in_affine) SAT_PR_LAUNCH(7, 20, true);
-    else if (small) SAT_PR_LAUNCH(7, 20, false);
-    else if (a.in_affine) SAT_PR_LAUNCH(6, 24, true);
-    else SAT_PR_LAUNCH(6, 24, false);
-#undef SAT_PR_LAUNCH
-    SAT_LAUNCH_CHECK();
-    return SAT_OK;
+    const ConvKernel k = small ? (a.in_affine ? conv_pr_kernel<7, 20, true> : conv_pr_kernel<7, 20, false>)
+                               : (a.in_affine ? conv_pr_kernel<6, 24, true> : conv_pr_kernel<6, 24, false>);
+    return launch_conv(k, dim3(sat_cdiv(a.M, 128) * a.tiles_n, groups), dim3(512), 0, s, a);
 }

@@ -160,12 +160,10 @@ __global__ __launch_bounds__(256, 2) void conv_rs_kernel(const ConvArgs p_) {
                 q += red[(g * 2 + 1) * BN + tid];
             }
             if (p.stat_partial) {
-                p.stat_partial[((long)t * 2 + 0) * p.N + tid] = s;
-                p.stat_partial[((long)t * 2 + 1) * p.N + tid] = q;
+                stat_slab_store(p.stat_partial, t, p.N, s, q, tid);
             }
             if (p.acc) {                                               // few-tile programs: the integer accumulators directly
-                atomicAdd((unsigned long long*)(p.acc + tid), (unsigned long long)__double2ll_rn((double)s * kStatScale));
-                atomicAdd((unsigned long long*)(p.acc + p.N + tid), (unsigned long long)__double2ll_rn((double)q * kStatScale));
+                stat_acc_add(p.acc, p.N, s, q, tid);
             }
         }
         {
@@ -205,28 +203,16 @@ bool rs_ok(const ConvArgs& a) {
 }
 
 template <int NJ>
-static int launch_rs_t(const ConvArgs& a, dim3 grid, size_t lds, hipEvent_t e0, hipEvent_t e1, hipStream_t s) {
-    static bool raised = false;            // more than 64 KB of dynamic LDS needs the attribute once per kernel
-    if (!raised && lds > 64 * 1024) {
-        if (hipFuncSetAttribute((const void*)conv_rs_kernel<NJ>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess)
-            return SAT_ERR_UNSUPPORTED;
-        raised = true;
-    }
-    if (e0) hipExtLaunchKernelGGL(conv_rs_kernel<NJ>, grid, dim3(256), lds, s, e0, e1, 0, a);
-    else hipLaunchKernelGGL(conv_rs_kernel<NJ>, grid, dim3(256), lds, s, a);
-    return SAT_OK;
+static int launch_rs_t(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
+    static bool raised = false;
+    return launch_conv(conv_rs_kernel<NJ>, grid, dim3(256), lds, s, a, &raised, 80 * 1024);
 }
 
 int launch_rs(ConvArgs& a, int groups, hipStream_t s) {
     if (!rs_ok(a)) return SAT_ERR_UNSUPPORTED;
     const int rows = a.M / a.Wout;
     const dim3 grid(rows < 512 ? rows : 512, groups);                // persistent over runs of output rows: two workgroups per CU
-    hipEvent_t e0 = t_ev_start, e1 = t_ev_stop;
-    t_ev_start = t_ev_stop = nullptr;
-    const int rc = a.N == 64 ? launch_rs_t<2>(a, grid, rs_lds_bytes(a), e0, e1, s) : launch_rs_t<1>(a, grid, rs_lds_bytes(a), e0, e1, s);
-    if (rc != SAT_OK) return rc;
-    SAT_LAUNCH_CHECK();
-    return SAT_OK;
+    return a.N == 64 ? launch_rs_t<2>(a, grid, rs_lds_bytes(a), s) : launch_rs_t<1>(a, grid, rs_lds_bytes(a), s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -361,12 +347,10 @@ __global__ __launch_bounds__(256, 2) void conv_rs64_kernel(const ConvArgs p_) {
             const float cs = red[((2 * c2) * 2 + 0) * 32 + rr] + red[((2 * c2 + 1) * 2 + 0) * 32 + rr];
             const float cq = red[((2 * c2) * 2 + 1) * 32 + rr] + red[((2 * c2 + 1) * 2 + 1) * 32 + rr];
             if (p.stat_partial) {
-                p.stat_partial[((long)blockIdx.x * 2 + 0) * p.N + tid] = cs;
-                p.stat_partial[((long)blockIdx.x * 2 + 1) * p.N + tid] = cq;
+                stat_slab_store(p.stat_partial, blockIdx.x, p.N, cs, cq, tid);
             }
             if (p.acc) {
-                atomicAdd((unsigned long long*)(p.acc + tid), (unsigned long long)__double2ll_rn((double)cs * kStatScale));
-                atomicAdd((unsigned long long*)(p.acc + p.N + tid), (unsigned long long)__double2ll_rn((double)cq * kStatScale));
+                stat_acc_add(p.acc, p.N, cs, cq, tid);
             }
         }
         if (p.stat_partial) {                                          // the slabs no workgroup owns: zeros
@@ -398,19 +382,8 @@ bool rs64_ok(const ConvArgs& a) {
 
 int launch_rs64(ConvArgs& a, int groups, hipStream_t s) {
     if (!rs64_ok(a)) return SAT_ERR_UNSUPPORTED;
-    const dim3 grid(rs64_grid(a), groups);
-    const size_t lds = rs64_lds_bytes(a);
     static bool raised = false;
-    if (!raised && lds > 64 * 1024) {
-        if (hipFuncSetAttribute((const void*)conv_rs64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess) return SAT_ERR_UNSUPPORTED;
-        raised = true;
-    }
-    hipEvent_t e0 = t_ev_start, e1 = t_ev_stop;
-    t_ev_start = t_ev_stop = nullptr;
-    if (e0) hipExtLaunchKernelGGL(conv_rs64_kernel, grid, dim3(256), lds, s, e0, e1, 0, a);
-    else hipLaunchKernelGGL(conv_rs64_kernel, grid, dim3(256), lds, s, a);
-    SAT_LAUNCH_CHECK();
-    return SAT_OK;
+    return launch_conv(conv_rs64_kernel, dim3(rs64_grid(a), groups), dim3(256), rs64_lds_bytes(a), s, a, &raised, 80 * 1024);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -522,12 +495,10 @@ __global__ __launch_bounds__(256, 2) void conv_rs8_kernel(const ConvArgs p_) {
                 q += red[(g * 2 + 1) * BN + tid];
             }
             if (p.stat_partial) {
-                p.stat_partial[((long)t * 2 + 0) * p.N + tid] = s;
-                p.stat_partial[((long)t * 2 + 1) * p.N + tid] = q;
+                stat_slab_store(p.stat_partial, t, p.N, s, q, tid);
             }
             if (p.acc) {
-                atomicAdd((unsigned long long*)(p.acc + tid), (unsigned long long)__double2ll_rn((double)s * kStatScale));
-                atomicAdd((unsigned long long*)(p.acc + p.N + tid), (unsigned long long)__double2ll_rn((double)q * kStatScale));
+                stat_acc_add(p.acc, p.N, s, q, tid);
             }
         }
         {
@@ -562,13 +533,7 @@ bool rs8_ok(const ConvArgs& a) {
 int launch_rs8(ConvArgs& a, int groups, hipStream_t s) {
     if (!rs8_ok(a)) return SAT_ERR_UNSUPPORTED;
     const int rows = a.M / a.Wout;
-    const dim3 grid(rows < 512 ? rows : 512, groups);
-    hipEvent_t e0 = t_ev_start, e1 = t_ev_stop;
-    t_ev_start = t_ev_stop = nullptr;
-    if (e0) hipExtLaunchKernelGGL(conv_rs8_kernel, grid, dim3(256), rs8_lds_bytes(a), s, e0, e1, 0, a);
-    else hipLaunchKernelGGL(conv_rs8_kernel, grid, dim3(256), rs8_lds_bytes(a), s, a);
-    SAT_LAUNCH_CHECK();
-    return SAT_OK;
+    return launch_conv(conv_rs8_kernel, dim3(rows < 512 ? rows : 512, groups), dim3(256), rs8_lds_bytes(a), s, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -691,12 +656,10 @@ __global__ __launch_bounds__(256, 2) void conv_rs_stem_kernel(const ConvArgs p_)
                 q += red[(g * 2 + 1) * BN + tid];
             }
             if (p.stat_partial) {
-                p.stat_partial[((long)blockIdx.x * 2 + 0) * p.N + tid] = s;
-                p.stat_partial[((long)blockIdx.x * 2 + 1) * p.N + tid] = q;
+                stat_slab_store(p.stat_partial, blockIdx.x, p.N, s, q, tid);
             }
             if (p.acc) {
-                atomicAdd((unsigned long long*)(p.acc + tid), (unsigned long long)__double2ll_rn((double)s * kStatScale));
-                atomicAdd((unsigned long long*)(p.acc + p.N + tid), (unsigned long long)__double2ll_rn((double)q * kStatScale));
+                stat_acc_add(p.acc, p.N, s, q, tid);
             }
         }
         if (p.stat_partial) {
@@ -720,11 +683,5 @@ bool rs_stem_ok(const ConvArgs& a) {
 
 int launch_rs_stem(ConvArgs& a, int groups, hipStream_t s) {
     if (!rs_stem_ok(a)) return SAT_ERR_UNSUPPORTED;
-    const dim3 grid(rs_stem_grid(a), groups);
-    hipEvent_t e0 = t_ev_start, e1 = t_ev_stop;
-    t_ev_start = t_ev_stop = nullptr;
-    if (e0) hipExtLaunchKernelGGL(conv_rs_stem_kernel, grid, dim3(256), rs_stem_lds_bytes(a), s, e0, e1, 0, a);
-    else hipLaunchKernelGGL(conv_rs_stem_kernel, grid, dim3(256), rs_stem_lds_bytes(a), s, a);
-    SAT_LAUNCH_CHECK();
-    return SAT_OK;
+    return launch_conv(conv_rs_stem_kernel, dim3(rs_stem_grid(a), groups), dim3(256), rs_stem_lds_bytes(a), s, a);
 }

@@ -154,12 +154,10 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(const ConvArgs p_) {
                 q += red[(g * 2 + 1) * BN + tid];
             }
             if (p.stat_partial) {
-                p.stat_partial[((long)tile * 2 + 0) * p.N + tid] = s;
-                p.stat_partial[((long)tile * 2 + 1) * p.N + tid] = q;
+                stat_slab_store(p.stat_partial, tile, p.N, s, q, tid);
             }
             if (p.acc) {                                               // few-tile programs: the integer accumulators directly
-                atomicAdd((unsigned long long*)(p.acc + tid), (unsigned long long)__double2ll_rn((double)s * kStatScale));
-                atomicAdd((unsigned long long*)(p.acc + p.N + tid), (unsigned long long)__double2ll_rn((double)q * kStatScale));
+                stat_acc_add(p.acc, p.N, s, q, tid);
             }
         }
 #pragma unroll
@@ -196,16 +194,9 @@ static int stem_max_segments(const ConvArgs& a) {
 }
 
 template <int NLOAD>
-static int launch_stem_t(const ConvArgs& a, dim3 grid, size_t lds, hipEvent_t e0, hipEvent_t e1, hipStream_t s) {
-    static bool raised = false;            // more than 64 KB of dynamic LDS needs the attribute once per kernel
-    if (!raised && lds > 64 * 1024) {
-        if (hipFuncSetAttribute((const void*)conv_stem_kernel<NLOAD>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
-            return SAT_ERR_UNSUPPORTED;
-        raised = true;
-    }
-    if (e0) hipExtLaunchKernelGGL(conv_stem_kernel<NLOAD>, grid, dim3(256), lds, s, e0, e1, 0, a);
-    else hipLaunchKernelGGL(conv_stem_kernel<NLOAD>, grid, dim3(256), lds, s, a);
-    return SAT_OK;
+static int launch_stem_t(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
+    static bool raised = false;
+    return launch_conv(conv_stem_kernel<NLOAD>, grid, dim3(256), lds, s, a, &raised, 96 * 1024);
 }
 
 int launch_stem(ConvArgs& a, int groups, hipStream_t s) {
@@ -215,22 +206,15 @@ int launch_stem(ConvArgs& a, int groups, hipStream_t s) {
     const dim3 grid(grid_x, groups);
     const int tail = 128 * (64 * 2 + 16) + 4 * 2 * 64 * 4;            // C tile + column-sum scratch
     const int nload = sat_cdiv((long)stem_max_segments(a) * 7 * (a.Win / 2), 256);
-    hipEvent_t e0 = t_ev_start, e1 = t_ev_stop;
-    t_ev_start = t_ev_stop = nullptr;
-    int rc;
     const size_t lds2 = (size_t)2 * nload * 4096 + tail;             // double buffered: two workgroups of <= 78 KB per CU
     if (nload >= 4 && nload <= 8 && lds2 <= 78 * 1024) {
         switch (nload) {
-            case 4: rc = launch_stem_t<4>(a, grid, lds2, e0, e1, s); break;
-            case 5: rc = launch_stem_t<5>(a, grid, lds2, e0, e1, s); break;
-            case 6: rc = launch_stem_t<6>(a, grid, lds2, e0, e1, s); break;
-            case 7: rc = launch_stem_t<7>(a, grid, lds2, e0, e1, s); break;
-            default: rc = launch_stem_t<8>(a, grid, lds2, e0, e1, s); break;
+            case 4: return launch_stem_t<4>(a, grid, lds2, s);
+            case 5: return launch_stem_t<5>(a, grid, lds2, s);
+            case 6: return launch_stem_t<6>(a, grid, lds2, s);
+            case 7: return launch_stem_t<7>(a, grid, lds2, s);
+            default: return launch_stem_t<8>(a, grid, lds2, s);
         }
-    } else {
-        rc = launch_stem_t<0>(a, grid, (size_t)kStemSeg * 7 * a.Win * 8 + tail, e0, e1, s);
     }
-    if (rc != SAT_OK) return rc;
-    SAT_LAUNCH_CHECK();
-    return SAT_OK;
+    return launch_stem_t<0>(a, grid, (size_t)kStemSeg * 7 * a.Win * 8 + tail, s);
 }

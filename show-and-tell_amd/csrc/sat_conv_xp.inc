@@ -39,10 +39,8 @@ __global__ __launch_bounds__(256, 2) void conv_xp_kernel(const ConvArgs p_) {
     const int r = lane & 31, h = lane >> 5;
     const int CT = p.ct;
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int tile_m = swz / p.tiles_n, ns = swz - tile_m * p.tiles_n;      // tiles_n = column splits: N / (CT * 128)
+    const int tile = xcd_tile();
+    const int tile_m = tile / p.tiles_n, ns = tile - tile_m * p.tiles_n;      // tiles_n = column splits: N / (CT * 128)
     const int m0 = tile_m * BM, nbase = ns * CT * BN;
     const int G = CT * NK;                                                   // weight stages of this workgroup
 
@@ -85,37 +83,7 @@ __global__ __launch_bounds__(256, 2) void conv_xp_kernel(const ConvArgs p_) {
     }
     // ---- (scale, shift) of the operand's BatchNorm into slot 4 (same arithmetic as conv_glds_kernel) while the panel is in flight ----
     float* in_tab = (float*)(smem + 4 * SLOT);
-    if constexpr (AFF) {
-        const double inv = p.in_inv;                     // 1 / (2^22 * count), divided on the host
-        for (int c = tid; c < p.Cin; c += NT) {
-            float sc, sh;
-            if (p.in_acc) {
-                const long long s1 = p.in_acc[c], s2 = p.in_acc[p.Cin + c];
-                const double mean = (double)s1 * inv;
-                double var = (double)s2 * inv - mean * mean;
-                if (var < 0.0) var = 0.0;
-                const float invstd = 1.0f / sqrtf((float)var + p.in_eps);
-                sc = p.in_gamma[c] * invstd;
-                sh = p.in_beta[c] - (float)mean * sc;
-                if (bid == 0) {
-                    if (p.in_running_mean) {
-                        const double unbiased = p.in_count > 1.0 ? var * p.in_count / (p.in_count - 1.0) : var;
-                        p.in_running_mean[c] = (float)((1.0 - p.in_momentum) * p.in_running_mean[c] + p.in_momentum * (double)(float)mean);
-                        p.in_running_var[c] = (float)((1.0 - p.in_momentum) * p.in_running_var[c] + p.in_momentum * (double)(float)unbiased);
-                    }
-                    if (p.in_acc_clear) {
-                        p.in_acc_clear[c] = 0;
-                        p.in_acc_clear[p.Cin + c] = 0;
-                    }
-                }
-            } else {
-                sc = p.in_scale[c];
-                sh = p.in_shift[c];
-            }
-            in_tab[c] = sc;
-            in_tab[p.Cin + c] = sh;
-        }
-    }
+    if constexpr (AFF) conv_in_table<NT>(p, in_tab);
     // the panel has landed and the table is visible
     wait_vmcnt<0>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -309,12 +277,10 @@ __global__ __launch_bounds__(256, 2) void conv_xp_kernel(const ConvArgs p_) {
                             q += red[(gm * 2 + 1) * BN + t];
                         }
                         if (p.acc) {
-                            atomicAdd((unsigned long long*)(p.acc + n0 + t), (unsigned long long)__double2ll_rn((double)s * kStatScale));
-                            atomicAdd((unsigned long long*)(p.acc + p.N + n0 + t), (unsigned long long)__double2ll_rn((double)q * kStatScale));
+                            stat_acc_add(p.acc, p.N, s, q, n0, t);
                         }
                         if (p.stat_partial) {
-                            p.stat_partial[((long)tile_m * 2 + 0) * p.N + n0 + t] = s;
-                            p.stat_partial[((long)tile_m * 2 + 1) * p.N + n0 + t] = q;
+                            stat_slab_store(p.stat_partial, tile_m, p.N, s, q, n0, t);
                         }
                     }
                     const char* c_lo = smem + cslot * SLOT;
@@ -351,39 +317,13 @@ bool xp_ok(const ConvArgs& a, int ct) {
            a.N % (ct * 128) == 0 && !a.residual && !a.out_scale && (!a.in_affine || a.Cin <= 512);
 }
 
-int launch_xp(ConvArgs& a, int ct, int groups, hipStream_t s) {
-    if (!xp_ok(a, ct)) return SAT_ERR_UNSUPPORTED;
-    a.ct = ct;
-    a.in_inv = a.in_count > 0 ? 1.0 / (kStatScale * a.in_count) : 0.0;
-    a.tiles_n = a.N / (ct * 128);
-    const dim3 grid(sat_cdiv(a.M, 128) * a.tiles_n, groups), block(256);
-    hipEvent_t e0 = t_ev_start, e1 = t_ev_stop;
-    t_ev_start = t_ev_stop = nullptr;
-    if (a.K == 256) {
-        if (a.in_affine) {
-            if (e0) hipExtLaunchKernelGGL((conv_xp_kernel<4, true>), grid, block, 0, s, e0, e1, 0, a);
-            else hipLaunchKernelGGL((conv_xp_kernel<4, true>), grid, block, 0, s, a);
-        } else {
-            if (e0) hipExtLaunchKernelGGL((conv_xp_kernel<4, false>), grid, block, 0, s, e0, e1, 0, a);
-            else hipLaunchKernelGGL((conv_xp_kernel<4, false>), grid, block, 0, s, a);
-        }
-    } else if (a.K == 128) {
-        if (a.in_affine) {
-            if (e0) hipExtLaunchKernelGGL((conv_xp_kernel<2, true>), grid, block, 0, s, e0, e1, 0, a);
-            else hipLaunchKernelGGL((conv_xp_kernel<2, true>), grid, block, 0, s, a);
-        } else {
-            if (e0) hipExtLaunchKernelGGL((conv_xp_kernel<2, false>), grid, block, 0, s, e0, e1, 0, a);
-            else hipLaunchKernelGGL((conv_xp_kernel<2, false>), grid, block, 0, s, a);
-        }
-    } else {
-        if (a.in_affine) {
-            if (e0) hipExtLaunchKernelGGL((conv_xp_kernel<1, true>), grid, block, 0, s, e0, e1, 0, a);
-            else hipLaunchKernelGGL((conv_xp_kernel<1, true>), grid, block, 0, s, a);
-        } else {
-            if (e0) hipExtLaunchKernelGGL((conv_xp_kernel<1, false>), grid, block, 0, s, e0, e1, 0, a);
-            else hipLaunchKernelGGL((conv_xp_kernel<1, false>), grid, block, 0, s, a);
-        }
-    }
-    SAT_LAUNCH_CHECK();
-    return SAT_OK;
+template <int CT>
+int launch_xp(ConvArgs& a, int groups, hipStream_t s) {
+    if (!xp_ok(a, CT)) return SAT_ERR_UNSUPPORTED;
+    a.ct = CT;
+    a.tiles_n = a.N / (CT * 128);
+    static constexpr ConvKernel kKernel[3][2] = {{conv_xp_kernel<1, false>, conv_xp_kernel<1, true>},      // [K / 128][in_affine]
+                                                 {conv_xp_kernel<2, false>, conv_xp_kernel<2, true>},
+                                                 {conv_xp_kernel<4, false>, conv_xp_kernel<4, true>}};
+    return launch_conv(kKernel[a.K / 128][a.in_affine], dim3(sat_cdiv(a.M, 128) * a.tiles_n, groups), dim3(256), 0, s, a);
 }

@@ -4,7 +4,7 @@
 //   decoder : embedding gather / deterministic scatter, row-wise softmax-CE, column sums, LSTM backward
 //             pointwise step, BatchNorm1d forward/backward
 //   trainer : fused elementwise clamp + Adam over one flat buffer (train.py:88-91,146)
-#include "sat_internal.h"
+#include "sat_bn_stats.h"
 #include <stdlib.h>
 
 namespace {
@@ -182,8 +182,7 @@ __global__ __launch_bounds__(1024) void bn_slab_to_acc_kernel(const float* __res
             S += ss[g][cl];
             Q += sq[g][cl];
         }
-        atomicAdd((unsigned long long*)(acc + c), (unsigned long long)__double2ll_rn(S * SAT_STAT_SCALE));
-        atomicAdd((unsigned long long*)(acc + C + c), (unsigned long long)__double2ll_rn(Q * SAT_STAT_SCALE));
+        stat_acc_add(acc, C, S, Q, c);
     }
 }
 
@@ -210,21 +209,6 @@ __global__ __launch_bounds__(256) void bn_running_apply_kernel(const sat_bn_runn
     }
 }
 
-// Where a BatchNorm's (scale, shift) comes from: either a table the finalize kernel wrote, or -- `acc` set -- the
-// fixed-point integer sums the producing conv accumulated (sat_conv_glds.hip): then every workgroup derives the
-// table itself into LDS (a few KB of loads, f64 arithmetic identical to bn_finalize_kernel), and workgroup 0 also
-// updates the running statistics and clears the OTHER step-parity's accumulators for the next step.
-struct BnSrc {
-    const float* scale;
-    const float* shift;
-    const long long* acc;     // [2][C] (this step's parity)
-    long long* acc_clear;     // [2][C] (other parity) or NULL
-    const float* gamma;
-    const float* beta;
-    float* running_mean;
-    float* running_var;
-};
-
 // grouped program (sat_op.groups): group g's statistics live g blocks further on -- accumulators [G][2 parities][2][C], the
 // deferred running-statistics log [G][2][C]
 __device__ __forceinline__ BnSrc bn_group(BnSrc b, long g, int C) {
@@ -234,29 +218,6 @@ __device__ __forceinline__ BnSrc bn_group(BnSrc b, long g, int C) {
         if (b.running_mean) { b.running_mean += g * 2 * C; b.running_var += g * 2 * C; }
     }
     return b;
-}
-
-__device__ __forceinline__ void bn_table_from_acc(const BnSrc& b, int C, double count, float momentum, float eps,
-                                                  float* sc, float* sh) {
-    const double inv = 1.0 / (SAT_STAT_SCALE * count);      // one f64 division per thread, none per channel
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        const long long s1 = b.acc[c], s2 = b.acc[C + c];
-        const double mean = (double)s1 * inv;
-        double var = (double)s2 * inv - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float invstd = 1.0f / sqrtf((float)var + eps);
-        const float s = b.gamma[c] * invstd;
-        sc[c] = s;
-        sh[c] = b.beta[c] - (float)mean * s;
-        if (blockIdx.x == 0) {
-            if (b.running_mean) {
-                const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-                b.running_mean[c] = (float)((1.0 - momentum) * b.running_mean[c] + momentum * (double)(float)mean);
-                b.running_var[c] = (float)((1.0 - momentum) * b.running_var[c] + momentum * (double)(float)unbiased);
-            }
-            if (b.acc_clear) { b.acc_clear[c] = 0; b.acc_clear[C + c] = 0; }
-        }
-    }
 }
 
 // out = relu(in0*s0 + t0)  /  out = relu(in0*s0 + t0 + (in1*s1 + t1 | in1)); NHWC, C % chunk == 0.
@@ -298,11 +259,11 @@ __global__ void bn_act_kernel(const T* in0, const T* __restrict__ in1, T* out,
     }
     bool derived = false;
     if (b0.acc) {
-        bn_table_from_acc(b0, C, count, momentum, eps, tab, tab + C);
+        bn_table<0>(b0, C, count, sat_stat_inv(count), momentum, eps, threadIdx.x, blockIdx.x == 0, tab, tab + C);
         s0 = tab; t0 = tab + C; derived = true;
     }
     if (ADD && has_b1 && b1.acc) {
-        bn_table_from_acc(b1, C, count, momentum, eps, tab + 2 * C, tab + 3 * C);
+        bn_table<0>(b1, C, count, sat_stat_inv(count), momentum, eps, threadIdx.x, blockIdx.x == 0, tab + 2 * C, tab + 3 * C);
         s1 = tab + 2 * C; t1 = tab + 3 * C; derived = true;
     }
     if (derived) __syncthreads();
@@ -392,7 +353,7 @@ __global__ void bn_relu_strided_kernel(const T* __restrict__ in, T* __restrict__
     const float* s = b.scale;
     const float* t = b.shift;
     if (b.acc) {
-        bn_table_from_acc(b, C, count, momentum, eps, tab, tab + C);
+        bn_table<0>(b, C, count, sat_stat_inv(count), momentum, eps, threadIdx.x, blockIdx.x == 0, tab, tab + C);
         __syncthreads();
         s = tab;
         t = tab + C;
@@ -423,7 +384,7 @@ __global__ void bn_relu_maxpool_kernel(const T* __restrict__ in, T* __restrict__
     const float* s = b.scale;
     const float* t = b.shift;
     if (b.acc) {                // statistics arrive as integer sums: derive (scale, shift) like bn_act_kernel does
-        bn_table_from_acc(b, C, count, momentum, eps, tab, tab + C);
+        bn_table<0>(b, C, count, sat_stat_inv(count), momentum, eps, threadIdx.x, blockIdx.x == 0, tab, tab + C);
         __syncthreads();
         s = tab;
         t = tab + C;
