@@ -562,6 +562,35 @@ int sat_ss_decoder_fwd(const float* features /*[B,E]*/, const float* embed /*[V,
                        const float* const* lstm_w /*[host]*/, int num_layers, int H, const float* lin_w, const float* lin_b,
                        float* const* tapes /*[host]*/, float* X, float* logits, int64_t ldl, float ss_prob, uint64_t seed, int rank,
                        int64_t* used, int64_t used_stride, float* workspace, int64_t ws_bytes, sat_stream_t stream);
+/* Scheduled sampling in the Show-Attend-Tell training forward (model2.py:38-85, the model train.py:37 builds; schedule
+ * train.py:109-113).  Same random numbers as above; rows b < batch_sizes[t+1] of step t+1 >= 1 are fed, in the embedding half of
+ * the LSTMCell input [emb | ctx], used[b][t+1] = mask(b, t+1) ? s(b, t+1) : captions[b][t+1], s drawn from the logits of step t
+ * (classifier(context2out(ctx_t) + hidden2tout(h_t))); used[b][0] = captions[b][0] (<start>) and the context half is always step
+ * t+1's own attention context.
+ * sat_ss_attend_fwd: the decoder loop as ONE call, no host synchronisation.  Given feats [B*P,C] (the encoder features, rows
+ *   (b, p)), ctx_enc = feats image_att_w, h0 / c0 [B,H] (init_lstm), captions [B][cap_stride >= T] (train.py's captions[:, :-1]),
+ *   batch_sizes [host] / prefix [device, T+1] of the packed order; H == E + C.  w: HOST array of SAT_SSA_NUM_WEIGHTS device
+ *   pointers (SAT_SSA_* order below); tapes: HOST array of SAT_SSA_NUM_TAPES device pointers that receive what the teacher-forced
+ *   forward leaves in them: PROJ [N,C] (weight_hh(h_{t-1})), ALPHA [N,P], X [N,H] (= [emb | ctx] of every packed row), GATES [N,4H]
+ *   (activated), CS [N,H], HS [N,H] (h_t), Zin [N,C+H] (= [ctx | h]), Z [N,E] (the output layer before the classifier).
+ *   toks [N] int64 out: the packed tokens fed; logits [N,ldl] out (exact f32, ldl % 4 == 0, pad columns untouched);
+ *   used [B][used_stride >= T] out.  Null or impossible arguments: SAT_ERR_ARG before anything is enqueued.
+ *   workspace: sat_ss_attend_fwd_ws_bytes(batch_sizes[0], P, C, E, H, V) = the sum, each rounded up to 256 bytes, of
+ *   sat_ss_decoder_fwd_ws_bytes(B, V) (draw partials), sat_attention_ws_bytes(B, P), max over M <= B of
+ *   sat_skinny_gemm_ws_bytes(M, C, H) and (M, E, C) (split-K slabs), B*H*4 (cell state) and E*4 (b_c2o + b_h2o); 0 for
+ *   non-positive sizes. */
+enum {
+    SAT_SSA_WEIGHT_HH_W, SAT_SSA_WEIGHT_HH_B, SAT_SSA_WEIGHT_ATT, SAT_SSA_EMBEDDING, SAT_SSA_CELL_W_IH, SAT_SSA_CELL_W_HH,
+    SAT_SSA_CELL_B_IH, SAT_SSA_CELL_B_HH, SAT_SSA_C2O_W, SAT_SSA_C2O_B, SAT_SSA_H2O_W, SAT_SSA_H2O_B, SAT_SSA_CLS_W, SAT_SSA_CLS_B,
+    SAT_SSA_NUM_WEIGHTS
+};
+enum { SAT_SSA_PROJ, SAT_SSA_ALPHA, SAT_SSA_X, SAT_SSA_GATES, SAT_SSA_CS, SAT_SSA_HS, SAT_SSA_ZIN, SAT_SSA_Z, SAT_SSA_NUM_TAPES };
+int64_t sat_ss_attend_fwd_ws_bytes(int B, int P, int C, int E, int H, int V);
+int sat_ss_attend_fwd(const float* feats, const float* ctx_enc, const float* h0, const float* c0, const int64_t* captions,
+                      int64_t cap_stride, const int32_t* batch_sizes /*[host] T*/, const int32_t* prefix /*[T+1] device*/, int T, int P,
+                      int C, int E, int H, int V, const float* const* w /*[host]*/, float* const* tapes /*[host]*/, int64_t* toks,
+                      float* logits, int64_t ldl, float ss_prob, uint64_t seed, int rank, int64_t* used, int64_t used_stride,
+                      float* workspace, int64_t ws_bytes, sat_stream_t stream);
 /* The truncation rule of the reference's id -> word loop (`evaluation`, eval.py:103-109: `if word == '<end>': break`):
  * kept[b] = number of ids of row b in front of the first end_id (T when the row has none).  ids: [B] rows of T int64 with
  * `stride` elements between rows (model.sample's [B,20], or one hypothesis plane of the beam ids). */

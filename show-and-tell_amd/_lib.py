@@ -161,6 +161,9 @@ SIGNATURES = {
                               _vp, _i64, _vp]),
     "sat_ss_decoder_fwd": (_i, [_vp, _vp, _vp, _i64, C.POINTER(C.c_int32), _vp, _i, _i, _i, C.POINTER(_vp), _i, _i, _vp, _vp,
                                 C.POINTER(_vp), _vp, _vp, _i64, _f, C.c_uint64, _i, _vp, _i64, _vp, _i64, _vp]),
+    "sat_ss_attend_fwd_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
+    "sat_ss_attend_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(C.c_int32), _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_vp),
+                               C.POINTER(_vp), _vp, _vp, _i64, _f, C.c_uint64, _i, _vp, _i64, _vp, _i64, _vp]),
     "sat_clamp_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp]),
     "sat_clamp_adam_step_guarded": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp, _vp]),
     "sat_step_fault_flag": (_i, [C.POINTER(_vp), _i, _vp, _vp, _vp]),

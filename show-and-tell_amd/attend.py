@@ -6,7 +6,9 @@
                path (implicit-GEMM conv with the bias + ReLU riding in the bf16 conv epilogue, SAT_OP_MAXPOOL2)
     decoder  : context_encode = features @ image_att_w (sat_gemm_f32); init_lstm; per packed step: weight_hh projection,
                sat_attention_fwd (tanh / softmax / weighted mean, model2.py:73-78), sat_lstmcell_fwd (model2.py:58);
-               output_layer batched over all packed rows after the loop (model2.py:80-85)
+               output_layer batched over all packed rows after the loop (model2.py:80-85); in training with ss_prob > 0
+               (scheduled sampling, train.py:109-113) the whole loop, output layer and Gumbel-max draws per step, is one
+               `sat_ss_attend_fwd` call
     backward : hand-written (sat_attention_bwd, LSTMCell BPTT, batched weight-gradient GEMMs) behind torch.autograd, so
                `loss.backward()` (train.py:144) works unchanged; `finetune(allow=True)` (model2.py:87-89) adds the conv-stack
                backward (f32 mode): dgrad = the forward conv kernel on flipped weights, wgrad = split-K GEMMs over the flat
@@ -327,7 +329,9 @@ class _AttendFn(torch.autograd.Function):
     """decoder half of model2.py:38-65 given the encoder features (the conv stack is frozen, model2.py:17)."""
 
     @staticmethod
-    def forward(ctx, model, features, fmean, captions, pi, *params):
+    def forward(ctx, model, features, fmean, captions, pi, ss, *params):
+        """ss: None (teacher forcing) or dict(prob, seed, rank) -- scheduled sampling through `sat_ss_attend_fwd`; receives
+        "used", the tokens fed [B, T]"""
         lib = L.load()
         m = model
         dev = features.device
@@ -342,10 +346,13 @@ class _AttendFn(torch.autograd.Function):
         h0, c0 = HSX[:B], torch.empty(B, H, device=dev)
         _gemm(lib, 0, 0, fmean, C, m.init_hidden.weight, C, h0, H, B, H, C, m.init_hidden.bias)  # model2.py:67-71
         _gemm(lib, 0, 0, fmean, C, m.init_memory.weight, C, c0, H, B, H, C, m.init_memory.bias)
-        c = c0.clone()
         HS, PROJ = HSX[B:], torch.empty(N, C, device=dev)
         X, GATES = torch.empty(N, Hin, device=dev), torch.empty(N, 4 * H, device=dev)
         CS, ALPHA = torch.empty(N, H, device=dev), torch.empty(N, P, device=dev)
+        if ss is not None:
+            return _ss_attend_forward(ctx, lib, m, f2, fmean, ctx_enc, h0, c0, HSX, captions, pi, ss,
+                                      dict(PROJ=PROJ, ALPHA=ALPHA, X=X, GATES=GATES, CS=CS, HS=HS))
+        c = c0.clone()
         watt = m.weight_att.view(-1)
         att_ws = torch.empty(B * P, device=dev)
         # the embedding half of every step's LSTMCell input [emb | ctx] (model2.py:55-57) in one gather
@@ -384,7 +391,43 @@ class _AttendFn(torch.autograd.Function):
         from .attend_bwd import attend_backward
         want = ctx.needs_input_grad[1]                     # features carry a graph only when the conv stack is fine-tuned
         grads, d_feats, d_fmean = attend_backward(ctx.m, ctx.pi, ctx.captions, ctx.tapes, dlogits, want_dfeat=want)
-        return (None, d_feats, d_fmean if ctx.needs_input_grad[2] else None, None, None) + tuple(grads)
+        return (None, d_feats, d_fmean if ctx.needs_input_grad[2] else None, None, None, None) + tuple(grads)
+
+
+_SS_WEIGHTS = ("weight_hh.weight", "weight_hh.bias", "weight_att", "embedding.weight", "lstmcell.weight_ih", "lstmcell.weight_hh",
+               "lstmcell.bias_ih", "lstmcell.bias_hh", "context2out.weight", "context2out.bias", "hidden2tout.weight",
+               "hidden2tout.bias", "classifier.weight", "classifier.bias")      # include/sat_hip.h SAT_SSA_* order
+_SS_TAPES = ("PROJ", "ALPHA", "X", "GATES", "CS", "HS", "Zin", "Z")                # SAT_SSA_PROJ .. SAT_SSA_Z
+
+
+def _ss_attend_forward(ctx, lib, m, f2, fmean, ctx_enc, h0, c0, HSX, captions, pi, ss, tp):
+    """the recurrence of _AttendFn.forward with scheduled sampling (model2.py:54-62 + 80-85 per step, the input of step t >= 1
+    drawn from the logits of step t-1 with probability ss["prob"]): one `sat_ss_attend_fwd` call leaves the same tapes, so
+    attend_backward runs unchanged on the tokens fed"""
+    dev, st = f2.device, L.stream()
+    B, P, C = pi.B, tp["ALPHA"].shape[1], f2.shape[1]
+    E, H, V, N, T = m.embed_size, m.hidden_size, m.vocab_size, pi.N, pi.T
+    tp["Zin"], tp["Z"] = torch.empty(N, C + H, device=dev), torch.empty(N, E, device=dev)
+    Wz = torch.empty(E, C + H, device=dev)                 # [W_c2o | W_h2o]: the backward's dZin = dZ Wz
+    L.check(lib.sat_rows_copy(L.ptr(m.context2out.weight), C, None, 0, E, E, C, L.ptr(Wz), C + H, st), "sat_rows_copy")
+    L.check(lib.sat_rows_copy(L.ptr(m.hidden2tout.weight), H, None, 0, E, E, H, Wz.data_ptr() + C * 4, C + H, st), "sat_rows_copy")
+    named = dict(m.named_parameters())
+    w = (L.C.c_void_p * len(_SS_WEIGHTS))(*[named[k].data_ptr() for k in _SS_WEIGHTS])
+    tapes = (L.C.c_void_p * len(_SS_TAPES))(*[tp[k].data_ptr() for k in _SS_TAPES])
+    toks = torch.empty(N, dtype=torch.int64, device=dev)
+    used = torch.empty(B, T, dtype=torch.int64, device=dev)
+    logits = L.logits_buffer(N, V, dev)
+    ldl = logits.shape[1]
+    wsb = lib.sat_ss_attend_fwd_ws_bytes(B, P, C, E, H, V)
+    ws = torch.empty(wsb // 4, device=dev)
+    L.check(lib.sat_ss_attend_fwd(f2.data_ptr(), ctx_enc.data_ptr(), h0.data_ptr(), c0.data_ptr(), captions.data_ptr(),
+                                  captions.stride(0), pi.bs_c, pi.prefix_dev.data_ptr(), T, P, C, E, H, V, w, tapes, toks.data_ptr(),
+                                  logits.data_ptr(), ldl, float(ss["prob"]), int(ss["seed"]), int(ss["rank"]), used.data_ptr(),
+                                  used.stride(0), ws.data_ptr(), wsb, st), "sat_ss_attend_fwd")
+    ss["used"] = used
+    ctx.m, ctx.pi, ctx.captions = m, pi, captions
+    ctx.tapes = dict(f2=f2, fmean=fmean, ctx_enc=ctx_enc, h0=h0, c0=c0, Wz=Wz, toks=toks, HSX=HSX, **tp)
+    return logits if ldl == V else logits[:, :V]
 
 
 class _VggFn(torch.autograd.Function):
@@ -442,6 +485,9 @@ class ShowAttendTellModel(nn.Module):
         self.classifier = _Lin(embed_size, vocab_size)
         self.hidden_size, self.embed_size, self.vocab_size, self.feat = hidden_size, embed_size, vocab_size, feat
         self.compute_dtype = compute_dtype
+        self.ss_prob = 0                  # scheduled sampling (train.py:109-113; schedule: trainer.ss_prob_for_epoch), training mode only
+        self.ss_rank = 0                  # data-parallel rank: a stream of draws of its own per rank
+        self.last_ss_inputs = self.last_ss_seed = None   # tokens fed [B, T] and seed of the last sampled forward
         self._programs, self._guard = {}, None
         self._pf_list = []          # features in flight: [(images, feats, fmean, event, weights signature, instance)]
         self.register_load_state_dict_post_hook(lambda mod, k: mod._programs.clear())
@@ -550,6 +596,9 @@ class ShowAttendTellModel(nn.Module):
         return self.decode(feats, fmean, captions, lengths)
 
     def decode(self, features, fmean, captions, lengths):
+        """The decoder half of `forward`.  In training mode with ss_prob > 0 the embedding half of the input of step t >= 1 is,
+        with probability ss_prob, a token drawn from softmax(logits of step t-1) (scheduled sampling; seed drawn from torch's CPU
+        generator); the tokens fed and the seed are kept as `last_ss_inputs` / `last_ss_seed`."""
         L.require_gpu(captions, "captions")
         if len(lengths) != features.shape[0]:
             raise ValueError("len(lengths) != batch size")
@@ -561,7 +610,14 @@ class ShowAttendTellModel(nn.Module):
         if self._guard is None or self._guard.status.device != features.device:
             self._guard = IdGuard(features.device)
         self._guard.submit(captions, pi.T, self.vocab_size, "captions")
-        return _AttendFn.apply(self, features, fmean, captions, pi, *self._params())
+        ss = None
+        if self.training and self.ss_prob > 0:
+            from .models import draw_ss_seed
+            ss = dict(prob=float(self.ss_prob), seed=draw_ss_seed(), rank=int(self.ss_rank))
+        out = _AttendFn.apply(self, features, fmean, captions, pi, ss, *self._params())
+        if ss is not None:
+            self.last_ss_inputs, self.last_ss_seed = ss["used"], ss["seed"]
+        return out
 
     @torch.no_grad()
     def sample(self, images, states=None):

@@ -17,12 +17,13 @@ int sat_skinny_sample(const float* h, const float* w, const float* b, int M, int
 namespace {
 
 // one workgroup per row b: mask(b, t) = u < ss_prob; if set, the arg-max of the Gumbel-max partials is the token fed to step t
-// (its embedding row goes to x[b]), else the teacher's token (x[b] already holds its row).  teacher == NULL: every row samples.
+// (its embedding row goes to x + b*x_stride), else the teacher's token (x's row already holds it).  teacher == NULL: every row
+// samples.
 __global__ __launch_bounds__(256) void ss_select_kernel(const float* __restrict__ pmax, const int* __restrict__ pidx, int ncg,
                                                         unsigned t, unsigned ctr3, unsigned key0, unsigned key1, float ss_prob,
                                                         const int64_t* __restrict__ teacher, long teacher_stride, int64_t* ids,
                                                         long ids_stride, const float* __restrict__ embed, int E, int V,
-                                                        float* __restrict__ x) {
+                                                        float* __restrict__ x, long x_stride) {
     __shared__ float sb[256];
     __shared__ int si[256];
     const int row = blockIdx.x, tid = threadIdx.x;
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void ss_select_kernel(const float* __restrict_
     if (tid == 0) ids[(long)row * ids_stride] = tok;
     if (embed && x) {
         const float* src = embed + (long)tok * E;
-        float* dst = x + (long)row * E;
+        float* dst = x + (long)row * x_stride;
         for (int e = tid; e < E; e += 256) dst[e] = src[e];
     }
 }
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(256) void ss_init_used_kernel(const int64_t* __rest
 // one sampling step: projection of M rows (+ optional logits store) and the draw for the first m_sel <= M of them
 int sample_step(const float* h, const float* lin_w, const float* lin_b, int M, int m_sel, int H, int V, float* logits, long ldl,
                 float ss_prob, uint64_t seed, int t, int rank, const int64_t* teacher, long teacher_stride, int64_t* ids,
-                long ids_stride, const float* embed, int E, float* x, float* workspace, hipStream_t s) {
+                long ids_stride, const float* embed, int E, float* x, long x_stride, float* workspace, hipStream_t s) {
     const int ncg = sat_cdiv(V, 16);
     float* pmax = workspace;
     int* pidx = (int*)(workspace + (long)M * ncg);
@@ -81,7 +82,7 @@ int sample_step(const float* h, const float* lin_w, const float* lin_b, int M, i
     SAT_TRY(sat_skinny_sample(h, lin_w, lin_b, M, H, V, logits, ldl, k0, k1, (unsigned)t, 2u * (unsigned)rank, pmax, pidx, s));
     if (m_sel < 1) return SAT_OK;
     hipLaunchKernelGGL(ss_select_kernel, dim3(m_sel), dim3(256), 0, s, pmax, pidx, ncg, (unsigned)t, 2u * (unsigned)rank + 1u, k0,
-                       k1, ss_prob, teacher, teacher_stride, ids, ids_stride, embed, E, V, x);
+                       k1, ss_prob, teacher, teacher_stride, ids, ids_stride, embed, E, V, x, x_stride);
     SAT_LAUNCH_CHECK();
     return SAT_OK;
 }
@@ -98,7 +99,7 @@ extern "C" int sat_vocab_sample(const float* h, const float* lin_w, const float*
     if ((logits && ldl < V) || (x && (!embed || E < 1))) return SAT_ERR_ARG;
     if (ws_bytes < sat_ss_decoder_fwd_ws_bytes(B, V)) return SAT_ERR_WORKSPACE;
     return sample_step(h, lin_w, lin_b, B, B, H, V, logits, ldl, ss_prob, seed, t, rank, teacher, teacher_stride, ids, ids_stride,
-                       embed, E, x, workspace, (hipStream_t)stream);
+                       embed, E, x, E, workspace, (hipStream_t)stream);
 }
 
 extern "C" int sat_ss_decoder_fwd(const float* features, const float* embed, const int64_t* captions, int64_t cap_stride,
@@ -153,7 +154,7 @@ extern "C" int sat_ss_decoder_fwd(const float* features, const float* embed, con
         if (t >= 1 && t + 1 < T) {
             // the input of step t+1 >= 2: a draw from this step's logits where mask(b, t+1) holds, the teacher's token elsewhere
             SAT_TRY(sample_step(inp, lin_w, lin_b, n, n_next, H, V, lg, ldl, ss_prob, seed, t + 1, rank, captions + t, cap_stride,
-                                used + t, used_stride, embed, E, X + (off + n) * E, workspace, s));
+                                used + t, used_stride, embed, E, X + (off + n) * E, E, workspace, s));
         } else if (lg) {
             // step 0 (its successor's input, <start>, is never replaced) and the last step: logits only
             SAT_TRY(sat_skinny_store(inp, H, lin_w, H, 0, n, V, H, 1, lg, ldl, 0, lin_b, s));
@@ -161,4 +162,130 @@ extern "C" int sat_ss_decoder_fwd(const float* features, const float* embed, con
         off += n;
     }
     return SAT_OK;
+}
+
+// ---- Show-Attend-Tell (model2.py:38-85, the model train.py:37 builds) with scheduled sampling ------------------------------------
+// The input of step t >= 1 is [emb | ctx_t]: with probability ss_prob the embedding half holds a token drawn from softmax(logits of
+// step t-1), logits = classifier(context2out(ctx_{t-1}) + hidden2tout(h_{t-1})); the context half is always step t's own context.
+// No one-column lag here (the image is not a step of its own): the draw for step t+1 uses counter t+1 and the logits of step t, so
+// the output layer runs per step instead of once over all packed rows.  Per step: weight_hh projection (split-K skinny GEMM),
+// attention (rows-dot + context, the context straight into X's context half), LSTMCell (tapes GATES / CS / HS), the output layer
+// Z = [ctx | h] [W_c2o | W_h2o]^T + (b_c2o + b_h2o) as one two-product skinny GEMM, then the vocab projection with the Gumbel-max
+// epilogue and the select (t + 1 < T), or the projection alone (last step).
+
+namespace {
+
+constexpr long kWsAlign = 256;
+
+long ws_round(long n) { return (n + kWsAlign - 1) / kWsAlign * kWsAlign; }
+
+// byte offsets of the pieces of sat_ss_attend_fwd's workspace; the last entry is the total
+struct SsAttendWs {
+    long sample, att, skinny, cell, zbias, total;
+};
+
+SsAttendWs ss_attend_ws(int B, int P, int C, int E, int H, int V) {
+    long sk = 0;                                          // split-K slabs of the two per-step GEMMs, for every row count <= B
+    for (int m = 1; m <= B; ++m) {
+        const long a = sat_skinny_gemm_ws_bytes(m, C, H), b = sat_skinny_gemm_ws_bytes(m, E, C);
+        sk = a > sk ? a : sk;
+        sk = b > sk ? b : sk;
+    }
+    SsAttendWs w;
+    w.sample = 0;
+    w.att = w.sample + ws_round(sat_ss_decoder_fwd_ws_bytes(B, V));
+    w.skinny = w.att + ws_round(sat_attention_ws_bytes(B, P));
+    w.cell = w.skinny + ws_round(sk);
+    w.zbias = w.cell + ws_round((long)B * H * sizeof(float));
+    w.total = w.zbias + ws_round((long)E * sizeof(float));
+    return w;
+}
+
+}  // namespace
+
+extern "C" int64_t sat_ss_attend_fwd_ws_bytes(int B, int P, int C, int E, int H, int V) {
+    if (B < 1 || P < 1 || C < 1 || E < 1 || H < 1 || V < 1) return 0;
+    return ss_attend_ws(B, P, C, E, H, V).total;
+}
+
+extern "C" int sat_ss_attend_fwd(const float* feats, const float* ctx_enc, const float* h0, const float* c0, const int64_t* captions,
+                                 int64_t cap_stride, const int32_t* batch_sizes, const int32_t* prefix, int T, int P, int C, int E,
+                                 int H, int V, const float* const* w, float* const* tapes, int64_t* toks, float* logits, int64_t ldl,
+                                 float ss_prob, uint64_t seed, int rank, int64_t* used, int64_t used_stride, float* workspace,
+                                 int64_t ws_bytes, sat_stream_t stream) {
+    if (!feats || !ctx_enc || !h0 || !c0 || !captions || !batch_sizes || !prefix || !w || !tapes || !toks || !logits || !used ||
+        !workspace)
+        return SAT_ERR_ARG;
+    if (T < 1 || P < 1 || C < 4 || (C & 3) || E < 4 || (E & 3) || H != E + C || V < 1 || rank < 0) return SAT_ERR_ARG;
+    if (cap_stride < T || used_stride < T || ldl < V || (ldl & 3)) return SAT_ERR_ARG;
+    for (int k = 0; k < SAT_SSA_NUM_WEIGHTS; ++k)
+        if (!w[k]) return SAT_ERR_ARG;
+    for (int k = 0; k < SAT_SSA_NUM_TAPES; ++k)
+        if (!tapes[k]) return SAT_ERR_ARG;
+    const int B = batch_sizes[0];
+    long N = 0;
+    for (int t = 0; t < T; ++t) {
+        if (batch_sizes[t] < 1 || (t > 0 && batch_sizes[t] > batch_sizes[t - 1])) return SAT_ERR_ARG;
+        N += batch_sizes[t];
+    }
+    // what sat_attention_fwd would refuse only after earlier steps had been enqueued
+    if ((long)2 * C * 4 > 60 * 1024 || (long)(((P + 3) & ~3) + 8 + 8 * 64) * 4 > 60 * 1024) return SAT_ERR_UNSUPPORTED;
+    const SsAttendWs lay = ss_attend_ws(B, P, C, E, H, V);
+    if (ws_bytes < lay.total) return SAT_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)workspace;
+    float* sample_ws = (float*)(base + lay.sample);
+    float* att_ws = (float*)(base + lay.att);
+    float* sk_ws = (float*)(base + lay.skinny);
+    float* cell = (float*)(base + lay.cell);
+    float* zbias = (float*)(base + lay.zbias);
+    const long att_bytes = lay.skinny - lay.att, sk_bytes = lay.cell - lay.skinny;
+    const float *w_whh = w[SAT_SSA_WEIGHT_HH_W], *b_whh = w[SAT_SSA_WEIGHT_HH_B], *w_att = w[SAT_SSA_WEIGHT_ATT];
+    const float* embed = w[SAT_SSA_EMBEDDING];
+    const float *w_ih = w[SAT_SSA_CELL_W_IH], *w_hh = w[SAT_SSA_CELL_W_HH], *b_ih = w[SAT_SSA_CELL_B_IH], *b_hh = w[SAT_SSA_CELL_B_HH];
+    const float *w_c2o = w[SAT_SSA_C2O_W], *w_h2o = w[SAT_SSA_H2O_W], *w_cls = w[SAT_SSA_CLS_W], *b_cls = w[SAT_SSA_CLS_B];
+    float *PROJ = tapes[SAT_SSA_PROJ], *ALPHA = tapes[SAT_SSA_ALPHA], *X = tapes[SAT_SSA_X], *GATES = tapes[SAT_SSA_GATES];
+    float *CS = tapes[SAT_SSA_CS], *HS = tapes[SAT_SSA_HS], *Zin = tapes[SAT_SSA_ZIN], *Z = tapes[SAT_SSA_Z];
+    const int Hin = H;
+
+    SAT_TRY(sat_rows_add(w[SAT_SSA_C2O_B], E, w[SAT_SSA_H2O_B], E, 1, E, zbias, E, stream));
+    // used = the teacher's tokens; X's embedding half = their rows (draws overwrite both, step by step)
+    hipLaunchKernelGGL(ss_init_used_kernel, dim3(sat_cdiv((long)B * T, 256)), dim3(256), 0, s, captions, (long)cap_stride, B, T, used,
+                       (long)used_stride);
+    SAT_LAUNCH_CHECK();
+    SAT_TRY(sat_pack_tokens(used, used_stride, prefix, T, (int)N, 0, toks, stream));
+    SAT_TRY(sat_rows_copy(embed, E, toks, 1, V, (int)N, E, X, Hin, stream));
+    hipError_t e = hipMemcpyAsync(cell, c0, (size_t)B * H * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return (int)e;
+    long off = 0, prev = 0;
+    for (int t = 0; t < T; ++t) {
+        const int n = batch_sizes[t];
+        const int n_next = (t + 1 < T) ? batch_sizes[t + 1] : 0;
+        const float* hprev = t == 0 ? h0 : HS + prev * H;
+        float* x = X + off * Hin;
+        // model2.py:74 weight_hh(hidden), then the attention with its context into X's context half (model2.py:55-57, 73-78)
+        SAT_TRY(sat_skinny_gemm2_f32(hprev, H, w_whh, H, H, nullptr, 0, nullptr, 0, 0, 0, n, C, b_whh, PROJ + off * C, C, sk_ws,
+                                     sk_bytes, stream));
+        SAT_TRY(sat_attention_fwd(ctx_enc, feats, PROJ + off * C, C, w_att, n, P, C, ALPHA + off * P, x + E, Hin, att_ws, att_bytes,
+                                  stream));
+        SAT_TRY(sat_lstmcell_fwd(x, hprev, cell, w_ih, w_hh, b_ih, b_hh, n, Hin, H, HS + off * H, GATES + off * 4L * H, CS + off * H,
+                                 stream));
+        // output_layer (model2.py:80-84) of this step's rows: Z = ctx W_c2o^T + h W_h2o^T + (b_c2o + b_h2o)
+        SAT_TRY(sat_skinny_gemm2_f32(x + E, Hin, w_c2o, C, C, HS + off * H, H, w_h2o, H, H, 0, n, E, zbias, Z + off * E, E, sk_ws,
+                                     sk_bytes, stream));
+        float* lg = logits + off * ldl;
+        if (n_next) {
+            // the input of step t+1: a draw from this step's logits where mask(b, t+1) holds, the teacher's token elsewhere
+            SAT_TRY(sample_step(Z + off * E, w_cls, b_cls, n, n_next, E, V, lg, ldl, ss_prob, seed, t + 1, rank, captions + t + 1,
+                                cap_stride, used + t + 1, used_stride, embed, E, X + (off + n) * Hin, Hin, sample_ws, s));
+        } else {
+            SAT_TRY(sat_skinny_store(Z + off * E, E, w_cls, E, 0, n, V, E, 1, lg, ldl, 0, b_cls, s));
+        }
+        prev = off;
+        off += n;
+    }
+    // the output layer's input tape [ctx | h] of every row (attend_backward's dWz) and the tokens actually fed (its embedding scatter)
+    SAT_TRY(sat_rows_copy(X + E, Hin, nullptr, 0, N, (int)N, C, Zin, C + H, stream));
+    SAT_TRY(sat_rows_copy(HS, H, nullptr, 0, N, (int)N, H, Zin + C, C + H, stream));
+    return sat_pack_tokens(used, used_stride, prefix, T, (int)N, 0, toks, stream);
 }

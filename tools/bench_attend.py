@@ -2,9 +2,14 @@
 """Throughput of the Show-Attend-Tell path (model2.py, the model train.py:37 constructs) on one MI355X: training step
 (VGG16 features[:-3] frozen + attention decoder fwd + CE + hand-written backward + clamp + torch Adam, train.py:134-146) and
 greedy sampling (eval.py:99), batch 64, 224x224, hidden 1024 / embed 512 (config.py:27-28 defaults), vocab 10000, len-20 captions.
-    python tools/bench_attend.py [bf16|f32]"""
+    python tools/bench_attend.py [bf16|f32] [--ss-prob P] [--ab REGIONS] [--forwards N]
+--ss-prob: scheduled sampling (model.ss_prob) in the training step.  --ab REGIONS: only the training step, ss_prob 0 and P
+interleaved (order alternating per region, 10 steps each), per-region times and medians.  --forwards N: only N sampled decoder
+forwards on fixed features (for a kernel trace)."""
+import argparse
 import importlib
 import os
+import statistics
 import sys
 import time
 
@@ -12,7 +17,13 @@ import torch
 
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 sat = importlib.import_module("show-and-tell_amd")
-dtype = sys.argv[1] if len(sys.argv) > 1 else "bf16"
+ap = argparse.ArgumentParser()
+ap.add_argument("dtype", nargs="?", default="bf16", choices=["bf16", "f32"])
+ap.add_argument("--ss-prob", type=float, default=0.0)
+ap.add_argument("--ab", type=int, default=0)
+ap.add_argument("--forwards", type=int, default=0)
+args = ap.parse_args()
+dtype = args.dtype
 B, T, V = 64, 20, 10000
 torch.manual_seed(123)
 model = sat.ShowAttendTellModel(1024, 512, V, 512, None, compute_dtype=dtype).cuda()
@@ -54,17 +65,49 @@ def step(i=0, last=True):
     return loss
 
 
+def region(n=10):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(n):
+        loss = step(i, i == n - 1)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / n, loss
+
+
+if args.forwards:
+    model.ss_prob = args.ss_prob
+    feats, fmean = model._encode(images)
+    with torch.no_grad():
+        for _ in range(args.forwards):
+            model.decode(feats, fmean, caps[:, :-1], l1)
+    torch.cuda.synchronize()
+    print("%d decoder forwards, ss_prob %g" % (args.forwards, args.ss_prob))
+    sys.exit(0)
+if args.ab:
+    probs = (0.0, args.ss_prob)
+    for p in probs:
+        model.ss_prob = p
+        for i in range(3):
+            step(i, i == 2)
+    times = {p: [] for p in probs}
+    for r in range(args.ab):
+        for p in (probs if r % 2 == 0 else probs[::-1]):
+            model.ss_prob = p
+            times[p].append(region()[0] * 1e3)
+    for p in probs:
+        print("ss_prob %-5g ms/step per region: %s" % (p, " ".join("%.3f" % t for t in times[p])))
+    m0, m1 = statistics.median(times[probs[0]]), statistics.median(times[probs[1]])
+    print("Show-Attend-Tell train step (%s conv stack, %s), median of %d regions x 10 steps: ss_prob 0 %.3f ms, ss_prob %g %.3f ms, "
+          "delta %+.3f ms (%+.1f %%)" % (dtype, "FusedClampAdam" if FUSED_OPT else "torch clamp + Adam", args.ab, m0, args.ss_prob, m1,
+                                         m1 - m0, 100 * (m1 - m0) / m0))
+    sys.exit(0)
+model.ss_prob = args.ss_prob
 for i in range(3):
     loss = step(i, i == 2)
-torch.cuda.synchronize()
-t0 = time.perf_counter()
-n = 10
-for i in range(n):
-    loss = step(i, i == n - 1)
-torch.cuda.synchronize()
-dt = (time.perf_counter() - t0) / n
-print("Show-Attend-Tell train step (%s conv stack, drop-in autograd path + torch CE, %s): %.2f ms/step = %.0f img/s, loss %.4f"
-      % (dtype, "FusedClampAdam" if FUSED_OPT else "torch clamp + Adam", dt * 1e3, B / dt, loss.item()))
+dt, loss = region()
+print("Show-Attend-Tell train step (%s conv stack, drop-in autograd path + torch CE, %s, ss_prob %g): %.2f ms/step = %.0f img/s, "
+      "loss %.4f" % (dtype, "FusedClampAdam" if FUSED_OPT else "torch clamp + Adam", args.ss_prob, dt * 1e3, B / dt, loss.item()))
+model.ss_prob = 0
 with torch.no_grad():
     feats, fmean = model._encode(images)
     torch.cuda.synchronize()
