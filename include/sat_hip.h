@@ -246,6 +246,11 @@ int sat_conv_variant_family(int variant);
  * only: every process, rank and box gets the same answer (config.py:15 `random_seed`: same seed, same bits). */
 int sat_conv_num_variants(void);
 int sat_conv_default_variant(const sat_op* op /*[host]*/, int want_sig);
+/* The variant (1-based) sat_run_ops would launch for this bf16 SAT_OP_CONV: op->variant when the op can run it, else the built-in
+ * choice (a variant the op cannot run is replaced silently at launch: a caller that depends on WHICH kernel runs -- a test of one
+ * kernel, a table of tuned choices -- asks here).  0 when the op is rejected, is not a bf16 conv, or has a Cout that is not a
+ * multiple of 8 (the register-staged kernel: no variants).  Host only: reads no device memory, launches nothing. */
+int sat_conv_resolved_variant(const sat_op* op /*[host]*/);
 /* bf16 weights [Cout][taps][Cin] (the kernels' layout; Cout % 32 == 0, Cin % 64 == 0) -> `packed` (same element count) in the
  * MFMA fragment order conv_pw_kernel streams into registers: [Cout/32][Cin/64][taps][4][64 lanes][8].  Once per weight version
  * of a frozen stack (`self.resnet(images)`, models.py:14-15,27). */

@@ -84,6 +84,7 @@ SIGNATURES = {
     "sat_gram_slab_floats": (_i64, [_i64, _i]),
     "sat_conv_num_variants": (_i, []),
     "sat_conv_default_variant": (_i, [C.POINTER(SatOp), _i]),
+    "sat_conv_resolved_variant": (_i, [C.POINTER(SatOp)]),
     "sat_conv_pack_weights": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sat_conv_autotune": (_i, [C.POINTER(SatOp), _i, _i, _vp, _i64, _vp]),
     "sat_conv_autotune_topk": (_i, [C.POINTER(SatOp), _i, _i, _vp, _i64, _vp, _i, C.POINTER(C.c_int32)]),
@@ -172,6 +173,12 @@ SIGNATURES = {
     "sat_cast_bf16_f32": (_i, [_vp, _vp, _i64, _vp]),
 }
 
+# Symbols added since ABI_VERSION was last raised (additions do not raise it).  Another build of the same ABI version -- SAT_LIB,
+# or a -DSAT_TESTHOOKS build made before the addition -- need not export them: they are bound where present, and a call through a
+# library that lacks one raises AttributeError (nothing is computed another way).  The library built from this tree exports
+# every one (tests/test_cabi_and_host.py, tests/test_conv_cases_host.py).
+ADDED_WITHIN_ABI = ("sat_conv_resolved_variant",)
+
 _lib = None
 
 
@@ -183,6 +190,8 @@ def open_library(path):
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback." % path)
     lib = C.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
+        if name in ADDED_WITHIN_ABI and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)       # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

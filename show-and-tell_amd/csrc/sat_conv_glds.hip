@@ -841,15 +841,28 @@ int prepare_args(const sat_op* op, int parity, ConvArgs& a) {
     return SAT_OK;
 }
 
+// the variant (0-based) a prepared op launches: the one it names when the op can run it, else the built-in choice
+int resolve_variant(const sat_op* op, const ConvArgs& a) {
+    int v = (op->variant > 0 && op->variant <= kNumVariants) ? op->variant - 1 : heuristic_variant(a);
+    if (!variant_ok(v, a)) v = heuristic_variant(a);      // e.g. the in-LDS transforms live in the plain unified-wave loop
+    return v;
+}
+
 }  // namespace
 
 // bf16 SAT_OP_CONV; arguments already validated by sat_conv_launch
 int sat_conv_glds_launch(const sat_op* op, int parity, hipStream_t s) {
     ConvArgs a;
     SAT_TRY(prepare_args(op, parity, a));
-    int v = (op->variant > 0 && op->variant <= kNumVariants) ? op->variant - 1 : heuristic_variant(a);
-    if (!variant_ok(v, a)) v = heuristic_variant(a);      // e.g. the in-LDS transforms live in the plain unified-wave loop
-    return launch_variant(v, a, op_groups(op), s);
+    return launch_variant(resolve_variant(op, a), a, op_groups(op), s);
+}
+
+// the variant (1-based) that launch picks, asked on the host: no device memory is read, nothing is launched.  0: sat_run_ops rejects the op
+extern "C" int sat_conv_resolved_variant(const sat_op* op) {
+    if (!op || op->kind != SAT_OP_CONV || op->dtype != SAT_BF16) return 0;
+    ConvArgs a;
+    if (sat_conv_check_args(op) != SAT_OK || prepare_args(op, 0, a) != SAT_OK) return 0;
+    return resolve_variant(op, a) + 1;
 }
 
 #include <algorithm>

@@ -402,8 +402,8 @@ int sat_conv_glds_launch(const sat_op* op, int parity, hipStream_t s);   // sat_
 
 static bool conv_legacy() { return false; }
 
-// SAT_OP_CONV
-int sat_conv_launch(const sat_op* op, int parity, hipStream_t s) {
+// the argument checks of every SAT_OP_CONV, host only (sat_conv_resolved_variant asks them too)
+int sat_conv_check_args(const sat_op* op) {
     if (!op->in0 || !op->w || !op->out) return SAT_ERR_ARG;
     const int esz = op->dtype == SAT_BF16 ? 2 : 4;
     const int ch = 16 / esz;
@@ -412,6 +412,14 @@ int sat_conv_launch(const sat_op* op, int parity, hipStream_t s) {
     // every 16-byte chunk address n*sN + hi*sH + wi*sW + c must be 16-byte aligned
     if ((op->sN % ch) || (op->sH % ch)) return SAT_ERR_ARG;
     if ((op->KW > 1 || op->pad || (op->flags & SAT_CONV_PADW)) ? (op->sW % ch) != 0 : ((long)op->stride * op->sW) % ch != 0) return SAT_ERR_ARG;
+    if (op->ldc && op->ldc < op->Cout) return SAT_ERR_ARG;
+    if (op->stat_partial && op->tiles_m != sat_cdiv((long)op->N * op->Hout * op->Wout, 128)) return SAT_ERR_ARG;
+    return SAT_OK;
+}
+
+// SAT_OP_CONV
+int sat_conv_launch(const sat_op* op, int parity, hipStream_t s) {
+    SAT_TRY(sat_conv_check_args(op));
     GemmArgs a = {};
     a.A = op->in0; a.B = op->w; a.C = op->out; a.bias = nullptr; a.bias2 = nullptr;
     a.stat_partial = op->stat_partial;
@@ -420,9 +428,8 @@ int sat_conv_launch(const sat_op* op, int parity, hipStream_t s) {
     a.Hin = op->Hin; a.Win = op->Win; a.Cin = op->Cin; a.Hout = op->Hout; a.Wout = op->Wout;
     a.KH = op->KH; a.KW = op->KW; a.stride = op->stride; a.pad = op->pad;
     a.padw = (op->flags & SAT_CONV_PADW) ? op->pad_w : op->pad;
-    if (op->ldc) { if (op->ldc < op->Cout) return SAT_ERR_ARG; a.ldc = op->ldc; }
+    if (op->ldc) a.ldc = op->ldc;
     a.sN = op->sN; a.sH = op->sH; a.sW = op->sW;
-    if (op->stat_partial && op->tiles_m != sat_cdiv(a.M, 128)) return SAT_ERR_ARG;
     if (op->dtype == SAT_BF16 && (op->Cout % 8) == 0 && !conv_legacy()) return sat_conv_glds_launch(op, parity, s);
     if (op->scale1 || op->shift1 || op->in1) return SAT_ERR_UNSUPPORTED;   // fused inference epilogue: bf16 LDS-DMA kernel only
     // register-staged kernel (f32 parity mode, odd shapes).  BM is always 128 (it fixes the partial-slab geometry); BN 64 for narrow layers or to fill the chip

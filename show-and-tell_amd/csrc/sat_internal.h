@@ -4,6 +4,7 @@
 #include "../../include/sat_hip.h"
 
 int sat_conv_launch(const sat_op* op, int parity, hipStream_t s);
+int sat_conv_check_args(const sat_op* op);      // the host-only argument checks sat_conv_launch starts with
 int sat_image_prep_launch(const sat_op* op, hipStream_t s);
 int sat_bn_finalize_launch(const sat_op* op, int parity, hipStream_t s);
 int sat_bn_eval_batch_launch(const sat_op* op, hipStream_t s);

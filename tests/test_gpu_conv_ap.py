@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_cases import run_named
 from test_gpu_kernels import _conv_op, _pack_weights, cu, st, sync
 
 pytestmark = pytest.mark.gpu
@@ -63,7 +64,7 @@ def test_conv_ap_is_bit_identical_to_the_ring_kernel(lib, N, H, W, Cout, affine,
             sd, td = cu(scale), cu(shift)
             o.scale0, o.shift0 = sd.data_ptr(), td.data_ptr()
             extra.update(sd=sd, td=td)
-        L.check(lib.sat_run_ops_parity(C.pointer(o), 1, 0, st()))
+        run_named(lib, o)
         sync()
         return keep, extra
 
@@ -108,12 +109,12 @@ def test_conv_ap_grouped_launch_equals_one_launch_per_batch(lib):
     xg = cu(torch.stack(xs).contiguous())
     outg = torch.full((G, M, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
     accg = torch.zeros(G, 2, 2, Cout, dtype=torch.int64, device="cuda")
-    L.check(lib.sat_run_ops_parity(C.pointer(op(xg, outg, accg, G)), 1, 0, st()))
+    run_named(lib, op(xg, outg, accg, G))
     sync()
     for k in range(G):
         out1 = torch.full((M, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
         acc1 = torch.zeros(2, 2, Cout, dtype=torch.int64, device="cuda")
         x1 = xg[k].contiguous()
-        L.check(lib.sat_run_ops_parity(C.pointer(op(x1, out1, acc1, 1)), 1, 0, st()))
+        run_named(lib, op(x1, out1, acc1, 1))
         sync()
         assert torch.equal(out1, outg[k]) and torch.equal(acc1, accg[k]), k

@@ -11,6 +11,7 @@ import importlib
 import pytest
 import torch
 
+from conv_cases import resolved, run_named
 from test_gpu_kernels import _pack_weights, cu, st, sync
 
 pytestmark = pytest.mark.gpu
@@ -96,7 +97,7 @@ def _one_launch(lib, k, variant, table=None, inplace=False):
     o = _conv(k, s["c3"], s["c1"], s["oacc"], variant)
     _bn_source(o, k, s, False, table)
     o.in1, o.out1, o.flags = s["res"].data_ptr(), (s["c3"] if inplace else s["y"]).data_ptr(), L.CONV_IN_RESIDUAL
-    L.check(lib.sat_run_ops_parity(C.pointer(o), 1, 0, st()), "conv_ay")
+    run_named(lib, o)
     sync()
     if inplace:
         s["y"] = s["c3"]
@@ -147,6 +148,7 @@ def test_conv_ay_with_a_precomputed_table_in_place_and_grouped(lib):
     _bn_source(o, k, s, False)
     o.in1, o.out1, o.flags = s["res"].data_ptr(), s["c3"].data_ptr(), L.CONV_IN_RESIDUAL
     ops = (L.SatOp * 1)(o)
+    assert resolved(lib, ops[0]) == AY8
     assert lib.sat_run_ops_parity(ops, 1, 0, st()) == 0 and ops[0].variant == AY4      # (runs: the launch falls back on a variant that may alias)
     sync()
     assert torch.equal(s["c3"], want["y"]) and torch.equal(s["c1"], want["c1"])

@@ -1,6 +1,6 @@
 """GPU: conv_rs_kernel (variant 38, csrc/sat_conv_rs.inc) -- the 3 x 3 / stride 1 convs over 32 channels of the Inception-v3 stem
 (Conv2d_2a_3x3: 32 -> 32 without padding, Conv2d_2b_3x3: 32 -> 64 with padding 1; BASELINE configs[3]) with the weights in registers and
-whole input rows in LDS -- against the ring kernel (variant 1: same MFMA, same K order, so the output tensor is BITWISE equal; the column
+whole input rows in LDS -- against the ring kernel (variant 5, a 64-column tile: the wider tiles do not run Cout <= 64; same MFMA, same K order, so the output tensor is BITWISE equal; the column
 sums to rounding) and the f64 definition: the stem's own map sizes at a small batch, maps whose rows are barely 128 pixels wide, tiles that
 straddle two rows and two images, a ragged last tile, statistics as slabs / integer atomics / none, grouped."""
 import ctypes as C
@@ -10,12 +10,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_cases import resolved, run_named
 from test_gpu_kernels import _conv_op, _stem_op, cu, st, sync
 
 pytestmark = pytest.mark.gpu
 sat = importlib.import_module("show-and-tell_amd")
 L = sat._lib
 RS = 38
+RING = 5            # the ring kernel with 64-column tiles: the comparison kernel for Cout <= 64 (128- and 256-column tiles do not run it)
 RS64 = 39
 RS8 = 40
 RS_STEM = 41
@@ -28,7 +30,7 @@ def lib():
 
 
 @pytest.mark.parametrize("mode", ["slab", "atomic", "none"])
-@pytest.mark.parametrize("N,H,W,Cout,pad", [(2, 149, 149, 32, 0), (2, 147, 147, 64, 1), (1, 5, 131, 32, 0), (3, 4, 128, 64, 1), (1, 3, 300, 64, 0)])
+@pytest.mark.parametrize("N,H,W,Cout,pad", [(2, 149, 149, 32, 0), (2, 147, 147, 64, 1), (1, 5, 131, 32, 0), (3, 4, 128, 64, 1), (1, 3, 162, 64, 0)])
 def test_conv_rs_is_bit_identical_to_the_ring_kernel(lib, N, H, W, Cout, pad, mode):
     Cin = 32
     g = torch.Generator().manual_seed(N * 13 + W + Cout)
@@ -43,12 +45,11 @@ def test_conv_rs_is_bit_identical_to_the_ring_kernel(lib, N, H, W, Cout, pad, mo
         if mode == "atomic":
             extra["acc"] = torch.zeros(2, 2, Cout, dtype=torch.int64, device="cuda")
             o.stat_acc = extra["acc"].data_ptr()
-        ops = (L.SatOp * 1)(o)
-        L.check(lib.sat_run_ops_parity(ops, 1, 0, st()))
+        run_named(lib, o)
         sync()
         return keep, extra
 
-    want, wx = run(1)
+    want, wx = run(RING)
     got, gx = run(RS)
     assert torch.isfinite(got[2].float()).all()
     assert torch.equal(got[2], want[2])
@@ -77,7 +78,7 @@ def test_conv_rs_is_the_default_for_its_geometry_and_runs_grouped(lib):
         o1, k1, _ = _conv_op(L.SAT_BF16, x.float(), w.float(), 1, 1, stats=False)
         acc = torch.zeros(2, 2, Cout, dtype=torch.int64, device="cuda")
         o1.stat_acc, o1.variant = acc.data_ptr(), RS
-        L.check(lib.sat_run_ops_parity(C.pointer(o1), 1, 0, st()))
+        run_named(lib, o1)
         sync()
         outs.append((k1[2].clone(), acc.clone()))
     xg = cu(torch.stack(xs))
@@ -85,7 +86,7 @@ def test_conv_rs_is_the_default_for_its_geometry_and_runs_grouped(lib):
     outg = torch.full((2, N * H * W, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
     accg = torch.zeros(2, 2, 2, Cout, dtype=torch.int64, device="cuda")
     og.in0, og.out, og.stat_acc, og.groups, og.variant = xg.data_ptr(), outg.data_ptr(), accg.data_ptr(), 2, RS
-    L.check(lib.sat_run_ops_parity(C.pointer(og), 1, 0, st()))
+    run_named(lib, og)
     sync()
     for q in range(2):
         assert torch.equal(outg[q], outs[q][0]) and torch.equal(accg[q], outs[q][1])
@@ -99,6 +100,7 @@ def test_conv_rs_refuses_other_geometries(lib):
         o, keep, _ = _conv_op(L.SAT_BF16, x, w, stride, pad, stats=False)
         assert lib.sat_conv_default_variant(C.byref(o), -1) != RS
         o.variant = RS                                    # asked for anyway: the launch falls back on a variant that runs it
+        assert resolved(lib, o) == lib.sat_conv_default_variant(C.byref(o), -1)
         L.check(lib.sat_run_ops_parity(C.pointer(o), 1, 0, st()))
         sync()
         ref = F.conv2d(x.bfloat16().double().permute(0, 3, 1, 2), w.bfloat16().double().permute(0, 3, 1, 2), None, stride, pad)
@@ -123,16 +125,15 @@ def test_conv_rs64_is_bit_identical_to_the_ring_kernel(lib, N, H, W, mode):
         if mode == "atomic":
             extra["acc"] = torch.zeros(2, 2, Cout, dtype=torch.int64, device="cuda")
             o.stat_acc = extra["acc"].data_ptr()
-        ops = (L.SatOp * 1)(o)
-        L.check(lib.sat_run_ops_parity(ops, 1, 0, st()))
+        run_named(lib, o)
         sync()
         return keep, extra
 
-    want, wx = run(1)
-    got, gx = run(RS64)
     slabs_ok = mode != "slab" or lib.sat_conv_tiles_m(N * H * W) >= min(N * H // 2, 512)
     if not slabs_ok:
         pytest.skip("fewer statistics slabs than workgroups: the library falls back on another variant")
+    want, wx = run(RING)
+    got, gx = run(RS64)
     assert torch.isfinite(got[2].float()).all()
     assert torch.equal(got[2], want[2])
     assert (got[2].float().cpu().double() - ref).abs().max().item() < 3e-2 + 4e-3 * ref.abs().max().item()
@@ -155,7 +156,7 @@ def test_conv_rs64_default_signature_and_groups(lib):
         o1, k1, _ = _conv_op(L.SAT_BF16, x.float(), w.float(), 1, 1, stats=False)
         acc = torch.zeros(2, 2, C_, dtype=torch.int64, device="cuda")
         o1.stat_acc, o1.variant = acc.data_ptr(), RS64
-        L.check(lib.sat_run_ops_parity(C.pointer(o1), 1, 0, st()))
+        run_named(lib, o1)
         sync()
         outs.append((k1[2].clone(), acc.clone()))
     xg = cu(torch.stack(xs))
@@ -163,7 +164,7 @@ def test_conv_rs64_default_signature_and_groups(lib):
     outg = torch.full((2, N * H * W, C_), float("nan"), device="cuda", dtype=torch.bfloat16)
     accg = torch.zeros(2, 2, 2, C_, dtype=torch.int64, device="cuda")
     og.in0, og.out, og.stat_acc, og.groups, og.variant = xg.data_ptr(), outg.data_ptr(), accg.data_ptr(), 2, RS64
-    L.check(lib.sat_run_ops_parity(C.pointer(og), 1, 0, st()))
+    run_named(lib, og)
     sync()
     for q in range(2):
         assert torch.equal(outg[q], outs[q][0]) and torch.equal(accg[q], outs[q][1])
@@ -187,14 +188,13 @@ def test_conv_rs8_is_bit_identical_to_the_ring_kernel(lib, N, H, W, mode):
         if mode == "atomic":
             extra["acc"] = torch.zeros(2, 2, Cout, dtype=torch.int64, device="cuda")
             o.stat_acc = extra["acc"].data_ptr()
-        ops = (L.SatOp * 1)(o)
         if v == RS8:
             assert lib.sat_conv_default_variant(C.byref(o), -1) == RS8
-        L.check(lib.sat_run_ops_parity(ops, 1, 0, st()))
+        run_named(lib, o)
         sync()
         return keep, extra
 
-    want, wx = run(1)
+    want, wx = run(RING)
     got, gx = run(RS8)
     assert torch.isfinite(got[2].float()).all()
     assert torch.equal(got[2], want[2])
@@ -206,10 +206,12 @@ def test_conv_rs8_is_bit_identical_to_the_ring_kernel(lib, N, H, W, mode):
         torch.testing.assert_close(gx["acc"].double() / 2 ** 22, wx["acc"].double() / 2 ** 22, rtol=1e-4, atol=3e-2)
 
 
-@pytest.mark.parametrize("N,H,W,groups", [(3, 224, 224, 1), (2, 160, 192, 1), (1, 130, 250, 1), (2, 224, 224, 2)])
+@pytest.mark.parametrize("N,H,W,groups", [(6, 224, 224, 1), (9, 160, 192, 1), (9, 130, 248, 1), (6, 224, 224, 2)])
 def test_conv_rs_stem_is_bit_identical_to_the_stem_kernel(lib, N, H, W, groups):
     """conv_rs_stem_kernel (variant 41): ResNet's 7 x 7 / stride 2 stem in the op program's layout as a rolling window of seven input
-    rows, against conv_stem_kernel (variant 31): output bitwise equal, the column sums (per workgroup here, per tile there) equal in total"""
+    rows, against conv_stem_kernel (variant 31): output bitwise equal, the column sums (per workgroup here, per tile there) equal in total.
+    The kernel owns a statistics slab per workgroup (one per output row, 512 at most), so with slabs it runs only where there are that
+    many 128-row slabs: six images at 224 x 224, nine at the smaller maps (the widest rows its LDS window holds: 256 padded pixels)"""
     g = torch.Generator().manual_seed(N * 7 + W)
     Hp, Wp = H + 6, (W + 8 + 1) // 2 * 2
     Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
@@ -222,7 +224,7 @@ def test_conv_rs_stem_is_bit_identical_to_the_stem_kernel(lib, N, H, W, groups):
     for v in (31, RS_STEM):
         o, out, part = _stem_op(xd, wd, Ho, Wo, groups)
         o.variant = v
-        L.check(lib.sat_run_ops(C.pointer(o), 1, st()))
+        run_named(lib, o)
         sync()
         res[v] = (out.clone(), part.clone())
     assert lib.sat_conv_variant_signature(RS_STEM) == 7002
@@ -233,7 +235,7 @@ def test_conv_rs_stem_is_bit_identical_to_the_stem_kernel(lib, N, H, W, groups):
         for q in range(2):
             o, out, part = _stem_op(xd[q * N:(q + 1) * N].contiguous(), wd, Ho, Wo, 1)
             o.variant = RS_STEM
-            L.check(lib.sat_run_ops(C.pointer(o), 1, st()))
+            run_named(lib, o)
             sync()
             assert torch.equal(out, res[RS_STEM][0][q * N * Ho * Wo:(q + 1) * N * Ho * Wo])
             assert torch.equal(part[0], res[RS_STEM][1][q])
@@ -261,7 +263,7 @@ def test_rolling_window_kernels_run_the_inference_epilogue(lib, kind):
     else:
         N, H, W, Cin, Cout, stride, pad, variant = {"rs32": (2, 20, 149, 32, 32, 1, 0, RS), "rs64": (3, 56, 56, 64, 64, 1, 1, RS64),
                                                     "rs8": (2, 41, 299, 8, 32, 2, 0, RS8)}[kind]
-        base = 1
+        base = RING
         x = (torch.randn(N, H, W, Cin, generator=g) + 0.1).bfloat16().float()
         w = (torch.randn(Cout, 3, 3, Cin, generator=g) / (3.0 * Cin ** 0.5)).bfloat16().float()
 
@@ -276,7 +278,7 @@ def test_rolling_window_kernels_run_the_inference_epilogue(lib, kind):
         o.scale1, o.shift1, o.flags, o.variant = sc.data_ptr(), sh.data_ptr(), 1, v
         if v == variant:
             assert lib.sat_conv_default_variant(C.byref(o), -1) == variant          # (no table entry: the geometry's default)
-        L.check(lib.sat_run_ops(C.pointer(o), 1, st()))
+        run_named(lib, o)
         sync()
         outs[v] = out.clone()
     assert torch.isfinite(outs[variant].float()).all() and float(outs[variant].float().min()) >= 0.0

@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_cases import RING_PARAMS, resolved, run_named
+
 pytestmark = pytest.mark.gpu
 
 sat = importlib.import_module("show-and-tell_amd")
@@ -96,7 +98,7 @@ def test_conv_fwd_and_stats(lib, dtype, N, H, W, Cin, Cout, k, stride, pad):
         x, w = x.bfloat16().float(), w.bfloat16().float()
     ref = F.conv2d(x.double(), w.double(), None, stride, pad).permute(0, 2, 3, 1).reshape(-1, Cout)
     o, keep, (n, ho, wo, co) = _conv_op(dtype, x.permute(0, 2, 3, 1), w.permute(0, 2, 3, 1), stride, pad)
-    L.check(lib.sat_run_ops(C.pointer(o), 1, st()))
+    run_named(lib, o)
     sync()
     out = keep[2].float().cpu().double()
     assert torch.isfinite(out).all()
@@ -115,21 +117,34 @@ PLAIN_CONV_VARIANTS = list(range(1, 27))      # ring kernel variants (27..29: co
 @pytest.mark.parametrize("N,H,W,Cin,Cout,k,stride,pad", [(3, 15, 13, 64, 192, 3, 1, 1), (2, 9, 9, 24, 72, 3, 2, 1),
                                                          (5, 8, 8, 320, 64, 1, 1, 0)])
 def test_conv_bf16_every_kernel_variant(lib, variant, N, H, W, Cin, Cout, k, stride, pad):
-    """every (tile, ring depth, waves) variant the autotuner may pick computes the same convolution + statistics"""
+    """every (tile, ring depth, waves) variant the autotuner may pick computes the same convolution + statistics.  A variant runs
+    only what `variant_ok` admits (anything else is silently another kernel), so: a tile wider than the shape's Cout admits gets
+    the next Cout it does (128 columns: Cout > 64, 256 columns: Cout > 128; still a ragged last column tile), and the 64-row-tile
+    variants, which have no statistics slabs (those are 128-row tiles), leave their column sums as integer-atomic sums"""
+    bn, bm = RING_PARAMS[variant][0], RING_PARAMS[variant][5]
+    if Cout <= bn // 2:
+        Cout = {128: 136, 256: 264}[bn]
     g = torch.Generator().manual_seed(variant * 31 + Cin)
     x = (torch.randn(N, Cin, H, W, generator=g)).bfloat16().float()
     w = (torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5).bfloat16().float()
     ref = F.conv2d(x.double(), w.double(), None, stride, pad).permute(0, 2, 3, 1).reshape(-1, Cout)
-    o, keep, _ = _conv_op(L.SAT_BF16, x.permute(0, 2, 3, 1), w.permute(0, 2, 3, 1), stride, pad)
+    o, keep, _ = _conv_op(L.SAT_BF16, x.permute(0, 2, 3, 1), w.permute(0, 2, 3, 1), stride, pad, stats=(bm == 128))
     o.variant = variant
-    L.check(lib.sat_run_ops(C.pointer(o), 1, st()))
+    if bm != 128:
+        acc = torch.zeros(2, 2, Cout, dtype=torch.int64, device="cuda")
+        o.stat_acc = acc.data_ptr()
+    run_named(lib, o)
     sync()
     out = keep[2].float().cpu().double()
     assert torch.isfinite(out).all()
     assert (out - ref).abs().max().item() < 2e-2
-    part = keep[3].cpu().double()
-    np.testing.assert_allclose(part[:, 0].sum(0).numpy(), ref.sum(0).numpy(), rtol=0, atol=1e-3 * ref.shape[0] ** 0.5 + 1e-4)
-    np.testing.assert_allclose(part[:, 1].sum(0).numpy(), (ref ** 2).sum(0).numpy(), rtol=2e-4, atol=1e-3)
+    if bm == 128:
+        part = keep[3].cpu().double()
+        s, q = part[:, 0].sum(0), part[:, 1].sum(0)
+    else:
+        s, q = acc[0, 0].cpu().double() / 2 ** 22, acc[0, 1].cpu().double() / 2 ** 22
+    np.testing.assert_allclose(s.numpy(), ref.sum(0).numpy(), rtol=0, atol=1e-3 * ref.shape[0] ** 0.5 + 1e-4)
+    np.testing.assert_allclose(q.numpy(), (ref ** 2).sum(0).numpy(), rtol=2e-4, atol=1e-3)
 
 
 @pytest.mark.parametrize("stat_mode", ["slab", "atomic"])
@@ -167,7 +182,7 @@ def test_conv_expansion_1x1_register_resident_panel_is_bit_identical(lib, varian
             o.running_mean1, o.running_var1 = rm.data_ptr(), rv.data_ptr()
             o.count, o.momentum, o.eps = M, 0.1, 1e-5
             extra.update(iacc=iacc, gd=gd, bd=bd, rm=rm, rv=rv)
-        L.check(lib.sat_run_ops_parity(C.pointer(o), 1, 0, st()))
+        run_named(lib, o)
         sync()
         return keep, extra
 
@@ -215,7 +230,7 @@ def test_conv3x3_lds_resident_patch_matches_the_ring_kernel(lib, N, H, W, Cin, C
         if stat_mode == "atomic":
             acc = torch.zeros(2, 2, Cout, dtype=torch.int64, device="cuda")
             o.stat_acc = acc.data_ptr()
-        L.check(lib.sat_run_ops_parity(C.pointer(o), 1, 0, st()))
+        run_named(lib, o)
         sync()
         return keep, acc
 
@@ -271,7 +286,7 @@ def test_conv3x3_lds_resident_patch_with_fused_input_bn_relu(lib, N, H, W, Cin, 
             sd, td = cu(scale), cu(shift)
             o.scale0, o.shift0 = sd.data_ptr(), td.data_ptr()
             extra.update(sd=sd, td=td)
-        L.check(lib.sat_run_ops_parity(C.pointer(o), 1, 0, st()))
+        run_named(lib, o)
         sync()
         return keep, extra
 
@@ -337,7 +352,7 @@ def test_conv3x3_weights_in_registers_is_bit_identical_to_the_lds_patch_kernel(l
         if stat_mode == "eval":
             extra += [cu(osc), cu(osh)]
             o.scale1, o.shift1, o.flags = extra[1].data_ptr(), extra[2].data_ptr(), 1
-        L.check(lib.sat_run_ops_parity(C.pointer(o), 1, 0, st()))
+        run_named(lib, o)
         sync()
         return keep, acc
 
@@ -395,7 +410,7 @@ def test_conv3x3_weights_in_registers_with_fused_input_bn_relu(lib, N, H, W, Cin
             sd, td = cu(scale), cu(shift)
             o.scale0, o.shift0 = sd.data_ptr(), td.data_ptr()
             extra.update(sd=sd, td=td)
-        L.check(lib.sat_run_ops_parity(C.pointer(o), 1, 0, st()))
+        run_named(lib, o)
         sync()
         return keep, extra
 
@@ -444,7 +459,7 @@ def test_conv1x1_weights_in_registers_is_bit_identical_to_the_ring_kernel(lib, N
             if mode == "eval_residual":
                 extra.append(cu(res))
                 o.in1 = extra[3].data_ptr()
-        L.check(lib.sat_run_ops_parity(C.pointer(o), 1, 0, st()))
+        run_named(lib, o)
         sync()
         return keep, acc
 
@@ -505,7 +520,7 @@ def test_conv1x1_weights_in_registers_with_fused_input_bn_relu(lib, N, H, W, Cin
             sd, td = cu(scale), cu(shift)
             o.scale0, o.shift0 = sd.data_ptr(), td.data_ptr()
             extra.update(sd=sd, td=td)
-        L.check(lib.sat_run_ops_parity(C.pointer(o), 1, 0, st()))
+        run_named(lib, o)
         sync()
         return keep, extra
 
@@ -555,7 +570,7 @@ def test_conv_stem_kernel_is_bit_identical_to_the_ring_kernel(lib, N, H, W):
     for v in (10, 31, 0):                               # 0: the heuristic must pick the stem kernel for this layout
         o, out, part = _stem_op(xd, wd, Ho, Wo)
         o.variant = v
-        L.check(lib.sat_run_ops(C.pointer(o), 1, st()))
+        run_named(lib, o)
         sync()
         res[v] = (out.clone(), part.clone())
     assert torch.isfinite(res[31][0].float()).all()
@@ -589,13 +604,13 @@ def test_grouped_conv_launch_equals_one_launch_per_batch(lib, kind):
         xd, wd = x.bfloat16().cuda(), w.reshape(64, 224).bfloat16().cuda()
         og, outg, partg = _stem_op(xd, wd, Ho, Wo, groups=G)
         og.variant = 31
-        L.check(lib.sat_run_ops(C.pointer(og), 1, st()))
+        run_named(lib, og)
         sync()
         M = N * Ho * Wo
         for k in range(G):
             o1, out1, part1 = _stem_op(xd[k * N:(k + 1) * N].contiguous(), wd, Ho, Wo)
             o1.variant = 31
-            L.check(lib.sat_run_ops(C.pointer(o1), 1, st()))
+            run_named(lib, o1)
             sync()
             assert torch.equal(outg[k * M:(k + 1) * M], out1) and torch.equal(partg[k], part1[0])
         return
@@ -630,7 +645,7 @@ def test_grouped_conv_launch_equals_one_launch_per_batch(lib, kind):
             o.running_mean1, o.running_var1 = log[0, 0].data_ptr(), log[0, 1].data_ptr()
             o.count, o.momentum, o.eps = M, 1.0, 1e-5
             extra.update(iacc=iacc, gd=gd, bd=bd, log=log)
-        L.check(lib.sat_run_ops_parity(C.pointer(o), 1, 0, st()))
+        run_named(lib, o)
         sync()
         return keep[2], extra
 
@@ -949,7 +964,7 @@ def test_conv1x1_with_input_bn_relu_fused(lib, derive, variant):
         sd, td = cu(scale), cu(shift)
         o.scale0, o.shift0 = sd.data_ptr(), td.data_ptr()
         extra = [sd, td]
-    L.check(lib.sat_run_ops_parity(C.pointer(o), 1, 0, st()))
+    run_named(lib, o)
     sync()
     out = keep[2].float().cpu().double()
     assert (out - ref).abs().max().item() < 3e-2 + 4e-3 * ref.abs().max().item()
@@ -983,7 +998,7 @@ def test_conv_inference_epilogue_affine_residual_relu(lib, variant, k, stride, p
     o.scale1, o.shift1, o.flags, o.variant = scd.data_ptr(), shd.data_ptr(), 1 if relu else 0, variant
     if resid:
         o.in1 = zd.data_ptr()
-    L.check(lib.sat_run_ops(C.pointer(o), 1, st()))
+    run_named(lib, o)
     sync()
     out = keep[2].float().cpu().double()
     assert (out - ref).abs().max().item() < 3e-2 + 8e-3 * ref.abs().max().item()
@@ -1411,12 +1426,13 @@ def test_wide_tile_output_stores_are_stable_over_many_launches(lib, variant):
     x = torch.randn(N, Cin, H, W, generator=g).bfloat16().float()
     w = (torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5).bfloat16().float()
     ref = F.conv2d(x.double(), w.double(), None, 1, 1).permute(0, 2, 3, 1).reshape(-1, Cout)
-    o, keep, _ = _conv_op(L.SAT_BF16, x.permute(0, 2, 3, 1), w.permute(0, 2, 3, 1), 1, 1)
+    # (the statistics slabs are 128-row tiles: the 64-row-tile variant runs without them; the pin is on the output stores)
+    o, keep, _ = _conv_op(L.SAT_BF16, x.permute(0, 2, 3, 1), w.permute(0, 2, 3, 1), 1, 1, stats=(RING_PARAMS[variant][5] == 128))
     o.variant = variant
     first = None
     for rep in range(40):
         keep[2].fill_(float("nan"))
-        L.check(lib.sat_run_ops(C.pointer(o), 1, st()))
+        run_named(lib, o)
         out = keep[2].clone()
         if first is None:
             first = out
@@ -1447,7 +1463,7 @@ def test_weights_in_registers_kernels_repeat_bit_for_bit_under_full_occupancy(li
     for rep in range(30):
         keep[2].fill_(float("nan"))
         acc.zero_()
-        L.check(lib.sat_run_ops_parity(C.pointer(o), 1, 0, st()))
+        run_named(lib, o)
         out, a = keep[2].clone(), acc.clone()
         if first is None:
             first = (out, a)
