@@ -1,4 +1,4 @@
-// Included by sat_conv_glds.hip inside its anonymous namespace (shares ConvArgs, the variant table and the epilogue conventions).
+// Included by sat_conv_glds.hip inside its anonymous namespace (shares ConvArgs, the variant table and the pieces of sat_conv_tile.h).
 //
 // "Expansion" 1x1 convolution (conv3 of a bottleneck, `self.resnet(images)`, models.py:27: K = planes = 256 input channels, N = 4 K
 // output channels) with the WEIGHTS RESIDENT IN REGISTERS and the workgroup PERSISTENT over row tiles.
@@ -92,9 +92,7 @@ __global__ __launch_bounds__(256, 2) void conv_ap_kernel(const ConvArgs p_) {
 
     if constexpr (AFF) {
         conv_in_table<NT>(p, in_tab);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // (a raw barrier: __syncthreads would also wait for every load in flight)
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        lds_barrier();      // (not __syncthreads: that would also wait for every load in flight)
     }
     // a landed stage (K-step kt of some tile) on its way to LDS buffer `buf`: relu(x * scale + shift) per channel, bit for bit the
     // normalise+ReLU kernel (rows past M stay zero)
@@ -102,23 +100,11 @@ __global__ __launch_bounds__(256, 2) void conv_ap_kernel(const ConvArgs p_) {
         char* at0 = smem + buf * ABUF + r0 * 128 + (lc << 4);
         if constexpr (AFF) {
             const float* ts = in_tab + kt * 64 + ((lc ^ sw0) << 3);
-            const f32x4 s0 = *(const f32x4*)ts, s1 = *(const f32x4*)(ts + 4);
-            const f32x4 t0 = *(const f32x4*)(ts + p.Cin), t1 = *(const f32x4*)(ts + p.Cin + 4);
+            const InTab tab = in_tab_fetch(ts, p.Cin);
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 u32x4 w = src[j];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    f32x2 sc2, sh2, f;
-                    sc2[0] = q < 2 ? s0[2 * q] : s1[2 * q - 4]; sc2[1] = q < 2 ? s0[2 * q + 1] : s1[2 * q - 3];
-                    sh2[0] = q < 2 ? t0[2 * q] : t1[2 * q - 4]; sh2[1] = q < 2 ? t0[2 * q + 1] : t1[2 * q - 3];
-                    f[0] = __uint_as_float(w[q] << 16);
-                    f[1] = __uint_as_float(w[q] & 0xffff0000u);
-                    f = __builtin_elementwise_fma(f, sc2, sh2);
-                    const s16x2 pk = __builtin_bit_cast(s16x2, __builtin_convertvector(f, bf16x2));
-                    const s16x2 zero2 = {0, 0};
-                    w[q] = ((ok >> j) & 1u) ? __builtin_bit_cast(unsigned int, __builtin_elementwise_max(pk, zero2)) : 0u;
-                }
+                w = bn_relu_chunk(w, tab, (ok >> j) & 1u);
                 *(u32x4*)(at0 + j * (RJ * 128)) = w;
             }
         } else {
@@ -130,7 +116,7 @@ __global__ __launch_bounds__(256, 2) void conv_ap_kernel(const ConvArgs p_) {
     // A fragment addresses, K-invariant: row i*32 + r (the four row blocks 4096 B apart, same swizzle), chunk (2 ks + h) ^ ((r >> 1) & 7)
     int a_off[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) a_off[ks] = r * 128 + (((2 * ks + h) ^ ((r >> 1) & 7)) << 4);
+    for (int ks = 0; ks < 4; ++ks) a_off[ks] = frag_off(r, h, ks);
 
     const __amdgpu_buffer_rsrc_t csrc = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, (int)((long)p.M * p.ldc * 2), 0x00020000);
     // this thread's eight 16-byte pieces of an output tile: piece `it` = row (tid >> 4) + 16 it, chunk tid & 15 -- one lane offset,
@@ -152,9 +138,7 @@ __global__ __launch_bounds__(256, 2) void conv_ap_kernel(const ConvArgs p_) {
         auto step = [&](auto kt_tag) {
             constexpr int KT = decltype(kt_tag)::value, K1 = (KT + 1) & 3;
             const int g = ts_ * NKS + KT;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // this wave's LDS writes of stage g ...
-            __builtin_amdgcn_s_barrier();                          // ... and everybody's; everybody is done with stage g - 1
-            asm volatile("" ::: "memory");
+            lds_barrier();      // this wave's LDS writes of stage g and everybody's; everybody is done with stage g - 1
             if (g + 1 < S) store_a_stage(K1, K1 & 1, ar[K1], KT == 3 ? ok_next : ok_cur);      // (uniform branch)
             load_a_stage(g + 5, ar[K1]);
             const char* st = smem + (KT & 1) * ABUF;
@@ -198,12 +182,10 @@ __global__ __launch_bounds__(256, 2) void conv_ap_kernel(const ConvArgs p_) {
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int row = acc_row(i, e, h);
                 *(bf16_t*)(ctile + row * CROW + colw * 2) = (bf16_t)acc[i][e];
             }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                          // (the next tile's first K-step barrier keeps the tile region safe)
-        asm volatile("" ::: "memory");
+        lds_barrier();      // (the next tile's first K-step barrier keeps the tile region safe)
         // write-through (sc0 sc1) stores the compiler counts itself (a raw buffer store, not store16_wt's inline asm: uncounted stores
         // in the loop would make every counted wait on a younger activation stage wait for them too); rows past M fall outside the
         // buffer and are dropped

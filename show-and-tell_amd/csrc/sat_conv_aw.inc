@@ -1,4 +1,4 @@
-// Included by sat_conv_glds.hip inside its anonymous namespace (shares ConvArgs, the variant table and the epilogue conventions).
+// Included by sat_conv_glds.hip inside its anonymous namespace (shares ConvArgs, the variant table and the pieces of sat_conv_tile.h).
 //
 // 1x1 convolution (conv1 / conv3 / the projection of a bottleneck, `self.resnet(images)`, models.py:27) as a 128 x 128-tile GEMM with
 // the WEIGHTS STRAIGHT INTO REGISTERS from the fragment-ordered copy (sat_conv_pack_weights, taps = 1) -- conv_pw_kernel's other half:
@@ -100,9 +100,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_aw_kernel(const ConvArgs p_) 
     float* in_tab = (float*)(smem + TAB);
     if constexpr (AFF) {
         conv_in_table<NT>(p, in_tab);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // (a raw barrier: __syncthreads would also wait for every load in flight)
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        lds_barrier();      // (not __syncthreads: that would also wait for every load in flight)
     }
     // a landed stage on its way to LDS: (AFF: relu(x * scale + shift) per channel, bit for bit the normalise+ReLU kernel; rows past M
     // stay zero) then 16 bytes per row into slot lc of rows r0 + 32 j of buffer `buf`
@@ -112,23 +110,11 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_aw_kernel(const ConvArgs p_) 
             const float* ts = in_tab + g * 64 + ((lc ^ sw0) << 3);
             const bool live = g < nk;                           // (past the end: whatever, nobody reads it; keep the table reads in bounds)
             const float* tq = live ? ts : in_tab;
-            const f32x4 s0 = *(const f32x4*)tq, s1 = *(const f32x4*)(tq + 4);
-            const f32x4 t0 = *(const f32x4*)(tq + p.Cin), t1 = *(const f32x4*)(tq + p.Cin + 4);
+            const InTab tab = in_tab_fetch(tq, p.Cin);
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 u32x4 w = src[j];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    f32x2 sc2, sh2, f;
-                    sc2[0] = q < 2 ? s0[2 * q] : s1[2 * q - 4]; sc2[1] = q < 2 ? s0[2 * q + 1] : s1[2 * q - 3];
-                    sh2[0] = q < 2 ? t0[2 * q] : t1[2 * q - 4]; sh2[1] = q < 2 ? t0[2 * q + 1] : t1[2 * q - 3];
-                    f[0] = __uint_as_float(w[q] << 16);
-                    f[1] = __uint_as_float(w[q] & 0xffff0000u);
-                    f = __builtin_elementwise_fma(f, sc2, sh2);
-                    const s16x2 pk = __builtin_bit_cast(s16x2, __builtin_convertvector(f, bf16x2));
-                    const s16x2 zero2 = {0, 0};
-                    w[q] = ((a_ok >> j) & 1u) ? __builtin_bit_cast(unsigned int, __builtin_elementwise_max(pk, zero2)) : 0u;
-                }
+                w = bn_relu_chunk(w, tab, (a_ok >> j) & 1u);
                 *(u32x4*)(at0 + j * (RJ * 128)) = w;
             }
         } else {
@@ -140,7 +126,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_aw_kernel(const ConvArgs p_) 
     // A fragment addresses, K-invariant: row i*32 + r (the four row blocks 4096 B apart, same swizzle), chunk (2 ks + h) ^ ((r >> 1) & 7)
     int a_off[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) a_off[ks] = r * 128 + (((2 * ks + h) ^ ((r >> 1) & 7)) << 4);
+    for (int ks = 0; ks < 4; ++ks) a_off[ks] = frag_off(r, h, ks);
 
     store_a_stage(0, 0, ar[0]);
     load_a_stage(3, ar[0]);
@@ -151,9 +137,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_aw_kernel(const ConvArgs p_) 
     auto step = [&](int g, auto u_tag, auto tail_tag) {
         constexpr int U = decltype(u_tag)::value, U1 = (U + 1) % 3;
         constexpr bool TAIL = decltype(tail_tag)::value;       // one of the last three K-steps: nothing it could request would be used
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // this wave's LDS writes of stage g ...
-        __builtin_amdgcn_s_barrier();                          // ... and everybody's; everybody is done with K-step g - 1 (a raw barrier:
-        asm volatile("" ::: "memory");                        // the loads in flight stay in flight)
+        // this wave's LDS writes of stage g and everybody's; everybody is done with K-step g - 1 (the loads in flight stay in flight)
+        lds_barrier();
         store_a_stage(g + 1, U1, ar[U1]);
         if constexpr (!TAIL) load_a_stage(g + 4, ar[U1]);
         const char* st = smem + U * ABUF;
@@ -201,9 +186,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_aw_kernel(const ConvArgs p_) 
     if (rem > 2) step(g + 2, std::integral_constant<int, 2>{}, std::true_type{});
     // (stages requested past the end by the steps before the peeled ones are plain loads the compiler tracks, register reuse included;
     // RES: the residual stays in flight across the statistics / tile staging)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // every wave's LDS traffic is done before the A buffers become the tile
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    lds_barrier();      // every wave's LDS traffic is done before the A buffers become the tile
 
     // ---- epilogue: BatchNorm column sums (a lane holds 64 of a column's 128 rows), bf16 tile through LDS ----
     if (p.stat_partial || p.acc) {
@@ -216,8 +199,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_aw_kernel(const ConvArgs p_) 
                 s += v;
                 q += v * v;
             }
-        s += __shfl_xor(s, 32, 64);
-        q += __shfl_xor(q, 32, 64);
+        lane_halves(s, q);
         const int col = n0 + colw;
         if (h == 0 && col < p.N) {
             if (p.acc) {
@@ -234,16 +216,14 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_aw_kernel(const ConvArgs p_) 
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int row = acc_row(i, e, h);
                 float v = acc[i][e];
                 if (p.out_scale) v = v * osc + osh;
                 if (relu_now) v = fmaxf(v, 0.0f);
                 *(bf16_t*)(smem + row * CROW + colw * 2) = (bf16_t)v;
             }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    lds_barrier();
 #pragma unroll
     for (int it = 0; it < ITS; ++it) {
         const int qid = tid + it * NT;

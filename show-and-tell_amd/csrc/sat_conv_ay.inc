@@ -1,4 +1,4 @@
-// Included by sat_conv_glds.hip inside its anonymous namespace (shares ConvArgs, the variant table and the epilogue conventions).
+// Included by sat_conv_glds.hip inside its anonymous namespace (shares ConvArgs, the variant table and the pieces of sat_conv_tile.h).
 //
 // conv1 of a bottleneck that ALSO FINISHES THE PREVIOUS BOTTLENECK (`self.resnet(images)`, models.py:27, train-mode BatchNorm):
 //     y_k   = relu(bn3_k(c3_k) + y_{k-1})          (what the normalise + add + ReLU launch computed and wrote)
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ay_kernel(const ConvArgs p_) 
     //      (the same for all its rows), so the LDS image is the ring kernel's.  Rows past M: an offset past the buffers (loads read 0,
     //      stores are dropped) ----
     const int lc = tid & 7, r0 = tid >> 3;
-    const int sw0 = (r0 >> 1) & 7;
+    const int sw0 = swz_of(r0);
     const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.A), 0, (int)(p.in_bytes), 0x00020000);
     const __amdgpu_buffer_rsrc_t zsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.in_res), 0, (int)(p.in_bytes), 0x00020000);
     const __amdgpu_buffer_rsrc_t ysrc = __builtin_amdgcn_make_buffer_rsrc(p.Y, 0, (int)(p.in_bytes), 0x00020000);
@@ -99,9 +99,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ay_kernel(const ConvArgs p_) 
     // bn3's (scale, shift) of all Cin channels into LDS once (bn_table's arithmetic, sat_bn_stats.h)
     {
         conv_in_table<NT>(p, in_tab);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // (a raw barrier: __syncthreads would also wait for every load in flight)
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        lds_barrier();      // (not __syncthreads: that would also wait for every load in flight)
     }
     // a landed stage on its way to LDS (and to y): relu(x * scale + shift + z) per channel; rows past M stay zero
     auto store_stage = [&](int g, int buf, u32x4 (&sx)[NJ], u32x4 (&sz)[NJ]) {
@@ -138,7 +136,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ay_kernel(const ConvArgs p_) 
     // A fragment addresses, K-invariant: row i*32 + r (the four row blocks 4096 B apart, same swizzle), chunk (2 ks + h) ^ ((r >> 1) & 7)
     int a_off[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) a_off[ks] = r * 128 + (((2 * ks + h) ^ ((r >> 1) & 7)) << 4);
+    for (int ks = 0; ks < 4; ++ks) a_off[ks] = frag_off(r, h, ks);
 
     store_stage(0, 0, ax[0], az[0]);
     load_stage(PDA, ax[0], az[0]);
@@ -149,9 +147,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ay_kernel(const ConvArgs p_) 
     auto step = [&](int g, auto u_tag, auto st_tag, auto al_tag, auto bl_tag) {
         constexpr int U = decltype(u_tag)::value, LB = U & 1, S1 = (U + 1) % PDA;
         constexpr bool ST = decltype(st_tag)::value, AL = decltype(al_tag)::value, BL = decltype(bl_tag)::value;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // this wave's LDS writes of stage g ...
-        __builtin_amdgcn_s_barrier();                          // ... and everybody's; everybody is done reading K-step g - 1 (a raw
-        asm volatile("" ::: "memory");                        // barrier: the loads in flight stay in flight)
+        lds_barrier();      // this wave's LDS writes of stage g and everybody's; everybody is done reading K-step g - 1
         if constexpr (ST) store_stage(g + 1, LB ^ 1, ax[S1], az[S1]);
         if constexpr (AL) load_stage(g + 1 + PDA, ax[S1], az[S1]);
         const char* st = smem + LB * ABUF;
@@ -188,11 +184,9 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ay_kernel(const ConvArgs p_) 
     group(g, std::integral_constant<int, 1>{});
     group(g + PDA, std::integral_constant<int, 2>{});
 
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // every wave's LDS traffic is done before the buffers become the tile
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    lds_barrier();      // every wave's LDS traffic is done before the buffers become the tile
 
-    // ---- epilogue (conv_aw_kernel's): BatchNorm column sums (a lane holds 64 of a column's 128 rows), bf16 tile through LDS ----
+    // ---- epilogue: BatchNorm column sums (a lane holds 64 of a column's 128 rows, then lane_halves), bf16 tile through LDS (acc_row) ----
     const int colw = wave * 32 + r;
     if (p.stat_partial || p.acc) {
         float s = 0.0f, q = 0.0f;
@@ -220,12 +214,10 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ay_kernel(const ConvArgs p_) 
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int row = i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int row = acc_row(i, e, h);
             *(bf16_t*)(smem + row * CROW + colw * 2) = (bf16_t)acc[i][e];
         }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    lds_barrier();
     constexpr int ITS = BM * (BN / 8) / NT;
 #pragma unroll
     for (int it = 0; it < ITS; ++it) {

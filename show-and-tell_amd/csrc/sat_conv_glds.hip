@@ -17,7 +17,7 @@
 //   * epilogue: f32 accumulators -> per-tile BatchNorm column sums (fixed order) and a bf16 tile staged through
 //     LDS so global stores are full 16-byte-per-lane rows;
 //   * blockIdx -> tile map is XCD-aware (tiles sharing an activation panel share an L2).
-#include "sat_bn_stats.h"
+#include "sat_conv_tile.h"
 #include <hip/hip_ext.h>
 
 // diagnostics (sat_run_ops_timed): when armed, the NEXT conv launch of this thread records its own begin / end
@@ -87,32 +87,6 @@ struct ConvArgs {
 };
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N == 0 || N == 2 || N == 3 || N == 4 || N == 5 || N == 6 || N == 7 || N == 8 || N == 9 || N == 10 || N == 12 ||
-                      N == 15 || N == 16 || N == 17 || N == 18 || N == 19 || N == 20 || N == 21 || N == 22 || N == 24,
-                  "add the vmcnt literal");
-    if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-    if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    if constexpr (N == 15) asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-    if constexpr (N == 19) asm volatile("s_waitcnt vmcnt(19)" ::: "memory");
-    if constexpr (N == 20) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-    if constexpr (N == 21) asm volatile("s_waitcnt vmcnt(21)" ::: "memory");
-    if constexpr (N == 22) asm volatile("s_waitcnt vmcnt(22)" ::: "memory");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    if constexpr (N == 17) asm volatile("s_waitcnt vmcnt(17)" ::: "memory");
-    if constexpr (N == 18) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-    if constexpr (N == 24) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-}
 
 // BN: tile width (128/64); S: ring stages; NW: waves (4/8); UNIFORM: Cin % 64 == 0 (a K-step never straddles a tap);
 // SPEC: wave specialisation -- waves 0..NW/2-1 own the accumulators (ds_read + MFMA only), waves NW/2..NW-1 only
@@ -225,7 +199,7 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
 #pragma unroll
     for (int i = 0; i < NAI; ++i) {
         const int row = lw * (NAI * 8) + i * 8 + (lane >> 3);
-        a_c[i] = ((lane & 7) ^ ((row >> 1) & 7)) * 8;
+        a_c[i] = swz_chunk(lane & 7, row) * 8;
         const int grow = m0 + row;
         a_mask[i] = 0u;
         if (grow < p.M && p.linear) {
@@ -258,7 +232,7 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
 #pragma unroll
     for (int i = 0; i < NBI; ++i) {
         const int row = lw * (NBI * 8) + i * 8 + (lane >> 3);
-        b_c[i] = ((lane & 7) ^ ((row >> 1) & 7)) * 8;
+        b_c[i] = swz_chunk(lane & 7, row) * 8;
         const int gn = n0 + row;
         b_ok[i] = gn < p.N;
         b_ptr[i] = b_ok[i] ? p.B + ((long)gn * p.ldb + b_c[i]) : zero;
@@ -363,13 +337,13 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
     for (int i = 0; i < TM; ++i) {
         const int row = wm * WM + i * 32 + r;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) a_off[i][ks] = row * 128 + (((2 * ks + h) ^ ((row >> 1) & 7)) << 4);
+        for (int ks = 0; ks < 4; ++ks) a_off[i][ks] = frag_off(row, h, ks);
     }
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int row = wn * WN + j * 32 + r;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) b_off[j][ks] = A_BYTES + row * 128 + (((2 * ks + h) ^ ((row >> 1) & 7)) << 4);
+        for (int ks = 0; ks < 4; ++ks) b_off[j][ks] = A_BYTES + row * 128 + (swz_chunk(2 * ks + h, row) << 4);      // (frag_off, summed in this order)
     }
 
     if (p.in_affine) {
@@ -385,7 +359,7 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
             const int q = tid + j * NT;
             const int row = q >> 3, pos = q & 7;
             if (m0 + row < p.M) {
-                const int c0 = kt * BK + ((pos ^ ((row >> 1) & 7)) << 3);      // channel of this chunk's first element
+                const int c0 = kt * BK + (swz_chunk(pos, row) << 3);      // channel of this chunk's first element
                 bf16x8 v = *(const bf16x8*)(sA + row * 128 + pos * 16);
                 const f32x4 s0 = *(const f32x4*)(in_tab + c0), s1 = *(const f32x4*)(in_tab + c0 + 4);
                 const f32x4 t0 = *(const f32x4*)(in_tab + p.Cin + c0), t1 = *(const f32x4*)(in_tab + p.Cin + c0 + 4);
@@ -397,20 +371,21 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
                 *(bf16x8*)(sA + row * 128 + pos * 16) = v;
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's LDS writes are done ...
-        __builtin_amdgcn_s_barrier();                         // ... and everybody's (raw barrier: the ring stays in flight)
-        asm volatile("" ::: "memory");
+        lds_barrier();         // this wave's LDS writes are done, and everybody's (no __syncthreads: the ring stays in flight)
     };
 
+    auto load_frag = [&](const char* st, int ks, bf16x8 (&fa)[TM], bf16x8 (&fb)[TN]) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) fa[i] = *(const bf16x8*)(st + a_off[i][ks]);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) fb[j] = *(const bf16x8*)(st + b_off[j][ks]);
+    };
     auto compute = [&](int buf) {
         const char* st = smem + buf * STAGE;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             bf16x8 af[TM], bf[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) af[i] = *(const bf16x8*)(st + a_off[i][ks]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) bf[j] = *(const bf16x8*)(st + b_off[j][ks]);
+            load_frag(st, ks, af, bf);
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -421,12 +396,6 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
 
     // PF: fragments of (stage, substep 0) are carried in registers across the barrier
     bf16x8 caf[TM], cbf[TN];
-    auto load_frag = [&](const char* st, int ks, bf16x8 (&fa)[TM], bf16x8 (&fb)[TN]) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) fa[i] = *(const bf16x8*)(st + a_off[i][ks]);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) fb[j] = *(const bf16x8*)(st + b_off[j][ks]);
-    };
     auto compute_pf = [&](int buf, bool first) {
         const char* st = smem + buf * STAGE;
         const char* nst = smem + (buf + 1 == S ? 0 : buf + 1) * STAGE;
@@ -461,8 +430,7 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
             int buf = 0;
             for (int kt = 0; kt < nk; ++kt) {
                 wait_vmcnt<WAITN>();
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
+                raw_barrier();
                 int nbuf = buf + D;
                 if (nbuf >= S) nbuf -= S;
                 issue(nbuf);
@@ -471,8 +439,7 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
         } else {
             int buf = 0;
             for (int kt = 0; kt < nk; ++kt) {
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");        // no LDS read may be hoisted above the barrier
+                raw_barrier();                         // no LDS read may be hoisted above the barrier
                 if constexpr (PF) compute_pf(buf, kt == 0);
                 else compute(buf);
                 buf = (buf + 1 == S) ? 0 : buf + 1;
@@ -484,8 +451,7 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
         int buf = 0;
         for (int kt = 0; kt < nk; ++kt) {
             wait_vmcnt<WAITN>();
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");            // no LDS read may be hoisted above the barrier
+            raw_barrier();                             // no LDS read may be hoisted above the barrier
             int nbuf = buf + D;
             if (nbuf >= S) nbuf -= S;
             issue(nbuf);
@@ -516,8 +482,7 @@ __global__ __launch_bounds__(NW * 64) void conv_glds_kernel(const ConvArgs p_) {
                     s += v;
                     q += v * v;
                 }
-            s += __shfl_xor(s, 32, 64);
-            q += __shfl_xor(q, 32, 64);
+            lane_halves(s, q);
             if (h == 0) {
                 red[(wm * 2 + 0) * BN + wn * WN + j * 32 + r] = s;
                 red[(wm * 2 + 1) * BN + wn * WN + j * 32 + r] = q;

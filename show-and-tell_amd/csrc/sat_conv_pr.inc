@@ -117,7 +117,7 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs p_) {
     }
     int b_off[4];                                              // B fragment offsets: row = wn*64 + j*32 + r, (row>>1)&7 = (r>>1)&7
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) b_off[ks] = (wn * 64 + r) * 128 + (((2 * ks + h) ^ ((r >> 1) & 7)) << 4);
+    for (int ks = 0; ks < 4; ++ks) b_off[ks] = (wn * 64 + r) * 128 + (swz_chunk(2 * ks + h, r) << 4);      // frag_off of row wn*64 + r, whose swizzle is r's
 
     f32x16 acc[2][2];
 #pragma unroll
@@ -138,28 +138,14 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs p_) {
     auto xform_patch = [&](int buf, int cb) {
         const int ll = tid - 256, lc = ll & 7, r0 = ll >> 3;
         const float* ts = in_tab + cb * 64 + lc * 8;
-        const f32x4 s0 = *(const f32x4*)ts, s1 = *(const f32x4*)(ts + 4);
-        const f32x4 t0 = *(const f32x4*)(ts + p.Cin), t1 = *(const f32x4*)(ts + p.Cin + 4);
+        const InTab tab = in_tab_fetch(ts, p.Cin);
         char* at0 = smem + buf * PBUF + r0 * 128 + ((lc ^ ((r0 >> 1) & 7)) << 4);
         u32x4 w[PRP / 4];
 #pragma unroll
         for (int j = 0; j < PRP / 4; ++j) w[j] = *(const u32x4*)(at0 + j * 4096);
 #pragma unroll
         for (int j = 0; j < PRP / 4; ++j) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                // word q = channels (2q, 2q+1): shift / mask, one packed fma, one packed convert (round to nearest even), ReLU on the
-                // bf16 pair as int16 -- bit for bit the scalar relu((float)x * scale + shift) -> bf16 of the normalise+ReLU kernel
-                f32x2 sc2, sh2, f;
-                sc2[0] = q < 2 ? s0[2 * q] : s1[2 * q - 4]; sc2[1] = q < 2 ? s0[2 * q + 1] : s1[2 * q - 3];
-                sh2[0] = q < 2 ? t0[2 * q] : t1[2 * q - 4]; sh2[1] = q < 2 ? t0[2 * q + 1] : t1[2 * q - 3];
-                f[0] = __uint_as_float(w[j][q] << 16);
-                f[1] = __uint_as_float(w[j][q] & 0xffff0000u);
-                f = __builtin_elementwise_fma(f, sc2, sh2);
-                const s16x2 pk = __builtin_bit_cast(s16x2, __builtin_convertvector(f, bf16x2));
-                const s16x2 zero2 = {0, 0};
-                w[j][q] = __builtin_bit_cast(unsigned int, __builtin_elementwise_max(pk, zero2));
-            }
+            w[j] = bn_relu_chunk(w[j], tab);
             *(u32x4*)(at0 + j * 4096) = w[j];
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -176,12 +162,10 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs p_) {
 #pragma unroll
         for (int s = 0; s < D; ++s) issue_b(s);
         wait_vmcnt<(D - 1) * NBI>();                           // the patch and stage 0
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        raw_barrier();
         if constexpr (AFF) {                                   // slice 0 (every loader's pieces have landed) before anybody reads it
             xform_patch(0, 0);
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
+            raw_barrier();
         }
         int slot = 0;
         for (int cb = 0; cb < NCB; ++cb) {
@@ -192,8 +176,7 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs p_) {
                 // this wait is about (g + 1) for t = 1 .. D-1, older (hence covered) from t = D on
                 if (t >= 1 && t <= D - 1 && has_next) wait_vmcnt<(D - 2) * NBI + PPL>();
                 else wait_vmcnt<(D - 2) * NBI>();
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
+                raw_barrier();
                 issue_b(slot == 0 ? S - 1 : slot - 1);
                 if (t == 0 && has_next) issue_patch((cb + 1) & 1);
                 // the next slice has landed for EVERY loader once barrier t = D is passed (each covered its own pieces in the wait
@@ -203,11 +186,9 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs p_) {
             }
         }
     } else {
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        raw_barrier();
         if constexpr (AFF) {
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
+            raw_barrier();
         }
         // fragment addresses of (patch buffer, tap): the A row of lane (r, h) is patch row r + kh W + kw, or the zero row
         auto a_addr = [&](const char* pb, int t, int i, const char*& base, int& sw) {
@@ -237,8 +218,7 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs p_) {
             const char* pbn = smem + ((cb + 1) & 1) * PBUF;
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
+                raw_barrier();
                 const char* sb = smem + RING + slot * SLOT;
                 const int nslot = (slot + 1 == S) ? 0 : slot + 1;
                 const char* sbn = smem + RING + nslot * SLOT;
@@ -267,7 +247,7 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs p_) {
     wait_vmcnt<0>();
     __syncthreads();
 
-    // ---- epilogue (the ring kernel's): BatchNorm column sums from the f32 accumulators, bf16 tile through LDS ----
+    // ---- epilogue: BatchNorm column sums from the f32 accumulators (lane_halves, then the M-waves in order), bf16 tile through LDS (acc_row) ----
     char* ring = smem + RING;
     float* red = (float*)(ring + BM * CROW);                  // [2 (wm)][2][BN]
     if ((p.stat_partial || p.acc) && !is_loader) {
@@ -298,7 +278,7 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs p_) {
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const int row = wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                    const int row = wm * 64 + acc_row(i, e, h);
                     *(bf16_t*)(ring + row * CROW + col * 2) = (bf16_t)acc[i][j][e];
                 }
         }

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs p_) {
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
         const int prow = (wave * PPL + e) * 8 + (lane >> 3);       // piece e; pieces e + 2, e + 4 sit 16, 32 rows further on
-        const int ch = (lane & 7) ^ ((prow >> 1) & 7);
+        const int ch = swz_chunk(lane & 7, prow);
         p_base[e] = p.A + (((long)m0 - (W + 1) + prow) * p.sW + ch * 8);
     }
     const long p_pitch = 8 * p.sW;                            // elements between consecutive pieces
@@ -144,9 +144,8 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs p_) {
     auto xform_patch = [&](int buf, int cb) {
         const int lc = tid & 7, r0 = tid >> 3;
         const float* ts = in_tab + cb * 64 + lc * 8;
-        const f32x4 s0 = *(const f32x4*)ts, s1 = *(const f32x4*)(ts + 4);
-        const f32x4 t0 = *(const f32x4*)(ts + p.Cin), t1 = *(const f32x4*)(ts + p.Cin + 4);
-        char* at0 = smem + buf * PBUF + r0 * 128 + ((lc ^ ((r0 >> 1) & 7)) << 4);
+        const InTab tab = in_tab_fetch(ts, p.Cin);
+        char* at0 = smem + buf * PBUF + r0 * 128 + (swz_chunk(lc, r0) << 4);
         // (three pieces at a time: the transform runs in the middle of the K loop, where registers are scarce)
 #pragma unroll
         for (int j0 = 0; j0 < PRP / 4; j0 += 3) {
@@ -157,19 +156,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs p_) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 if (j0 + j >= PRP / 4) continue;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    // bit for bit the scalar relu((float)x * scale + shift) -> bf16 of the normalise+ReLU kernel (conv_pr_kernel's form)
-                    f32x2 sc2, sh2, f;
-                    sc2[0] = q < 2 ? s0[2 * q] : s1[2 * q - 4]; sc2[1] = q < 2 ? s0[2 * q + 1] : s1[2 * q - 3];
-                    sh2[0] = q < 2 ? t0[2 * q] : t1[2 * q - 4]; sh2[1] = q < 2 ? t0[2 * q + 1] : t1[2 * q - 3];
-                    f[0] = __uint_as_float(w[j][q] << 16);
-                    f[1] = __uint_as_float(w[j][q] & 0xffff0000u);
-                    f = __builtin_elementwise_fma(f, sc2, sh2);
-                    const s16x2 pk = __builtin_bit_cast(s16x2, __builtin_convertvector(f, bf16x2));
-                    const s16x2 zero2 = {0, 0};
-                    w[j][q] = __builtin_bit_cast(unsigned int, __builtin_elementwise_max(pk, zero2));
-                }
+                w[j] = bn_relu_chunk(w[j], tab);
                 *(u32x4*)(at0 + (j0 + j) * 4096) = w[j];
             }
         }
@@ -189,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs p_) {
     auto tap_addr = [&](int buf, int t) {
         Tap a;
         const int prow = r + (t / 3) * W + (t % 3);
-        a.sw = (prow >> 1) & 7;
+        a.sw = swz_of(prow);
         const int base = buf * PBUF + prow * 128;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -224,8 +211,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs p_) {
                 if (t == 5) {
                     // slice cb + 1 is older than the weight loads of nine taps: any count below that many proves it landed
                     wait_vmcnt<24>();
-                    __builtin_amdgcn_s_barrier();
-                    asm volatile("" ::: "memory");
+                    raw_barrier();
                     __builtin_amdgcn_sched_barrier(0);
                     issue_patch(b2, cb + 2 < NCB);
                     __builtin_amdgcn_sched_barrier(0);
@@ -238,8 +224,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs p_) {
                 if constexpr (AFF && !LAST) {
                     if (t == 8 && ks == 3) {
                         // the first fragments of the next channel block come from the other buffer: everybody's transform is done
-                        __builtin_amdgcn_s_barrier();
-                        asm volatile("" ::: "memory");
+                        raw_barrier();
                     }
                 }
                 if (ks < 3) load_a(cur, ks + 1, f1);
@@ -278,8 +263,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs p_) {
                 s += v;
                 q += v * v;
             }
-        s += __shfl_xor(s, 32, 64);
-        q += __shfl_xor(q, 32, 64);
+        lane_halves(s, q);
         const int col = n0 + colw;
         if (h == 0 && col < p.N) {
             if (p.acc) {
@@ -297,7 +281,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvArgs p_) {
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int row = acc_row(i, e, h);
                 float v = acc[i][e];
                 if (p.out_scale) v = v * osc + osh;
                 if (p.out_relu) v = fmaxf(v, 0.0f);

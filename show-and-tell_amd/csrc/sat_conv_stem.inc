@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(const ConvArgs p_) {
         if (m0 + BM > p.M) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int row = wave * 32 + acc_row(0, e, h);
                 if (m0 + row >= p.M) { acc[0][e] = 0.0f; acc[1][e] = 0.0f; }
             }
         }
@@ -130,8 +130,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(const ConvArgs p_) {
                     s += v;
                     q += v * v;
                 }
-                s += __shfl_xor(s, 32, 64);
-                q += __shfl_xor(q, 32, 64);
+                lane_halves(s, q);
                 if (h == 0) {
                     red[(wave * 2 + 0) * BN + j * 32 + r] = s;
                     red[(wave * 2 + 1) * BN + j * 32 + r] = q;
@@ -142,7 +141,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(const ConvArgs p_) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int row = wave * 32 + acc_row(0, e, h);
                 *(bf16_t*)(ctile + row * CROW + (j * 32 + r) * 2) = (bf16_t)acc[j][e];
             }
         __syncthreads();

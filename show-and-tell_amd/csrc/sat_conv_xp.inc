@@ -20,10 +20,6 @@
 //   * 80 KB of LDS and <= 256 registers: two workgroups per CU, one wave of each per SIMD.
 // Arithmetic is that of conv_glds_kernel on the same geometry: the same MFMA, the same K order, the same per-tile column-sum
 // order as its 128-row tiles, the same operand transform expression -- the output tensor is bit-identical.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-
 template <int NK, bool AFF>      // K / 64; AFF: BatchNorm + ReLU of the operand (a template flag keeps the panel's registers in place)
 __global__ __launch_bounds__(256, 2) void conv_xp_kernel(const ConvArgs p_) {
     const ConvArgs p = group_args(p_);
@@ -86,42 +82,22 @@ __global__ __launch_bounds__(256, 2) void conv_xp_kernel(const ConvArgs p_) {
     if constexpr (AFF) conv_in_table<NT>(p, in_tab);
     // the panel has landed and the table is visible
     wait_vmcnt<0>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    lds_barrier();
     if constexpr (AFF) {
         // BatchNorm + ReLU of the panel, ONCE, in LDS, every thread on one 16-byte channel group (logical chunk lc of the K axis)
         // for 128 / RPT rows: its eight (scale, shift) pairs live in registers
         constexpr int LCN = NK * 8, RPT = NT / LCN;      // channel groups; row stride of a thread
         const int lc = tid % LCN, row0 = tid / LCN;
-        const f32x4 s0 = *(const f32x4*)(in_tab + lc * 8), s1 = *(const f32x4*)(in_tab + lc * 8 + 4);
-        const f32x4 t0 = *(const f32x4*)(in_tab + p.Cin + lc * 8), t1 = *(const f32x4*)(in_tab + p.Cin + lc * 8 + 4);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                    // every thread holds its table entries: slot 4 may take weight stage 0
-        asm volatile("" ::: "memory");
+        // (not in_tab_fetch: its shift address, table + lc * 8 + Cin, is summed in another order than this one and costs the kernel an instruction)
+        const InTab tab = {*(const f32x4*)(in_tab + lc * 8), *(const f32x4*)(in_tab + lc * 8 + 4), *(const f32x4*)(in_tab + p.Cin + lc * 8),
+                           *(const f32x4*)(in_tab + p.Cin + lc * 8 + 4)};
+        lds_barrier();      // every thread holds its table entries: slot 4 may take weight stage 0
         if (is_loader) issue_next(4);
         // rows row0 + jr*RPT: for RPT = 8 the swizzle term ((row>>1)&7) alternates between two values, for RPT >= 16 it is
         // constant -- two lane bases and immediate offsets, no per-row address arithmetic
         char* at_e = smem + (lc >> 3) * SLOT + row0 * 128 + (((lc & 7) ^ ((row0 >> 1) & 7)) << 4);
         char* at_o = smem + (lc >> 3) * SLOT + row0 * 128 + (((lc & 7) ^ (((row0 + RPT) >> 1) & 7)) << 4);
-        auto xform = [&](u32x4 w) {
-            // word q = channels (2q, 2q+1): unpack by shift / mask, one packed fma, ONE packed convert (round to nearest even,
-            // what the scalar (bf16_t) cast does), and the ReLU AFTER the rounding on the bf16 pair as int16 (sign bit set
-            // -> 0): rounding is monotonic and keeps the sign, so max(round(x), 0) == round(max(x, 0))
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x2 sc2, sh2, f;
-                sc2[0] = q < 2 ? s0[2 * q] : s1[2 * q - 4]; sc2[1] = q < 2 ? s0[2 * q + 1] : s1[2 * q - 3];
-                sh2[0] = q < 2 ? t0[2 * q] : t1[2 * q - 4]; sh2[1] = q < 2 ? t0[2 * q + 1] : t1[2 * q - 3];
-                f[0] = __uint_as_float(w[q] << 16);
-                f[1] = __uint_as_float(w[q] & 0xffff0000u);
-                f = __builtin_elementwise_fma(f, sc2, sh2);
-                const s16x2 pk = __builtin_bit_cast(s16x2, __builtin_convertvector(f, bf16x2));
-                const s16x2 zero2 = {0, 0};
-                w[q] = __builtin_bit_cast(unsigned int, __builtin_elementwise_max(pk, zero2));
-            }
-            return w;
-        };
+        auto xform = [&](u32x4 w) { return bn_relu_chunk(w, tab); };
         constexpr int NCH = BM / RPT;                    // chunks per thread
         if (full_tile) {                                 // uniform: straight-line code, all the reads in flight at once
             u32x4 w[NCH];
@@ -136,9 +112,7 @@ __global__ __launch_bounds__(256, 2) void conv_xp_kernel(const ConvArgs p_) {
                 if (m0 + row0 + jr * RPT < p.M) *(u32x4*)at = xform(*(const u32x4*)at);      // rows past M stay exact zeros
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        lds_barrier();
     } else {
         if (is_loader) issue_next(4);
     }
@@ -151,18 +125,16 @@ __global__ __launch_bounds__(256, 2) void conv_xp_kernel(const ConvArgs p_) {
         for (int kt = 0; kt < NK; ++kt)
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks)
-                af[i][kt * 4 + ks] = *(const bf16x8*)(smem + kt * SLOT + row * 128 + (((2 * ks + h) ^ ((row >> 1) & 7)) << 4));
+                af[i][kt * 4 + ks] = *(const bf16x8*)(smem + kt * SLOT + frag_off(row, h, ks));
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                        // the panel's slots are free: the ring takes them
-    asm volatile("" ::: "memory");
+    lds_barrier();      // the panel's slots are free: the ring takes them
     if (is_loader && G > 1) issue_next(0);
 
     // B fragment read offsets inside a slot: row*128 + ((chunk ^ ((row>>1)&7)) * 16), chunk = 2*ks + h
     // (row = wn*64 + j*32 + r: (row>>1)&7 = (r>>1)&7 for both j, and j only adds 4096 bytes)
     int b_off[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) b_off[ks] = (wn * 64 + r) * 128 + (((2 * ks + h) ^ ((r >> 1) & 7)) << 4);
+    for (int ks = 0; ks < 4; ++ks) b_off[ks] = wn * 64 * 128 + frag_off(r, h, ks);
 
     f32x16 acc[2][2];
     auto zero_acc = [&]() {
@@ -188,8 +160,7 @@ __global__ __launch_bounds__(256, 2) void conv_xp_kernel(const ConvArgs p_) {
                 if (g + 1 < G) wait_vmcnt<8>();
                 else wait_vmcnt<0>();
             }
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
+            raw_barrier();
             if (is_loader && g + D < G) issue_next(slot + D >= RS ? slot + D - RS : slot + D);
             {
                 const char* st = smem + slot * SLOT;
@@ -215,9 +186,7 @@ __global__ __launch_bounds__(256, 2) void conv_xp_kernel(const ConvArgs p_) {
                 //      idle; cslot+1 / cslot+2 hold the stages in flight ----
                 char* c_half = smem + (wm == 0 ? cslot : (cslot + 4) % RS) * SLOT;
                 float* red = (float*)(smem + ((cslot + 3) % RS) * SLOT);       // [2 (wm)][2][BN]
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();                 // every wave has finished its reads of stage g
-                asm volatile("" ::: "memory");
+                lds_barrier();      // every wave has finished its reads of stage g
                 if (p.stat_partial || p.acc) {
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
@@ -235,8 +204,7 @@ __global__ __launch_bounds__(256, 2) void conv_xp_kernel(const ConvArgs p_) {
                                 q2 = __builtin_elementwise_fma(v, v, q2);
                             }
                         float s = s2[0] + s2[1], q = q2[0] + q2[1];
-                        s += __shfl_xor(s, 32, 64);
-                        q += __shfl_xor(q, 32, 64);
+                        lane_halves(s, q);
                         if (h == 0) {
                             red[(wm * 2 + 0) * BN + wn * 64 + j * 32 + r] = s;
                             red[(wm * 2 + 1) * BN + wn * 64 + j * 32 + r] = q;
@@ -263,9 +231,7 @@ __global__ __launch_bounds__(256, 2) void conv_xp_kernel(const ConvArgs p_) {
                         }
                 }
                 zero_acc();
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
+                lds_barrier();
                 if (!is_loader) {
                     const int t = tid - 128;                 // 0..127
                     const int n0 = nbase + ct * BN;
