@@ -509,6 +509,24 @@ int sat_collate_captions(const int64_t* flat, const int64_t* offsets /*[B+1]*/, 
 int sat_gather_rows_f32(const float* in, const int32_t* order, int rows, int64_t cols, float* out, sat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * On-device image augmentation (added within ABI 18).
+ * main.py:26-36: RandomCrop/CenterCrop + RandomHorizontalFlip + ToTensor + Normalize of B images in one launch.
+ * src   uint8 [Bsrc][Hs][Ws][3]  (HWC, RGB: what PIL / numpy decode to)
+ * params int32 [B][3] = (top, left, flip) per OUTPUT image   [device]
+ * order  int32 [B] or NULL: output image b is made from src image order[b] (NULL: b) -- collate's length sort rides along
+ * out   f32 [B][3][Hc][Wc]  (NCHW, what every encoder entry point takes)
+ * out[b][c][y][x] = ((float)src[order[b]][top+y][left + (flip ? Wc-1-x : x)][c] / 255.0f - mean[c]) / std[c]
+ * evaluated in f32 with correctly rounded divisions, i.e. bit for bit ToTensor().div(255) then sub_(mean).div_(std).
+ * The kernel clamps top into [0, Hs-Hc], left into [0, Ws-Wc] and order[b] into [0, Bsrc): a bad parameter never addresses
+ * memory outside src (a safety net; callers validate on the host).  No allocation, no host sync, capturable.
+ * SAT_ERR_ARG before any launch: src, params, out, mean or std NULL; B, Bsrc, Hc or Wc <= 0; Hc > Hs or Wc > Ws; a std entry
+ * that is 0; a mean or std entry that is not finite.  SAT_ERR_UNSUPPORTED: Hc > 524280 or Wc > 2^28 (the launch grid; int indices inside a row).
+ */
+int sat_image_augment_u8(const uint8_t* src, int Bsrc, int Hs, int Ws, const int32_t* params, const int32_t* order,
+                         int B, int Hc, int Wc, const float mean[3] /*[host]*/, const float std[3] /*[host]*/,
+                         float* out, sat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Beam decode (the reference has only a stub, model2.py:113-114, next to the greedy loop
  * models.py:56-67).  Rows are (image b, hypothesis k) = b*K + k, K <= 8.
  * sat_beam_step: candidates (k, v) score scores_in[b,k] + log_softmax(logits[b*K+k])[v]; the best K of the K*V per

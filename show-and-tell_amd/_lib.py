@@ -149,6 +149,7 @@ SIGNATURES = {
     "sat_lstmcell_bwd_point": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "sat_collate_captions": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "sat_gather_rows_f32": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
+    "sat_image_augment_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp]),
     "sat_beam_step": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sat_beam_step_ws_bytes": (_i64, [_i, _i]),
     "sat_beam_gather_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -177,7 +178,7 @@ SIGNATURES = {
 # or a -DSAT_TESTHOOKS build made before the addition -- need not export them: they are bound where present, and a call through a
 # library that lacks one raises AttributeError (nothing is computed another way).  The library built from this tree exports
 # every one (tests/test_cabi_and_host.py, tests/test_conv_cases_host.py).
-ADDED_WITHIN_ABI = ("sat_conv_resolved_variant",)
+ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8")
 
 _lib = None
 

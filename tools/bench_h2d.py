@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """PCIe-inclusive rate of the training step (never bench.py's `value`): batches start in pinned HOST memory.
 sequential / look-ahead on resident batches, blocking .cuda() per step, sat.DevicePrefetcher (copies on a side stream), and the
-prefetcher at look-ahead depth feeding `next_images` (its upcoming device tensors are announced to the step)."""
+prefetcher at look-ahead depth feeding `next_images` (its upcoming device tensors are announced to the step); then the same two
+prefetcher lines fed with uint8 256x256 HWC host batches that `sat.ImageTransform` crops, flips and normalises on the device."""
 import importlib, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -43,3 +44,17 @@ def pref_la(m):
     for im, cp, ln in pf:
         ts.step(im, cp, ln, next_images=pf.upcoming_images() or None)
 timed("prefetcher depth 3 + look-ahead", pref_la)
+# the same batches as the bytes a decoder hands over: 64 x 256 x 256 x 3 uint8 = 12.6 MB per step instead of 38.5 MB of f32
+host_u8 = [(torch.randint(0, 256, (64, 256, 256, 3), dtype=torch.uint8).pin_memory(), cp, ln) for _, cp, ln in host]
+tf = sat.ImageTransform(224, generator=torch.Generator().manual_seed(123))
+def pref_u8(m):
+    for im, cp, ln in sat.DevicePrefetcher([host_u8[i % 4] for i in range(m)], "cuda", transform=tf):
+        ts.step(im, cp, ln)
+timed("prefetcher, sequential, uint8 256x256 host batches + on-device transform", pref_u8)
+def pref_la_u8(m):
+    pf = sat.DevicePrefetcher([host_u8[i % 4] for i in range(m)], "cuda", depth=depth, transform=tf)
+    for im, cp, ln in pf:
+        ts.step(im, cp, ln, next_images=pf.upcoming_images() or None)
+timed("prefetcher + look-ahead, uint8 256x256 host batches + on-device transform", pref_la_u8)
+timed("prefetcher + look-ahead, f32 host batches (again)", pref_la)
+timed("look-ahead, resident (again)", resident)
