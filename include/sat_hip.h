@@ -458,6 +458,28 @@ int sat_attention_bwd(const float* ctx_enc, const float* feats, const float* pro
                       int64_t ld_dctx2, int rows, int P, int C,
                       float* d_ctx_enc, float* d_proj, float* d_watt_part, float* d_feats /*[rows][P][C] += , or NULL*/,
                       float* workspace, int64_t ws_bytes, sat_stream_t stream);
+/* Doubly stochastic attention (Xu et al. 2015, section 4.2.1; added within ABI 18).  The training forward leaves the packed tape
+ * alpha [N][P] (rows time-major: step t holds images 0 .. prefix[t+1]-prefix[t]-1 at rows prefix[t] ..).
+ * sat_attention_coverage: cov[b][p] = sum over the steps t image b is alive in (b < prefix[t+1] - prefix[t]), ascending t, of
+ *   alpha[prefix[t] + b][p]   (cov nullable);   grad[b][p] = 2 coef (cov[b][p] - 1)   [B][P];
+ *   penalty[0] = coef * sum_b sum_p (cov[b][p] - 1)^2, per-wave partials in the workspace added in index order (no atomics: the
+ *   same input gives the same bits).  prefix: DEVICE int32 [T+1], as for sat_pack_tokens.  Any P >= 1; B <= 65535.  Two launches.
+ * sat_attention_bwd_ex: sat_attention_bwd whose row-dot launch writes
+ *   d_alpha[b][p] = feats[b,p,:] . d_ctx[b,:] / P + d_alpha_scale[0] * d_alpha_extra[b][p]
+ *   d_alpha_extra [rows][ld_extra] (ld_extra >= P); d_alpha_scale: DEVICE pointer to one float (the upstream gradient of the penalty
+ *   inside a backward pass: no host read).  Both NULL: exactly sat_attention_bwd, same kernels, same bits; one NULL: SAT_ERR_ARG.
+ *   Row index = image index within a step, so the grad [B][P] of sat_attention_coverage serves every step (rows = batch_sizes[t]).
+ */
+int64_t sat_attention_coverage_ws_bytes(int B, int P);
+int sat_attention_coverage(const float* alpha /*[N][P]*/, const int32_t* prefix /*device [T+1]*/, int T, int B, int P, float coef,
+                           float* cov /*[B][P] or NULL*/, float* grad /*[B][P]*/, float* penalty /*[1]*/, float* workspace,
+                           int64_t ws_bytes, sat_stream_t stream);
+int sat_attention_bwd_ex(const float* ctx_enc, const float* feats, const float* proj, int64_t ld_proj, const float* w_att,
+                         const float* alpha, const float* d_ctx, int64_t ld_dctx, const float* d_ctx2, int64_t ld_dctx2,
+                         const float* d_alpha_extra /*[rows][ld_extra] or NULL*/, int64_t ld_extra,
+                         const float* d_alpha_scale /*device [1] or NULL*/, int rows, int P, int C,
+                         float* d_ctx_enc, float* d_proj, float* d_watt_part, float* d_feats /*[rows][P][C] += , or NULL*/,
+                         float* workspace, int64_t ws_bytes, sat_stream_t stream);
 int sat_lstmcell_fwd(const float* x /*[B,In]*/, const float* h_in /*[B,H]*/, float* c /*[B,H] in place*/, const float* w_ih,
                      const float* w_hh, const float* b_ih, const float* b_hh, int B, int In, int H, float* h_out,
                      float* gates /*[B,4H] or NULL*/, float* c_tape /*[B,H] or NULL*/, sat_stream_t stream);
@@ -535,6 +557,9 @@ int sat_image_augment_u8(const uint8_t* src, int Bsrc, int Hs, int Ws, const int
  *   only continues with end_id, at unchanged score.
  * sat_beam_gather_rows: dst[b*K+k] = src[b*K+parent[b,k]] (LSTM h/c re-ordering), width floats per row, dst != src.
  * sat_beam_backtrack: parents/tokens [T][B*K] back-pointers -> ids [B*K][T].
+ * sat_beam_backtrack_rows (added within ABI 18): the same walk over a per-step record rows [T][B*K][cols] f32 (the attention maps
+ *   of a beam decode) -> out [B*K][T][cols].  The row of step t was computed before that step's selection, on the slot the
+ *   survivor was expanded from: it is taken at the survivor's PARENT of step t, not at its own slot.  Pure gather, any cols >= 1.
  */
 int sat_beam_step(const float* logits /*[B*K, ldl]*/, int64_t ldl, const float* scores_in /*[B*K]*/,
                   const int64_t* last_tokens /*[B*K] or NULL*/, int64_t end_id, int B, int K, int V,
@@ -545,6 +570,8 @@ int sat_beam_gather_rows(const float* src, const int32_t* parent, int B, int K, 
                          sat_stream_t stream);
 int sat_beam_backtrack(const int32_t* parents, const int64_t* tokens, int T, int B, int K, int64_t* ids,
                        sat_stream_t stream);
+int sat_beam_backtrack_rows(const int32_t* parents, const float* rows, int T, int B, int K, int cols, float* out,
+                            sat_stream_t stream);
 /* The whole decode loop of one batch as ONE call -- the 20 steps of `DecoderRNN.sample` (models.py:56-67; eval.py:99) enqueued from
  * C instead of step by step from the host language (round 4: seven launches per step through the FFI made the beam loop host-bound,
  * 2.44 ms per 20 steps for ~1.3 ms of GPU work).  Same kernels, same order as the step entry points: bit-identical results.

@@ -136,6 +136,10 @@ SIGNATURES = {
     "sat_attention_fwd": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp]),
     "sat_attention_bwd": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sat_attention_ws_bytes": (_i64, [_i, _i]),
+    "sat_attention_coverage_ws_bytes": (_i64, [_i, _i]),
+    "sat_attention_coverage": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sat_attention_bwd_ex": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _vp,
+                                  _vp, _i64, _vp]),
     "sat_bn_running_apply": (_i, [_vp, _i, _f, _vp]),
     "sat_pad_nhwc_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "sat_maxpool2_bwd_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
@@ -154,6 +158,7 @@ SIGNATURES = {
     "sat_beam_step_ws_bytes": (_i64, [_i, _i]),
     "sat_beam_gather_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "sat_beam_backtrack": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "sat_beam_backtrack_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sat_kept_tokens": (_i, [_vp, _i64, _i, _i, _i64, _vp, _vp]),
     "sat_beam_decode_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
     "sat_beam_decode": (_i, [_vp, _vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _i64, _vp]),
@@ -178,7 +183,8 @@ SIGNATURES = {
 # or a -DSAT_TESTHOOKS build made before the addition -- need not export them: they are bound where present, and a call through a
 # library that lacks one raises AttributeError (nothing is computed another way).  The library built from this tree exports
 # every one (tests/test_cabi_and_host.py, tests/test_conv_cases_host.py).
-ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8")
+ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_attention_coverage_ws_bytes", "sat_attention_coverage",
+                    "sat_attention_bwd_ex", "sat_beam_backtrack_rows")
 
 _lib = None
 

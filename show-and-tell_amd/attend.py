@@ -329,9 +329,10 @@ class _AttendFn(torch.autograd.Function):
     """decoder half of model2.py:38-65 given the encoder features (the conv stack is frozen, model2.py:17)."""
 
     @staticmethod
-    def forward(ctx, model, features, fmean, captions, pi, ss, *params):
+    def forward(ctx, model, features, fmean, captions, pi, ss, ex, *params):
         """ss: None (teacher forcing) or dict(prob, seed, rank) -- scheduled sampling through `sat_ss_attend_fwd`; receives
-        "used", the tokens fed [B, T]"""
+        "used", the tokens fed [B, T].  ex: dict(alpha_c) -- receives "alphas", the packed [N, P] attention tape; with
+        alpha_c > 0 the doubly stochastic penalty is a second output (`_attend_outputs`)."""
         lib = L.load()
         m = model
         dev = features.device
@@ -350,8 +351,9 @@ class _AttendFn(torch.autograd.Function):
         X, GATES = torch.empty(N, Hin, device=dev), torch.empty(N, 4 * H, device=dev)
         CS, ALPHA = torch.empty(N, H, device=dev), torch.empty(N, P, device=dev)
         if ss is not None:
-            return _ss_attend_forward(ctx, lib, m, f2, fmean, ctx_enc, h0, c0, HSX, captions, pi, ss,
-                                      dict(PROJ=PROJ, ALPHA=ALPHA, X=X, GATES=GATES, CS=CS, HS=HS))
+            logits = _ss_attend_forward(ctx, lib, m, f2, fmean, ctx_enc, h0, c0, HSX, captions, pi, ss,
+                                        dict(PROJ=PROJ, ALPHA=ALPHA, X=X, GATES=GATES, CS=CS, HS=HS))
+            return _attend_outputs(ctx, lib, ex, logits, V)
         c = c0.clone()
         watt = m.weight_att.view(-1)
         att_ws = torch.empty(B * P, device=dev)
@@ -384,14 +386,39 @@ class _AttendFn(torch.autograd.Function):
         ctx.m, ctx.pi, ctx.captions = m, pi, captions
         ctx.tapes = dict(f2=f2, fmean=fmean, ctx_enc=ctx_enc, h0=h0, c0=c0, PROJ=PROJ, HS=HS, X=X, GATES=GATES, CS=CS, ALPHA=ALPHA,
                          Zin=Zin, Wz=Wz, Z=Z, toks=toks, HSX=HSX)
-        return logits if ldl == V else logits[:, :V]
+        return _attend_outputs(ctx, lib, ex, logits, V)
 
     @staticmethod
-    def backward(ctx, dlogits):
+    def backward(ctx, dlogits, *dpen):
         from .attend_bwd import attend_backward
         want = ctx.needs_input_grad[1]                     # features carry a graph only when the conv stack is fine-tuned
-        grads, d_feats, d_fmean = attend_backward(ctx.m, ctx.pi, ctx.captions, ctx.tapes, dlogits, want_dfeat=want)
-        return (None, d_feats, d_fmean if ctx.needs_input_grad[2] else None, None, None, None) + tuple(grads)
+        extra = scale = None
+        if ctx.cov_grad is not None:
+            # the penalty's incoming gradient stays on the device (autograd hands zeros for an output the loss never used)
+            extra, scale = ctx.cov_grad, dpen[0].to(torch.float32).contiguous()
+        grads, d_feats, d_fmean = attend_backward(ctx.m, ctx.pi, ctx.captions, ctx.tapes, dlogits, want_dfeat=want,
+                                                  d_alpha_extra=extra, d_alpha_scale=scale)
+        return (None, d_feats, d_fmean if ctx.needs_input_grad[2] else None, None, None, None, None) + tuple(grads)
+
+
+def _attend_outputs(ctx, lib, ex, logits, V):
+    """What `_AttendFn.forward` returns, teacher-forced or sampled: the logits, and with ex["alpha_c"] > 0 also the doubly
+    stochastic penalty alpha_c * mean_{b,p} (1 - sum_t alpha[b,t,p])^2 as a 0-dim tensor -- one `sat_attention_coverage` call over
+    the packed tape; its grad [B, P] stays on ctx for the backward."""
+    pi, ALPHA = ctx.pi, ctx.tapes["ALPHA"]
+    ex["alphas"] = ALPHA
+    ctx.cov_grad = None
+    out = logits if logits.shape[1] == V else logits[:, :V]
+    if not ex["alpha_c"] > 0:
+        return out
+    B, P, dev = pi.B, ALPHA.shape[1], ALPHA.device
+    grad, pen = torch.empty(B, P, device=dev), torch.empty((), device=dev)
+    wsb = lib.sat_attention_coverage_ws_bytes(B, P)
+    ws = torch.empty(wsb // 4, device=dev)
+    L.check(lib.sat_attention_coverage(ALPHA.data_ptr(), pi.prefix_dev.data_ptr(), pi.T, B, P, float(ex["alpha_c"]) / (B * P), None,
+                                       grad.data_ptr(), pen.data_ptr(), ws.data_ptr(), wsb, L.stream()), "sat_attention_coverage")
+    ctx.cov_grad = grad
+    return out, pen
 
 
 _SS_WEIGHTS = ("weight_hh.weight", "weight_hh.bias", "weight_att", "embedding.weight", "lstmcell.weight_ih", "lstmcell.weight_hh",
@@ -427,7 +454,7 @@ def _ss_attend_forward(ctx, lib, m, f2, fmean, ctx_enc, h0, c0, HSX, captions, p
     ss["used"] = used
     ctx.m, ctx.pi, ctx.captions = m, pi, captions
     ctx.tapes = dict(f2=f2, fmean=fmean, ctx_enc=ctx_enc, h0=h0, c0=c0, Wz=Wz, toks=toks, HSX=HSX, **tp)
-    return logits if ldl == V else logits[:, :V]
+    return logits
 
 
 class _VggFn(torch.autograd.Function):
@@ -488,6 +515,8 @@ class ShowAttendTellModel(nn.Module):
         self.ss_prob = 0                  # scheduled sampling (train.py:109-113; schedule: trainer.ss_prob_for_epoch), training mode only
         self.ss_rank = 0                  # data-parallel rank: a stream of draws of its own per rank
         self.last_ss_inputs = self.last_ss_seed = None   # tokens fed [B, T] and seed of the last sampled forward
+        self.alpha_c = 0                  # weight of the doubly stochastic attention penalty (Xu et al. 2015, section 4.2.1); 0 = off
+        self.last_alphas = self.last_attention_penalty = None    # set by every decode / forward
         self._programs, self._guard = {}, None
         self._pf_list = []          # features in flight: [(images, feats, fmean, event, weights signature, instance)]
         self.register_load_state_dict_post_hook(lambda mod, k: mod._programs.clear())
@@ -598,7 +627,13 @@ class ShowAttendTellModel(nn.Module):
     def decode(self, features, fmean, captions, lengths):
         """The decoder half of `forward`.  In training mode with ss_prob > 0 the embedding half of the input of step t >= 1 is,
         with probability ss_prob, a token drawn from softmax(logits of step t-1) (scheduled sampling; seed drawn from torch's CPU
-        generator); the tokens fed and the seed are kept as `last_ss_inputs` / `last_ss_seed`."""
+        generator); the tokens fed and the seed are kept as `last_ss_inputs` / `last_ss_seed`.
+
+        Every call leaves `last_alphas`, the attention maps as the packed [N, P] tape (detached, no copy; row n belongs to the
+        logits' row n).  With `alpha_c > 0` it also leaves `last_attention_penalty`, a 0-dim tensor WITH a graph equal to
+        alpha_c * mean_{b,p} (1 - sum_t alpha[b,t,p])^2 (doubly stochastic attention), None otherwise; a training loop adds it:
+        `loss = criterion(out, targets) + model.last_attention_penalty`.  The mean is over this call's B images: under data
+        parallelism B is the rank's own batch."""
         L.require_gpu(captions, "captions")
         if len(lengths) != features.shape[0]:
             raise ValueError("len(lengths) != batch size")
@@ -614,20 +649,29 @@ class ShowAttendTellModel(nn.Module):
         if self.training and self.ss_prob > 0:
             from .models import draw_ss_seed
             ss = dict(prob=float(self.ss_prob), seed=draw_ss_seed(), rank=int(self.ss_rank))
-        out = _AttendFn.apply(self, features, fmean, captions, pi, ss, *self._params())
+        ex = dict(alpha_c=float(self.alpha_c))
+        out = _AttendFn.apply(self, features, fmean, captions, pi, ss, ex, *self._params())
+        self.last_attention_penalty = None
+        if ex["alpha_c"] > 0:
+            out, self.last_attention_penalty = out
+        self.last_alphas = ex.get("alphas")
         if ss is not None:
             self.last_ss_inputs, self.last_ss_seed = ss["used"], ss["seed"]
         return out
 
     @torch.no_grad()
-    def sample(self, images, states=None):
+    def sample(self, images, states=None, return_alphas=False):
         """Greedy search, 20 steps (model2.py:91-111; torch-0.1 keepdim semantics): i64 [B,20].  `states`: None = zeros (what
-        eval.py:82-83 passes), a (h, c) pair of [B,H] tensors, or eval.py:89's stacked [2,B,H] tensor."""
+        eval.py:82-83 passes), a (h, c) pair of [B,H] tensors, or eval.py:89's stacked [2,B,H] tensor.  return_alphas: also the
+        attention maps f32 [B, 20, P] -- where the model looked for each word."""
         feats, _ = self._encode(images)
+        if return_alphas:
+            ids, alphas = self.sample_features(feats, states, return_alphas=True)
+            return ids.squeeze(), alphas
         return self.sample_features(feats, states).squeeze()      # model2.py:111: [20] at batch 1
 
     @torch.no_grad()
-    def sample_features(self, features, states=None, steps=20, start_id=1):
+    def sample_features(self, features, states=None, steps=20, start_id=1, return_alphas=False):
         lib = L.load()
         m, dev, st = self, features.device, L.stream()
         B, P, C = features.shape
@@ -654,9 +698,11 @@ class ShowAttendTellModel(nn.Module):
         ws = torch.empty(wsb // 4, device=dev)
         watt = m.weight_att.view(-1)
         att_ws = torch.empty(B * P, device=dev)
+        amaps = torch.empty(steps, B, P, device=dev) if return_alphas else None       # step i's maps: the kernel's alpha output
         for i in range(steps):
             _gemm(lib, 0, 0, h, H, m.weight_hh.weight, H, proj, C, B, C, H, m.weight_hh.bias)
-            L.check(lib.sat_attention_fwd(L.ptr(ctx_enc), L.ptr(f2), L.ptr(proj), C, L.ptr(watt), B, P, C, None, L.ptr(ctxb), C,
+            L.check(lib.sat_attention_fwd(L.ptr(ctx_enc), L.ptr(f2), L.ptr(proj), C, L.ptr(watt), B, P, C,
+                                          amaps[i].data_ptr() if return_alphas else None, L.ptr(ctxb), C,
                                           att_ws.data_ptr(), att_ws.numel() * 4, st), "sat_attention_fwd")
             if i == 0:                                                               # model2.py:101-102
                 L.check(lib.sat_rows_copy(L.ptr(m.embedding.weight), E, start.data_ptr(), 1, V, B, E, L.ptr(X), Hin, st), "sat_rows_copy")
@@ -674,16 +720,22 @@ class ShowAttendTellModel(nn.Module):
             # model2.py:107-108: the NEXT LSTM input = [embedding(predicted), THIS step's context]
             L.check(lib.sat_rows_copy(L.ptr(m.embedding.weight), E, col.data_ptr(), ids.stride(0), V, B, E, L.ptr(X), Hin, st), "sat_rows_copy")
             L.check(lib.sat_rows_copy(L.ptr(ctxb), C, None, 0, B, B, C, X.data_ptr() + E * 4, Hin, st), "sat_rows_copy")
+        if return_alphas:
+            return ids, amaps.transpose(0, 1).contiguous()
         return ids
 
 
 @torch.no_grad()
-def _sample_beam_features(self, features, beam_size=5, states=None, end_id=None, steps=20, start_id=1, return_all=False):
+def _sample_beam_features(self, features, beam_size=5, states=None, end_id=None, steps=20, start_id=1, return_all=False,
+                          return_alphas=False):
     """Beam search over `sample`'s loop (model2.py:91-111; the reference's `sample_beam` is a stub, model2.py:113-114, so parity
     is pinned only at beam_size=1 == the greedy goldens).  Rows are (image b, hypothesis k) = b*K + k: the features and their
     attention encoding are replicated per hypothesis once (data movement), every step runs the greedy step's kernels on B*K rows,
     `sat_beam_step` keeps the best K of the K*V candidates per image, and h, c and the carried context follow their parent
-    (`sat_beam_gather_rows`).  Returns ids i64 [B,steps] of the best hypothesis (return_all: ids [B,K,steps] best-first, scores)."""
+    (`sat_beam_gather_rows`).  Returns ids i64 [B,steps] of the best hypothesis (return_all: ids [B,K,steps] best-first, scores).
+    return_alphas: the attention maps follow as the last value -- [B,steps,P] of the best hypothesis, with return_all [B,K,steps,P]
+    best-first.  Every step's maps are recorded per slot and `sat_beam_backtrack_rows` follows the parent chain: the map of a
+    step belongs to the slot its survivor was expanded from."""
     lib = L.load()
     m, dev, st = self, features.device, L.stream()
     B, P, C = features.shape
@@ -719,10 +771,12 @@ def _sample_beam_features(self, features, beam_size=5, states=None, end_id=None,
     start = torch.full((R,), int(start_id), dtype=torch.int64, device=dev)
     watt = m.weight_att.view(-1)
     att_ws = torch.empty(R * P, device=dev)
+    amaps = torch.empty(steps, R, P, device=dev) if return_alphas else None
     eid = -1 if end_id is None else int(end_id)
     for i in range(steps):
         _gemm(lib, 0, 0, h, H, m.weight_hh.weight, H, proj, C, R, C, H, m.weight_hh.bias)
-        L.check(lib.sat_attention_fwd(L.ptr(ctx_enc), L.ptr(f2), L.ptr(proj), C, L.ptr(watt), R, P, C, None, L.ptr(ctxb), C,
+        L.check(lib.sat_attention_fwd(L.ptr(ctx_enc), L.ptr(f2), L.ptr(proj), C, L.ptr(watt), R, P, C,
+                                      amaps[i].data_ptr() if return_alphas else None, L.ptr(ctxb), C,
                                       att_ws.data_ptr(), att_ws.numel() * 4, st), "sat_attention_fwd")
         if i == 0:                                                                   # model2.py:101-102
             L.check(lib.sat_rows_copy(L.ptr(m.embedding.weight), E, start.data_ptr(), 1, V, R, E, L.ptr(X), Hin, st), "sat_rows_copy")
@@ -752,16 +806,22 @@ def _sample_beam_features(self, features, beam_size=5, states=None, end_id=None,
         L.check(lib.sat_rows_copy(L.ptr(src_ctx), C, None, 0, R, R, C, X.data_ptr() + E * 4, Hin, st), "sat_rows_copy")
     ids = torch.empty(B, K, steps, dtype=torch.int64, device=dev)
     L.check(lib.sat_beam_backtrack(L.ptr(parents), L.ptr(tokens), steps, B, K, L.ptr(ids), st), "sat_beam_backtrack")
+    if return_alphas:
+        alphas = torch.empty(B, K, steps, P, device=dev)
+        L.check(lib.sat_beam_backtrack_rows(L.ptr(parents), L.ptr(amaps), steps, B, K, P, L.ptr(alphas), st), "sat_beam_backtrack_rows")
+        if return_all:
+            return ids, scores, alphas
+        return ids[:, 0].contiguous(), alphas[:, 0].contiguous()
     if return_all:
         return ids, scores
     return ids[:, 0].contiguous()
 
 
 @torch.no_grad()
-def _sample_beam(self, images, beam_size=5, states=None, end_id=None, return_all=False):
+def _sample_beam(self, images, beam_size=5, states=None, end_id=None, return_all=False, return_alphas=False):
     """`sample_beam(images, ...)`: the method the reference leaves as a stub (model2.py:113-114); BASELINE configs[4] asks beam 5."""
     feats, _ = self._encode(images)
-    return self.sample_beam_features(feats, beam_size, states, end_id, return_all=return_all)
+    return self.sample_beam_features(feats, beam_size, states, end_id, return_all=return_all, return_alphas=return_alphas)
 
 
 ShowAttendTellModel.sample_beam_features = _sample_beam_features

@@ -1,6 +1,8 @@
 """Backward of the Show-Attend-Tell decoder (`loss.backward()`, train.py:144, through model2.py:38-85), hand-written on
 the forward's tapes: batched MFMA GEMMs for every weight gradient, one `sat_attention_bwd` + one `sat_lstmcell_bwd_point`
-per packed step for the recurrence (BPTT).  The conv stack is frozen (model2.py:17): no gradient flows into it."""
+per packed step for the recurrence (BPTT).  The conv stack is frozen (model2.py:17): no gradient flows into it.  With the
+doubly stochastic penalty (`model.alpha_c > 0`) the step's call is `sat_attention_bwd_ex`, which adds the penalty's gradient to
+d_alpha on the device."""
 import torch
 
 from . import _lib as L
@@ -11,9 +13,10 @@ def _rows(t, r0):
     return t.data_ptr() + r0 * t.shape[1] * 4
 
 
-def attend_backward(m, pi, captions, tp, dlogits, want_dfeat=False):
+def attend_backward(m, pi, captions, tp, dlogits, want_dfeat=False, d_alpha_extra=None, d_alpha_scale=None):
     """Returns (gradients in `attend.PARAM_ORDER`, d_features [B,P,C] or None, d_fmean [B,C] or None); the last two only when
-    the conv stack is being fine-tuned (model2.py:87-89)."""
+    the conv stack is being fine-tuned (model2.py:87-89).  d_alpha_extra [B,P] / d_alpha_scale (device scalar): a second consumer
+    of the attention maps (the coverage penalty) -- every step's d_alpha gains d_alpha_scale * d_alpha_extra[b] for its rows b."""
     lib, st = L.load(), L.stream()
     dev = dlogits.device
     f2, fmean, ctx_enc = tp["f2"], tp["fmean"], tp["ctx_enc"]
@@ -65,10 +68,17 @@ def attend_backward(m, pi, captions, tp, dlogits, want_dfeat=False):
         _gemm(lib, 0, 1, _rows(DG, r0), 4 * H, m.lstmcell.weight_ih, Hin, _rows(DX, r0), Hin, bs, Hin, 4 * H)   # d[emb | ctx]
         # d context = its LSTMCell-input half + its output_layer half (summed where the attention backward reads it); the
         # projection weight_hh(h_{t-1}) comes from the forward's tape
-        L.check(lib.sat_attention_bwd(ctx_enc.data_ptr(), f2.data_ptr(), _rows(PROJ, r0), C, watt.data_ptr(), _rows(ALPHA, r0),
-                                      _rows(DX, r0) + E * 4, Hin, _rows(dZin, r0), C + H, bs, P, C, d_ctx_enc.data_ptr(),
-                                      _rows(DPROJ, r0), _rows(DWATT, r0), d_feats.data_ptr() if d_feats is not None else None,
-                                      att_ws.data_ptr(), att_ws.numel() * 4, st), "sat_attention_bwd")
+        if d_alpha_extra is None:
+            L.check(lib.sat_attention_bwd(ctx_enc.data_ptr(), f2.data_ptr(), _rows(PROJ, r0), C, watt.data_ptr(), _rows(ALPHA, r0),
+                                          _rows(DX, r0) + E * 4, Hin, _rows(dZin, r0), C + H, bs, P, C, d_ctx_enc.data_ptr(),
+                                          _rows(DPROJ, r0), _rows(DWATT, r0), d_feats.data_ptr() if d_feats is not None else None,
+                                          att_ws.data_ptr(), att_ws.numel() * 4, st), "sat_attention_bwd")
+        else:                                              # row index = image index: the same [B, P] serves every step
+            L.check(lib.sat_attention_bwd_ex(ctx_enc.data_ptr(), f2.data_ptr(), _rows(PROJ, r0), C, watt.data_ptr(), _rows(ALPHA, r0),
+                                             _rows(DX, r0) + E * 4, Hin, _rows(dZin, r0), C + H, d_alpha_extra.data_ptr(), P,
+                                             d_alpha_scale.data_ptr(), bs, P, C, d_ctx_enc.data_ptr(), _rows(DPROJ, r0),
+                                             _rows(DWATT, r0), d_feats.data_ptr() if d_feats is not None else None,
+                                             att_ws.data_ptr(), att_ws.numel() * 4, st), "sat_attention_bwd_ex")
         # dh_{t-1} = DG_t W_hh (through the LSTMCell) + DPROJ_t W_whh (through the attention projection): one launch
         L.check(lib.sat_skinny_gemm2_f32(_rows(DG, r0), 4 * H, m.lstmcell.weight_hh.data_ptr(), H, 4 * H,
                                          _rows(DPROJ, r0), C, m.weight_hh.weight.data_ptr(), H, C, 1, bs, H, None,

@@ -39,11 +39,14 @@ constexpr int kAttWaves = 8;
 
 // TANH = true: v[p] = sum_c tanh(x[b,p,c] + add[b,c]) * mul[c]      (scores)
 // TANH = false: v[p] = scale * sum_c x[b,p,c] * mul_row[b,c]         (d_alpha = feats . d_ctx / P)
-template <bool TANH>
+// EXTRA: v[p] += extra_scale[0] * extra[b,p]: a second consumer of alpha (the coverage penalty of sat_attention_coverage) adds its
+// gradient here, scaled by a DEVICE scalar (the penalty's upstream gradient); without it the expression is the one above, untouched
+template <bool TANH, bool EXTRA>
 __global__ __launch_bounds__(256) void att_rowdot_kernel(const float* __restrict__ x, const float* __restrict__ add, long ld_add,
                                                          const float* __restrict__ mul, long ld_mul,
                                                          const float* __restrict__ mul2, long ld_mul2, float scale, int P, int C,
-                                                         int pchunk, float* __restrict__ out) {
+                                                         int pchunk, const float* __restrict__ extra, long ld_extra,
+                                                         const float* __restrict__ extra_scale, float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float sm[];      // [C] add | [C] mul
     float* s_add = sm;
     float* s_mul = sm + C;
@@ -64,7 +67,11 @@ __global__ __launch_bounds__(256) void att_rowdot_kernel(const float* __restrict
             for (int e = 0; e < 4; ++e) acc += TANH ? tanhf(v[e] + s_add[c + e]) * s_mul[c + e] : v[e] * s_mul[c + e];
         }
         acc = wave_sum(acc);
-        if (lane == 0) out[(long)b * P + p] = acc * scale;
+        if (EXTRA) {
+            if (lane == 0) out[(long)b * P + p] = acc * scale + extra_scale[0] * extra[(long)b * ld_extra + p];
+        } else {
+            if (lane == 0) out[(long)b * P + p] = acc * scale;
+        }
     }
 }
 
@@ -111,7 +118,7 @@ __global__ __launch_bounds__(kAttWaves * 64) void att_context_kernel(const float
 }
 
 // Backward of the step for one (row, 64-channel chunk) (h_att recomputed, never stored):
-//   d_alpha[p] = (1/P) feats[b,p,:] . d_ctx[b,:]                    (att_rowdot_kernel<false>, in `d_alpha`)
+//   d_alpha[p] = (1/P) feats[b,p,:] . d_ctx[b,:]                    (att_rowdot_kernel<false, .>, in `d_alpha`)
 //   d_s[p]     = alpha[p] * (d_alpha[p] - sum_q alpha[q] d_alpha[q])
 //   d_pre[p,c] = d_s[p] * w_att[c] * (1 - h_att[p,c]^2)        -> d_ctx_enc[b,p,c] += d_pre   (accumulated over steps)
 //   d_proj[b,c] = sum_p d_pre[p,c];   d_w_att partial[b,c] = sum_p d_s[p] * h_att[p,c]
@@ -176,6 +183,37 @@ __global__ __launch_bounds__(kAttWaves * 64) void att_bwd_channel_kernel(const f
         d_proj[(long)b * C + c] = rp;
         d_watt_part[(long)b * C + c] = rw;
     }
+}
+
+// Coverage of the packed attention tape (doubly stochastic attention, Xu et al. 2015 section 4.2.1): one lane per (image b,
+// position p), one wave per workgroup, grid (ceil(P/64), B).  A lane adds its column over the steps its image is alive in, in
+// ascending t (loads coalesced along p, independent of each other), and the wave leaves sum_p (cov - 1)^2 of its 64 positions in
+// the workspace (butterfly: a fixed order).  cov_final_kernel adds the partials in index order.  No atomics.
+__global__ __launch_bounds__(64) void cov_kernel(const float* __restrict__ alpha, const int* __restrict__ prefix, int T, int P,
+                                                 float coef2, float* __restrict__ cov, float* __restrict__ grad,
+                                                 float* __restrict__ part) {
+    const int b = blockIdx.y, p = blockIdx.x * 64 + threadIdx.x;
+    float sq = 0.0f;
+    if (p < P) {
+        float acc = 0.0f;
+        for (int t = 0; t < T; ++t) {
+            const int r0 = prefix[t];
+            if (b < prefix[t + 1] - r0) acc += alpha[(long)(r0 + b) * P + p];
+        }
+        const float d = acc - 1.0f;
+        if (cov) cov[(long)b * P + p] = acc;
+        grad[(long)b * P + p] = coef2 * d;
+        sq = d * d;
+    }
+    sq = wave_sum(sq);
+    if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = sq;
+}
+__global__ __launch_bounds__(256) void cov_final_kernel(const float* __restrict__ part, int n, float coef, float* __restrict__ penalty) {
+    __shared__ float sh[4];
+    float acc = 0.0f;
+    for (int i = threadIdx.x; i < n; i += 256) acc += part[i];
+    acc = block_sum(acc, sh);
+    if (threadIdx.x == 0) penalty[0] = coef * acc;
 }
 
 // 2x2 / stride 2 max-pool, NHWC, 16 B per lane
@@ -575,11 +613,43 @@ extern "C" int sat_attention_fwd(const float* ctx_enc, const float* feats, const
     if (lds1 > 60 * 1024 || lds2 > 60 * 1024) return SAT_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const int pch = att_pchunk(rows, P);
-    hipLaunchKernelGGL(att_rowdot_kernel<true>, dim3(rows, sat_cdiv(P, pch)), dim3(256), lds1, s, ctx_enc, proj, (long)ld_proj, w_att,
-                       0L, (const float*)nullptr, 0L, 1.0f, P, C, pch, workspace);
+    hipLaunchKernelGGL((att_rowdot_kernel<true, false>), dim3(rows, sat_cdiv(P, pch)), dim3(256), lds1, s, ctx_enc, proj, (long)ld_proj,
+                       w_att, 0L, (const float*)nullptr, 0L, 1.0f, P, C, pch, (const float*)nullptr, 0L, (const float*)nullptr, workspace);
     SAT_LAUNCH_CHECK();
     hipLaunchKernelGGL(att_context_kernel, dim3(rows, sat_cdiv(C, 64)), dim3(kAttWaves * 64), lds2, s, workspace, feats, P, C, alpha,
                        context, (long)ld_ctx);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
+// sat_attention_bwd and sat_attention_bwd_ex: the same two launches; with d_alpha_extra the row-dot launch is the EXTRA instantiation
+static int att_bwd_launch(const float* ctx_enc, const float* feats, const float* proj, int64_t ld_proj, const float* w_att,
+                          const float* alpha, const float* d_ctx, int64_t ld_dctx, const float* d_ctx2, int64_t ld_dctx2,
+                          const float* d_alpha_extra, int64_t ld_extra, const float* d_alpha_scale, int rows, int P, int C,
+                          float* d_ctx_enc, float* d_proj, float* d_watt_part, float* d_feats, float* workspace, int64_t ws_bytes,
+                          sat_stream_t stream) {
+    if (!ctx_enc || !feats || !proj || !w_att || !alpha || !d_ctx || !d_ctx_enc || !d_proj || !d_watt_part || rows < 1 || P < 1 ||
+        C < 4 || (C & 3) || ld_proj < C || ld_dctx < C || (d_ctx2 && ld_dctx2 < C))
+        return SAT_ERR_ARG;
+    if ((d_alpha_extra == nullptr) != (d_alpha_scale == nullptr) || (d_alpha_extra && ld_extra < P)) return SAT_ERR_ARG;
+    if (!workspace || ws_bytes < sat_attention_ws_bytes(rows, P)) return SAT_ERR_WORKSPACE;
+    const size_t lds1 = (size_t)2 * C * sizeof(float);
+    const size_t lds2 = (size_t)(2 * ((P + 3) & ~3) + 8 + 2 * kAttWaves * 64) * sizeof(float);
+    if (lds1 > 60 * 1024 || lds2 > 60 * 1024) return SAT_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    const int pch = att_pchunk(rows, P);
+    if (d_alpha_extra)
+        hipLaunchKernelGGL((att_rowdot_kernel<false, true>), dim3(rows, sat_cdiv(P, pch)), dim3(256), lds1, s, feats,
+                           (const float*)nullptr, 0L, d_ctx, (long)ld_dctx, d_ctx2, (long)ld_dctx2, 1.0f / (float)P, P, C, pch,
+                           d_alpha_extra, (long)ld_extra, d_alpha_scale, workspace);
+    else
+        hipLaunchKernelGGL((att_rowdot_kernel<false, false>), dim3(rows, sat_cdiv(P, pch)), dim3(256), lds1, s, feats,
+                           (const float*)nullptr, 0L, d_ctx, (long)ld_dctx, d_ctx2, (long)ld_dctx2, 1.0f / (float)P, P, C, pch,
+                           (const float*)nullptr, 0L, (const float*)nullptr, workspace);
+    SAT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(att_bwd_channel_kernel, dim3(rows, sat_cdiv(C, 64)), dim3(kAttWaves * 64), lds2, s, ctx_enc, proj, (long)ld_proj,
+                       w_att, alpha, workspace, d_ctx, (long)ld_dctx, d_ctx2, (long)ld_dctx2, P, C, d_ctx_enc, d_proj, d_watt_part,
+                       d_feats);
     SAT_LAUNCH_CHECK();
     return SAT_OK;
 }
@@ -588,21 +658,32 @@ extern "C" int sat_attention_bwd(const float* ctx_enc, const float* feats, const
                                  const float* alpha, const float* d_ctx, int64_t ld_dctx, const float* d_ctx2, int64_t ld_dctx2,
                                  int rows, int P, int C, float* d_ctx_enc, float* d_proj, float* d_watt_part, float* d_feats,
                                  float* workspace, int64_t ws_bytes, sat_stream_t stream) {
-    if (!ctx_enc || !feats || !proj || !w_att || !alpha || !d_ctx || !d_ctx_enc || !d_proj || !d_watt_part || rows < 1 || P < 1 ||
-        C < 4 || (C & 3) || ld_proj < C || ld_dctx < C || (d_ctx2 && ld_dctx2 < C))
-        return SAT_ERR_ARG;
-    if (!workspace || ws_bytes < sat_attention_ws_bytes(rows, P)) return SAT_ERR_WORKSPACE;
-    const size_t lds1 = (size_t)2 * C * sizeof(float);
-    const size_t lds2 = (size_t)(2 * ((P + 3) & ~3) + 8 + 2 * kAttWaves * 64) * sizeof(float);
-    if (lds1 > 60 * 1024 || lds2 > 60 * 1024) return SAT_ERR_UNSUPPORTED;
+    return att_bwd_launch(ctx_enc, feats, proj, ld_proj, w_att, alpha, d_ctx, ld_dctx, d_ctx2, ld_dctx2, nullptr, 0, nullptr, rows, P, C,
+                          d_ctx_enc, d_proj, d_watt_part, d_feats, workspace, ws_bytes, stream);
+}
+
+extern "C" int sat_attention_bwd_ex(const float* ctx_enc, const float* feats, const float* proj, int64_t ld_proj, const float* w_att,
+                                    const float* alpha, const float* d_ctx, int64_t ld_dctx, const float* d_ctx2, int64_t ld_dctx2,
+                                    const float* d_alpha_extra, int64_t ld_extra, const float* d_alpha_scale, int rows, int P, int C,
+                                    float* d_ctx_enc, float* d_proj, float* d_watt_part, float* d_feats, float* workspace,
+                                    int64_t ws_bytes, sat_stream_t stream) {
+    return att_bwd_launch(ctx_enc, feats, proj, ld_proj, w_att, alpha, d_ctx, ld_dctx, d_ctx2, ld_dctx2, d_alpha_extra, ld_extra,
+                          d_alpha_scale, rows, P, C, d_ctx_enc, d_proj, d_watt_part, d_feats, workspace, ws_bytes, stream);
+}
+
+extern "C" int64_t sat_attention_coverage_ws_bytes(int B, int P) {
+    return B < 1 || P < 1 ? 0 : (int64_t)B * sat_cdiv(P, 64) * (int64_t)sizeof(float);
+}
+
+extern "C" int sat_attention_coverage(const float* alpha, const int32_t* prefix, int T, int B, int P, float coef, float* cov,
+                                      float* grad, float* penalty, float* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    if (!alpha || !prefix || !grad || !penalty || T < 1 || B < 1 || B > 65535 || P < 1) return SAT_ERR_ARG;
+    if (!workspace || ws_bytes < sat_attention_coverage_ws_bytes(B, P)) return SAT_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int pch = att_pchunk(rows, P);
-    hipLaunchKernelGGL(att_rowdot_kernel<false>, dim3(rows, sat_cdiv(P, pch)), dim3(256), lds1, s, feats, (const float*)nullptr, 0L,
-                       d_ctx, (long)ld_dctx, d_ctx2, (long)ld_dctx2, 1.0f / (float)P, P, C, pch, workspace);
+    const int chunks = sat_cdiv(P, 64);
+    hipLaunchKernelGGL(cov_kernel, dim3(chunks, B), dim3(64), 0, s, alpha, prefix, T, P, 2.0f * coef, cov, grad, workspace);
     SAT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(att_bwd_channel_kernel, dim3(rows, sat_cdiv(C, 64)), dim3(kAttWaves * 64), lds2, s, ctx_enc, proj, (long)ld_proj,
-                       w_att, alpha, workspace, d_ctx, (long)ld_dctx, d_ctx2, (long)ld_dctx2, P, C, d_ctx_enc, d_proj, d_watt_part,
-                       d_feats);
+    hipLaunchKernelGGL(cov_final_kernel, dim3(1), dim3(256), 0, s, workspace, B * chunks, coef, penalty);
     SAT_LAUNCH_CHECK();
     return SAT_OK;
 }

@@ -421,6 +421,23 @@ __global__ __launch_bounds__(256) void beam_backtrack_kernel(const int* __restri
     }
 }
 
+// The walk of beam_backtrack_kernel over a per-step record of f32 rows (the attention maps of a beam decode): one workgroup per
+// final hypothesis (b, k).  The row of step t was computed BEFORE that step's selection, on the slot the survivor was expanded
+// from, so it is read at the survivor's PARENT of step t -- which is also the slot the walk visits next.  Pure gather.
+__global__ __launch_bounds__(64) void beam_backtrack_rows_kernel(const int* __restrict__ parents, const float* __restrict__ rows,
+                                                                 int T, int BK, int K, int cols, float* __restrict__ out) {
+    const int row = blockIdx.x;
+    const int b = row / K;
+    int cur = row - b * K;
+    for (int t = T - 1; t >= 0; --t) {
+        cur = parents[(long)t * BK + b * K + cur];
+        cur = cur < 0 ? 0 : (cur >= K ? K - 1 : cur);                 // memory safety only: sat_beam_step writes 0..K-1
+        const float* src = rows + ((long)t * BK + b * K + cur) * cols;
+        float* dst = out + ((long)row * T + t) * cols;
+        for (int c = threadIdx.x; c < cols; c += 64) dst[c] = src[c];
+    }
+}
+
 // eval.py:103-109: the id -> word loop of `evaluation` stops at the first '<end>'.  One thread per caption row: the number of
 // ids in front of the first end_id (T when there is none) -- the host then reads ids[b][:kept[b]] only.
 __global__ __launch_bounds__(256) void kept_tokens_kernel(const int64_t* __restrict__ ids, long stride, int B, int T, int64_t end_id,
@@ -666,6 +683,15 @@ extern "C" int sat_beam_backtrack(const int32_t* parents, const int64_t* tokens,
     if (T <= 0 || B <= 0 || K <= 0) return SAT_ERR_ARG;
     hipLaunchKernelGGL(beam_backtrack_kernel, dim3(sat_cdiv((long)B * K, 256)), dim3(256), 0, (hipStream_t)stream, parents,
                        tokens, T, B * K, K, ids);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
+extern "C" int sat_beam_backtrack_rows(const int32_t* parents, const float* rows, int T, int B, int K, int cols, float* out,
+                                       sat_stream_t stream) {
+    if (!parents || !rows || !out || rows == out) return SAT_ERR_ARG;
+    if (T <= 0 || B <= 0 || K <= 0 || cols <= 0) return SAT_ERR_ARG;
+    hipLaunchKernelGGL(beam_backtrack_rows_kernel, dim3(B * K), dim3(64), 0, (hipStream_t)stream, parents, rows, T, B * K, K, cols, out);
     SAT_LAUNCH_CHECK();
     return SAT_OK;
 }

@@ -2,10 +2,11 @@
 """Throughput of the Show-Attend-Tell path (model2.py, the model train.py:37 constructs) on one MI355X: training step
 (VGG16 features[:-3] frozen + attention decoder fwd + CE + hand-written backward + clamp + torch Adam, train.py:134-146) and
 greedy sampling (eval.py:99), batch 64, 224x224, hidden 1024 / embed 512 (config.py:27-28 defaults), vocab 10000, len-20 captions.
-    python tools/bench_attend.py [bf16|f32] [--ss-prob P] [--ab REGIONS] [--forwards N]
---ss-prob: scheduled sampling (model.ss_prob) in the training step.  --ab REGIONS: only the training step, ss_prob 0 and P
-interleaved (order alternating per region, 10 steps each), per-region times and medians.  --forwards N: only N sampled decoder
-forwards on fixed features (for a kernel trace)."""
+    python tools/bench_attend.py [bf16|f32] [--ss-prob P] [--alpha-c A] [--ab REGIONS] [--forwards N]
+--ss-prob: scheduled sampling (model.ss_prob) in the training step.  --alpha-c: doubly stochastic attention (model.alpha_c; the
+step's loss is CE + model.last_attention_penalty).  --ab REGIONS: only the training step, two settings interleaved (order
+alternating per region, 10 steps each), per-region times, medians and spread: alpha_c 0 against A when --alpha-c is given (ss_prob
+fixed at P), else ss_prob 0 against P.  --forwards N: only N sampled decoder forwards on fixed features (for a kernel trace)."""
 import argparse
 import importlib
 import os
@@ -20,6 +21,7 @@ sat = importlib.import_module("show-and-tell_amd")
 ap = argparse.ArgumentParser()
 ap.add_argument("dtype", nargs="?", default="bf16", choices=["bf16", "f32"])
 ap.add_argument("--ss-prob", type=float, default=0.0)
+ap.add_argument("--alpha-c", type=float, default=0.0)
 ap.add_argument("--ab", type=int, default=0)
 ap.add_argument("--forwards", type=int, default=0)
 args = ap.parse_args()
@@ -57,6 +59,8 @@ def step(i=0, last=True):
     if LOOKAHEAD and not last:
         model.prefetch_features(batches[(i + 1) & 1])
     loss = crit(model.decode(feats, fmean, caps[:, :-1], l1), targets)
+    if model.last_attention_penalty is not None:
+        loss = loss + model.last_attention_penalty
     loss.backward()
     if not FUSED_OPT:
         for p in opt.param_groups[0]["params"]:
@@ -84,30 +88,36 @@ if args.forwards:
     print("%d decoder forwards, ss_prob %g" % (args.forwards, args.ss_prob))
     sys.exit(0)
 if args.ab:
-    probs = (0.0, args.ss_prob)
-    for p in probs:
-        model.ss_prob = p
+    if args.alpha_c > 0:
+        name, vals = "alpha_c", (0.0, args.alpha_c)
+        model.ss_prob = args.ss_prob
+    else:
+        name, vals = "ss_prob", (0.0, args.ss_prob)
+    for v in vals:
+        setattr(model, name, v)
         for i in range(3):
             step(i, i == 2)
-    times = {p: [] for p in probs}
+    times = {v: [] for v in vals}
     for r in range(args.ab):
-        for p in (probs if r % 2 == 0 else probs[::-1]):
-            model.ss_prob = p
-            times[p].append(region()[0] * 1e3)
-    for p in probs:
-        print("ss_prob %-5g ms/step per region: %s" % (p, " ".join("%.3f" % t for t in times[p])))
-    m0, m1 = statistics.median(times[probs[0]]), statistics.median(times[probs[1]])
-    print("Show-Attend-Tell train step (%s conv stack, %s), median of %d regions x 10 steps: ss_prob 0 %.3f ms, ss_prob %g %.3f ms, "
-          "delta %+.3f ms (%+.1f %%)" % (dtype, "FusedClampAdam" if FUSED_OPT else "torch clamp + Adam", args.ab, m0, args.ss_prob, m1,
-                                         m1 - m0, 100 * (m1 - m0) / m0))
+        for v in (vals if r % 2 == 0 else vals[::-1]):
+            setattr(model, name, v)
+            times[v].append(region()[0] * 1e3)
+    for v in vals:
+        print("%s %-5g ms/step per region: %s" % (name, v, " ".join("%.3f" % t for t in times[v])))
+    m0, m1 = statistics.median(times[vals[0]]), statistics.median(times[vals[1]])
+    print("Show-Attend-Tell train step (%s conv stack, %s), median of %d regions x 10 steps: %s 0 %.3f ms (min %.3f, max %.3f), "
+          "%s %g %.3f ms (min %.3f, max %.3f), delta %+.3f ms (%+.1f %%)"
+          % (dtype, "FusedClampAdam" if FUSED_OPT else "torch clamp + Adam", args.ab, name, m0, min(times[vals[0]]), max(times[vals[0]]),
+             name, vals[1], m1, min(times[vals[1]]), max(times[vals[1]]), m1 - m0, 100 * (m1 - m0) / m0))
     sys.exit(0)
-model.ss_prob = args.ss_prob
+model.ss_prob, model.alpha_c = args.ss_prob, args.alpha_c
 for i in range(3):
     loss = step(i, i == 2)
 dt, loss = region()
-print("Show-Attend-Tell train step (%s conv stack, drop-in autograd path + torch CE, %s, ss_prob %g): %.2f ms/step = %.0f img/s, "
-      "loss %.4f" % (dtype, "FusedClampAdam" if FUSED_OPT else "torch clamp + Adam", args.ss_prob, dt * 1e3, B / dt, loss.item()))
-model.ss_prob = 0
+print("Show-Attend-Tell train step (%s conv stack, drop-in autograd path + torch CE, %s, ss_prob %g, alpha_c %g): %.2f ms/step = "
+      "%.0f img/s, loss %.4f" % (dtype, "FusedClampAdam" if FUSED_OPT else "torch clamp + Adam", args.ss_prob, args.alpha_c, dt * 1e3,
+                                 B / dt, loss.item()))
+model.ss_prob = model.alpha_c = 0
 with torch.no_grad():
     feats, fmean = model._encode(images)
     torch.cuda.synchronize()
