@@ -648,6 +648,58 @@ int sat_kept_tokens(const int64_t* ids, int64_t stride, int B, int T, int64_t en
                     sat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * CIDEr of decoded id rows against reference captions (added within ABI 18).
+ * pycocoevalcap/cider/cider_scorer.py:93-181, `CiderScorer.compute_score()` with n = 4, the number train.py:169-177 keeps
+ * model-best.pth by.  Tokens are opaque int32 ids >= 0; everything below is f64.
+ *   df[g]    = number of corpus images whose reference set holds n-gram g (orders 1..4) at least once
+ *   ref_len  = log(number of corpus images)
+ *   w(g)     = tf(g) * (ref_len - log(max(1, df[g])))      an n-gram the corpus lacks: df = 0, w = tf * ref_len (it still counts
+ *                                                           in the hypothesis norm)
+ *   norm[o]  = sqrt(sum over the caption's distinct n-grams of order o of w^2)
+ *   length   = sum of tf over BIGRAMS = max(tokens - 1, 0)  (cider_scorer.py:128 tests the 0-based order against 1)
+ *   val[o]   = sum over the hypothesis's distinct n-grams of min(w_hyp, w_ref) * w_ref, / (norm_hyp[o] * norm_ref[o]) only when
+ *              both are non-zero, * exp(-(length_hyp - length_ref)^2 / (2 sigma^2))          per reference
+ *   score    = mean over the 4 orders of (sum over the image's references of val[o]) / references * 10
+ *   mean     = sum of the B scores (fixed order) / B
+ * Every sum runs in the order the reference walks its dicts (first occurrence in the caption); two calls give the same bits.
+ *
+ * The corpus n-grams are the nodes of a trie: node 0 is the root, node j + 1 has key keys[j] = (parent node << 32) | token, and
+ * df[j] is its document frequency.  The table is open addressing with linear probing, slot(key) = ((key * 0x9E3779B97F4A7C15)
+ * >> 32) & (capacity - 1), compares whole keys and is probed at most `capacity` times: a lookup is exact and always ends.
+ * sat_cider_table_insert: clears table_keys / table_nodes / status and inserts keys[0..n_keys) (one 64-bit compare-and-swap per
+ *   probed slot, node id stored beside the key; nothing reads the table in that launch).  *status (device i32) becomes non-zero
+ *   when the table filled up (bit 0) or a key came twice (bit 1); the caller reads it once.  capacity: a power of two >=
+ *   2 * n_keys.
+ * sat_cider_ref_stats: ref_norm[n_refs][4], the norms of every reference caption -- the same device function that the scoring
+ *   kernel runs over a hypothesis (one `log`, one code path).
+ * sat_cider_score: scores[b] for row b of ids ([B] rows of T int64, `stride` elements apart) against the references of image
+ *   image_index[b] (device i32 [B]; an image may come several times; clamped into the corpus in the kernel as a safety net), and
+ *   mean[0].  The row ends at kept[b] (device i32 [B] as sat_kept_tokens writes it, clamped to [0, T]) or, with kept NULL, in
+ *   front of its first end_id.  An id outside [0, 2^31) is no corpus token.  One wave per row; no allocation, no host sync.
+ * SAT_ERR_ARG before anything is enqueued: a NULL pointer (kept excepted); n_keys, n_nodes, n_refs, n_images, n_tokens,
+ * max_ref_tokens, B or T <= 0; stride < T; capacity not a power of two or below 2 * n_nodes; sigma not finite or <= 0.
+ * SAT_ERR_UNSUPPORTED: T > 64, max_ref_tokens > 128, capacity > 2^32.
+ */
+typedef struct sat_cider_corpus {
+    const uint64_t* table_keys;    /* [capacity] device */
+    const int32_t* table_nodes;    /* [capacity] device */
+    const int32_t* df;             /* [n_nodes] device */
+    const int32_t* ref_tokens;     /* [n_tokens] device: the reference captions back to back */
+    const int32_t* ref_offsets;    /* [n_refs + 1] device: caption r is ref_tokens[ref_offsets[r] .. ref_offsets[r+1]) */
+    const int32_t* image_offsets;  /* [n_images + 1] device: image i owns captions image_offsets[i] .. image_offsets[i+1] */
+    const double* ref_norm;        /* [n_refs][4] device (sat_cider_ref_stats writes it; may be NULL there) */
+    int64_t capacity, n_tokens;
+    int32_t n_nodes, n_refs, n_images;
+    int32_t max_ref_tokens;        /* the longest reference caption, as the host counted it */
+} sat_cider_corpus;
+int sat_cider_table_insert(const uint64_t* keys, int n_keys, uint64_t* table_keys, int32_t* table_nodes, int64_t capacity,
+                           int32_t* status, sat_stream_t stream);
+int sat_cider_ref_stats(const sat_cider_corpus* corpus /*[host]*/, double* ref_norm, sat_stream_t stream);
+int sat_cider_score(const sat_cider_corpus* corpus /*[host]*/, const int64_t* ids, int64_t stride, int B, int T,
+                    const int32_t* kept /*[B] or NULL*/, int64_t end_id, const int32_t* image_index /*[B]*/, double sigma,
+                    double* scores /*[B]*/, double* mean /*[1]*/, sat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * clip_gradient (train.py:88-91) + optim.Adam step (train.py:56,146) over one flat buffer.
  * clip <= 0 disables the clamp.  step is the 1-based Adam step count.
  */

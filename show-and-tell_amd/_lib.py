@@ -36,6 +36,13 @@ class SatBnRunningItem(C.Structure):
                 ("C", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SatCiderCorpus(C.Structure):
+    """mirror of `struct sat_cider_corpus` (include/sat_hip.h)"""
+    _fields_ = [("table_keys", _vp), ("table_nodes", _vp), ("df", _vp), ("ref_tokens", _vp), ("ref_offsets", _vp),
+                ("image_offsets", _vp), ("ref_norm", _vp), ("capacity", C.c_int64), ("n_tokens", C.c_int64),
+                ("n_nodes", C.c_int32), ("n_refs", C.c_int32), ("n_images", C.c_int32), ("max_ref_tokens", C.c_int32)]
+
+
 class SatOp(C.Structure):
     """mirror of `struct sat_op` (include/sat_hip.h); no instance attributes besides the fields, so a misspelt field raises"""
     __slots__ = ()
@@ -171,6 +178,9 @@ SIGNATURES = {
     "sat_ss_attend_fwd_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
     "sat_ss_attend_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(C.c_int32), _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_vp),
                                C.POINTER(_vp), _vp, _vp, _i64, _f, C.c_uint64, _i, _vp, _i64, _vp, _i64, _vp]),
+    "sat_cider_table_insert": (_i, [_vp, _i, _vp, _vp, _i64, _vp, _vp]),
+    "sat_cider_ref_stats": (_i, [C.POINTER(SatCiderCorpus), _vp, _vp]),
+    "sat_cider_score": (_i, [C.POINTER(SatCiderCorpus), _vp, _i64, _i, _i, _vp, _i64, _vp, C.c_double, _vp, _vp, _vp]),
     "sat_clamp_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp]),
     "sat_clamp_adam_step_guarded": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp, _vp]),
     "sat_step_fault_flag": (_i, [C.POINTER(_vp), _i, _vp, _vp, _vp]),
@@ -184,7 +194,7 @@ SIGNATURES = {
 # library that lacks one raises AttributeError (nothing is computed another way).  The library built from this tree exports
 # every one (tests/test_cabi_and_host.py, tests/test_conv_cases_host.py).
 ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_attention_coverage_ws_bytes", "sat_attention_coverage",
-                    "sat_attention_bwd_ex", "sat_beam_backtrack_rows")
+                    "sat_attention_bwd_ex", "sat_beam_backtrack_rows", "sat_cider_table_insert", "sat_cider_ref_stats", "sat_cider_score")
 
 _lib = None
 

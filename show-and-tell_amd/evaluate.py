@@ -7,7 +7,12 @@
     for word_id in sentence_ids: if word == '<end>': break        eval.py:103-109   sat_kept_tokens: the count per row, on the device
 
 `validation_step` returns device tensors (no host sync); `sentences` is the host-side id -> word join of eval.py:101-110 over
-the already truncated rows.  `language_eval` (COCO scorers, eval.py:15-55) is out of scope."""
+the already truncated rows.
+
+Of `language_eval` (eval.py:15-55) the one number the reference's trainer acts on is here: with a `CiderScorer` (cider.py) and
+the batch's `image_index`, `validation_step` also returns CIDEr (`lang_stats['CIDEr']`, train.py:169-177) of the decoded rows,
+per caption and as the batch mean, still without a host sync.  The reference words must already be tokenised: the PTB tokenizer
+(Java) and BLEU, METEOR, ROUGE and SPICE stay out of scope."""
 import torch
 
 from . import _lib as L
@@ -58,9 +63,12 @@ def kept_tokens(ids, end_id):
 
 
 @torch.no_grad()
-def validation_step(model, images, captions, lengths, state=None, end_id=2, beam_size=1):
+def validation_step(model, images, captions, lengths, state=None, end_id=2, beam_size=1, scorer=None, image_index=None):
     """One iteration of the loop body eval.py:71-118 (the caller has put the model in eval mode, eval.py:65).
-    Returns dict(loss f32[1], ids i64[B,20], kept i32[B]) -- all on the device, nothing synchronised."""
+    Returns dict(loss f32[1], ids i64[B,20], kept i32[B]) -- all on the device, nothing synchronised.  With a `CiderScorer`
+    and `image_index` (the corpus image of every row) the dict gains cider f64[1] and cider_scores f64[B] of `ids`."""
+    if (scorer is None) != (image_index is None):
+        raise ValueError("scorer and image_index go together")
     if model.training:
         raise RuntimeError("validation_step expects model.eval() (eval.py:65)")
     targets, _ = pack_validation_targets(captions, lengths)
@@ -74,7 +82,10 @@ def validation_step(model, images, captions, lengths, state=None, end_id=2, beam
         ids = model.sample(images, state)                               # eval.py:99
         if ids.dim() == 1:                                              # squeezed at batch 1 (models.py:67): one row
             ids = ids.view(1, -1)
-    return {"loss": loss, "ids": ids, "kept": kept_tokens(ids, end_id)}
+    out = {"loss": loss, "ids": ids, "kept": kept_tokens(ids, end_id)}
+    if scorer is not None:
+        out["cider"], out["cider_scores"] = scorer.score(ids, image_index, end_id=end_id, kept=out["kept"])
+    return out
 
 
 def sentences(ids, kept, idx2word):
