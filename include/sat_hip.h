@@ -700,6 +700,40 @@ int sat_cider_score(const sat_cider_corpus* corpus /*[host]*/, const int64_t* id
                     double* scores /*[B]*/, double* mean /*[1]*/, sat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Self-critical sequence training (Rennie et al. 2017; added within ABI 18): a caption SAMPLED from the model is trained with its
+ * cross entropy weighted by CIDEr(sampled) - CIDEr(greedy).  Nothing here synchronises or reads back; every entry point returns
+ * SAT_ERR_ARG for null or impossible arguments and SAT_ERR_WORKSPACE for a short workspace before anything is enqueued.
+ * sat_rollout_decoder_fwd: DecoderRNN.sample (models.py:56-67) in training form, ONE call for `steps` steps of all B rows: step 0
+ *   feeds features, step t >= 1 feeds embed[ids[b][t-1]]; every step runs the fused LSTM step per layer from a zero initial state
+ *   and the exact-f32 vocab projection, and ids[b][t] = s(b, t) of sat_vocab_sample's convention, drawn from step t's own logits
+ *   (counter (v >> 2, b, t, 2*rank), word v & 3: every row draws at every step, t = 0 included; no mask draw, no teacher).  Rows keep
+ *   running after they emit <end>; they are masked by sat_scst_weights.  Packed rows are n = t*B + b (batch_sizes = [B] * steps):
+ *   tapes (HOST array of 5 * num_layers device pointers, as for sat_ss_decoder_fwd) receive exactly what sat_lstm_fwd leaves there,
+ *   X [steps*B, E] the layer-0 input, logits [steps*B, ldl >= V] (pad columns untouched), ids [B][ids_stride >= steps].  Its
+ *   backward is sat_vocab_ce_bwd -> sat_lstm_bwd -> sat_embed_concat_bwd on ids[:, :steps-1].  E, H multiples of 4;
+ *   num_layers <= 8; lstm_w as for sat_ss_decoder_fwd.  workspace: sat_rollout_decoder_fwd_ws_bytes(B, V).
+ * sat_scst_weights: len[b] = min(kept[b] + 1, T) with kept[b] as sat_kept_tokens defines it (the <end> token itself is trained);
+ *   M = sum_b len[b] (an integer sum: exact in any order), or *denom when denom != NULL (a global token count);
+ *   w[t*B + b] = (float)((reward[b] - baseline[b]) / M) for t < len[b], +0.0f after -- f64 arithmetic, rounded once.  reward,
+ *   baseline (NULL: 0), denom: device f64.  Outputs w f32 [T*B], len i32 [B], m_out f64 [1].  One launch, one workgroup.
+ * sat_ce_rows_weighted: sat_ce_rows with the device weight w[n] of packed row n = t*B + b in place of inv_denom and the target
+ *   ids[b*ids_stride + t] (N a multiple of B, ids_stride >= N / B): row_loss[n] = lse_n - logit_n[target]; loss_out[0] (NULL: no
+ *   sum) = sum_n w[n] * row_loss[n] in a fixed order; write_grad: logits are overwritten IN PLACE with w[n] * (softmax - onehot).
+ *   A row with w[n] == 0 gets an all-zero gradient row and adds exactly 0 to the loss whatever its logits hold (a non-finite
+ *   logit of a masked row never becomes NaN * 0; its row_loss[n] is then non-finite).  Pad columns [V, ldl) are left alone. */
+int64_t sat_rollout_decoder_fwd_ws_bytes(int B, int V);
+int sat_rollout_decoder_fwd(const float* features /*[B,E]*/, const float* embed /*[V,E]*/, int B, int steps, int E, int V,
+                            const float* const* lstm_w /*[host]*/, int num_layers, int H, const float* lin_w, const float* lin_b,
+                            float* const* tapes /*[host]*/, float* X, float* logits, int64_t ldl, uint64_t seed, int rank, int64_t* ids,
+                            int64_t ids_stride, float* workspace, int64_t ws_bytes, sat_stream_t stream);
+int sat_scst_weights(const int64_t* ids, int64_t stride, int B, int T, int64_t end_id, const double* reward /*[B]*/,
+                     const double* baseline /*[B] or NULL*/, const double* denom /*[1] or NULL*/, float* w /*[T*B]*/,
+                     int32_t* len /*[B]*/, double* m_out /*[1]*/, sat_stream_t stream);
+int sat_ce_rows_weighted(float* logits /*[N,ldl]*/, int64_t ldl, const int64_t* ids, int64_t ids_stride, int B, int N, int V,
+                         const float* w /*[N]*/, int write_grad, float* row_loss /*[N]*/, float* loss_out /*[1] or NULL*/,
+                         sat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * clip_gradient (train.py:88-91) + optim.Adam step (train.py:56,146) over one flat buffer.
  * clip <= 0 disables the clamp.  step is the 1-based Adam step count.
  */

@@ -572,11 +572,18 @@ __device__ __forceinline__ float block_reduce(float v, bool is_max, float* sh) {
     return r;
 }
 
+// WEIGHTED (sat_ce_rows_weighted): the scale of row n is the device value w[n] instead of the scalar inv_denom, a row of weight 0
+// gets an all-zero gradient whatever its logits hold (never NaN * 0), and the target of packed row n = t * B + b is read where the
+// rollout left it, targets[b * tstride + t].  !WEIGHTED is sat_ce_rows: none of this is compiled into it.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void ce_rows_kernel(float* __restrict__ logits, long ldl, const int64_t* __restrict__ targets,
-                                                      int V, float inv_denom, int write_grad, float* __restrict__ row_loss) {
+                                                      int V, float inv_denom, int write_grad, float* __restrict__ row_loss,
+                                                      const float* __restrict__ w, long tstride, int B) {
     __shared__ float sh[4];
     const int row = blockIdx.x;
     float* x = logits + (long)row * ldl;
+    if constexpr (WEIGHTED) inv_denom = w[row];
+    const long tpos = WEIGHTED ? (long)(row % B) * tstride + row / B : (long)row;
     constexpr int RC = 12;                       // 16-byte chunks of the row a thread keeps in registers
     const int nq = V >> 2;
     if ((ldl & 3) == 0 && nq <= RC * 256 && (((uintptr_t)logits) & 15) == 0) {
@@ -604,7 +611,7 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(float* __restrict__ logits
         if (tail < V) s += expf(xt - m);
         s = block_reduce(s, false, sh);
         const float lse = m + logf(s);
-        long tgt = targets[row];
+        long tgt = targets[tpos];
         tgt = tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt);
         const int tq = (int)(tgt >> 2), te = (int)(tgt & 3);
         // the thread that holds the target logit reports the row loss
@@ -621,10 +628,11 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(float* __restrict__ logits
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
                         g[e] = (expf(rc[c][e] - lse) - ((4 * q + e) == (int)tgt ? 1.0f : 0.0f)) * inv_denom;
+                    if (WEIGHTED && inv_denom == 0.0f) g = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
                     *(f32x4*)(x + 4 * q) = g;
                 }
             }
-            if (tail < V) x[tail] = (expf(xt - lse) - (tail == (int)tgt ? 1.0f : 0.0f)) * inv_denom;
+            if (tail < V) x[tail] = (WEIGHTED && inv_denom == 0.0f) ? 0.0f : (expf(xt - lse) - (tail == (int)tgt ? 1.0f : 0.0f)) * inv_denom;
         }
         return;
     }
@@ -635,15 +643,65 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(float* __restrict__ logits
     for (int i = threadIdx.x; i < V; i += 256) s += expf(x[i] - m);
     s = block_reduce(s, false, sh);
     const float lse = m + logf(s);
-    long tgt = targets[row];
+    long tgt = targets[tpos];
     tgt = tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt);
     if (threadIdx.x == 0) row_loss[row] = lse - x[tgt];
     if (write_grad) {
         __syncthreads();   // x[tgt] read above before any overwrite
         for (int i = threadIdx.x; i < V; i += 256) {
             const float pr = expf(x[i] - lse);
-            x[i] = (pr - (i == (int)tgt ? 1.0f : 0.0f)) * inv_denom;
+            x[i] = (WEIGHTED && inv_denom == 0.0f) ? 0.0f : (pr - (i == (int)tgt ? 1.0f : 0.0f)) * inv_denom;
         }
+    }
+}
+
+// out[0] = sum_n w[n] * v[n] in sum_scale_kernel's order; a term of weight 0 is exactly 0 whatever v[n] holds
+__global__ __launch_bounds__(256) void weighted_sum_kernel(const float* __restrict__ v, const float* __restrict__ w, int n, float* out) {
+    __shared__ float sh[256];
+    float s = 0.0f;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float wi = w[i];
+        if (wi != 0.0f) s += wi * v[i];
+    }
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) sh[threadIdx.x] += sh[threadIdx.x + k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = sh[0];
+}
+
+// Self-critical sequence training (Rennie et al. 2017): the per-row weights of the sampled caption's cross entropy.  One workgroup:
+// len[b] = min(kept[b] + 1, T) (kept as kept_tokens_kernel counts it: the <end> token itself is trained), M = sum_b len[b] (integer,
+// so exact in any order) or *denom, w[t * B + b] = (float)((reward[b] - baseline[b]) / M) for t < len[b], +0 after: f64, rounded once.
+__global__ __launch_bounds__(256) void scst_weights_kernel(const int64_t* __restrict__ ids, long stride, int B, int T, int64_t end_id,
+                                                           const double* __restrict__ reward, const double* __restrict__ baseline,
+                                                           const double* __restrict__ denom, float* __restrict__ w,
+                                                           int32_t* __restrict__ len, double* __restrict__ m_out) {
+    __shared__ long long sh[256];
+    const int tid = threadIdx.x;
+    long long tot = 0;
+    for (int b = tid; b < B; b += 256) {
+        const int64_t* row = ids + (long)b * stride;
+        int n = 0;
+        while (n < T && row[n] != end_id) ++n;
+        n = n + 1 < T ? n + 1 : T;
+        len[b] = n;
+        tot += n;
+    }
+    sh[tid] = tot;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (tid < k) sh[tid] += sh[tid + k];
+        __syncthreads();
+    }
+    const double M = denom ? *denom : (double)sh[0];
+    if (tid == 0) m_out[0] = M;
+    for (int b = tid; b < B; b += 256) {        // the thread that wrote len[b] reads it back
+        const float wb = (float)((reward[b] - (baseline ? baseline[b] : 0.0)) / M);
+        const int n = len[b];
+        for (int t = 0; t < T; ++t) w[(long)t * B + b] = t < n ? wb : 0.0f;
     }
 }
 
@@ -1214,12 +1272,37 @@ extern "C" int sat_ce_rows(float* logits, int64_t ldl, const int64_t* targets, i
                            int write_grad, float* row_loss, float* loss_out, sat_stream_t stream) {
     if (!logits || !targets || !row_loss || N < 1 || V < 1 || ldl < V) return SAT_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ce_rows_kernel, dim3(N), dim3(256), 0, s, logits, (long)ldl, targets, V, inv_denom, write_grad, row_loss);
+    hipLaunchKernelGGL(ce_rows_kernel<false>, dim3(N), dim3(256), 0, s, logits, (long)ldl, targets, V, inv_denom, write_grad, row_loss,
+                       (const float*)nullptr, 0L, 1);
     SAT_LAUNCH_CHECK();
     if (loss_out) {
         hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(256), 0, s, row_loss, N, inv_denom, loss_out);
         SAT_LAUNCH_CHECK();
     }
+    return SAT_OK;
+}
+
+extern "C" int sat_ce_rows_weighted(float* logits, int64_t ldl, const int64_t* ids, int64_t ids_stride, int B, int N, int V,
+                                    const float* w, int write_grad, float* row_loss, float* loss_out, sat_stream_t stream) {
+    if (!logits || !ids || !w || !row_loss || B < 1 || N < 1 || N % B || V < 1 || ldl < V || ids_stride < N / B) return SAT_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ce_rows_kernel<true>, dim3(N), dim3(256), 0, s, logits, (long)ldl, ids, V, 0.0f, write_grad, row_loss, w,
+                       (long)ids_stride, B);
+    SAT_LAUNCH_CHECK();
+    if (loss_out) {
+        hipLaunchKernelGGL(weighted_sum_kernel, dim3(1), dim3(256), 0, s, row_loss, w, N, loss_out);
+        SAT_LAUNCH_CHECK();
+    }
+    return SAT_OK;
+}
+
+extern "C" int sat_scst_weights(const int64_t* ids, int64_t stride, int B, int T, int64_t end_id, const double* reward,
+                                const double* baseline, const double* denom, float* w, int32_t* len, double* m_out,
+                                sat_stream_t stream) {
+    if (!ids || !reward || !w || !len || !m_out || B < 1 || T < 1 || stride < T || (long)B * T > 0x7fffffffL) return SAT_ERR_ARG;
+    hipLaunchKernelGGL(scst_weights_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ids, (long)stride, B, T, end_id, reward,
+                       baseline, denom, w, len, m_out);
+    SAT_LAUNCH_CHECK();
     return SAT_OK;
 }
 

@@ -164,6 +164,52 @@ extern "C" int sat_ss_decoder_fwd(const float* features, const float* embed, con
     return SAT_OK;
 }
 
+// ---- sampled rollout (self-critical sequence training, Rennie et al. 2017) -------------------------------------------------------
+// DecoderRNN.sample (models.py:56-67) in training form, with a draw where the reference takes the arg-max: step 0 feeds the
+// features, step t >= 1 feeds embed[ids[b][t-1]], and ids[b][t] = s(b, t) drawn from step t's own logits (counter t: every row
+// draws at every step, no mask, no teacher).  All B rows run all `steps` steps, so the packed order is batch_sizes = [B] * steps
+// and the tapes, X and the logits are those of a teacher-forced forward on ids[:, :steps-1]: its backward applies unchanged.
+extern "C" int64_t sat_rollout_decoder_fwd_ws_bytes(int B, int V) { return sat_ss_decoder_fwd_ws_bytes(B, V); }
+
+extern "C" int sat_rollout_decoder_fwd(const float* features, const float* embed, int B, int steps, int E, int V,
+                                       const float* const* lstm_w, int num_layers, int H, const float* lin_w, const float* lin_b,
+                                       float* const* tapes, float* X, float* logits, int64_t ldl, uint64_t seed, int rank, int64_t* ids,
+                                       int64_t ids_stride, float* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    if (!features || !embed || !lstm_w || !lin_w || !lin_b || !tapes || !X || !logits || !ids || !workspace) return SAT_ERR_ARG;
+    if (B < 1 || steps < 1 || E < 4 || (E & 3) || H < 4 || (H & 3) || V < 1 || num_layers < 1 || num_layers > 8 || rank < 0)
+        return SAT_ERR_ARG;
+    if (ldl < V || ids_stride < steps || (long)B * steps > 0x7fffffffL) return SAT_ERR_ARG;
+    for (int l = 0; l < num_layers; ++l)
+        for (int k = 0; k < 5; ++k)
+            if (!tapes[5 * l + k] || !lstm_w[4 * l + (k & 3)]) return SAT_ERR_ARG;
+    if (ws_bytes < sat_rollout_decoder_fwd_ws_bytes(B, V)) return SAT_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemcpyAsync(X, features, (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, s);    // step 0's input
+    for (int l = 0; l < num_layers && e == hipSuccess; ++l) {                                                  // h_{-1} = c_{-1} = 0
+        e = hipMemsetAsync(tapes[5 * l + 3], 0, (size_t)B * H * sizeof(float), s);
+        if (e == hipSuccess) e = hipMemsetAsync(tapes[5 * l + 4], 0, (size_t)B * H * sizeof(float), s);
+    }
+    if (e != hipSuccess) return (int)e;
+    for (int t = 0; t < steps; ++t) {
+        const long off = (long)t * B;
+        const bool more = t + 1 < steps;
+        const float* inp = X + off * E;
+        int In = E;
+        for (int l = 0; l < num_layers; ++l) {
+            float* GA = tapes[5 * l], *CS = tapes[5 * l + 1], *HS = tapes[5 * l + 2], *HP = tapes[5 * l + 3], *cst = tapes[5 * l + 4];
+            SAT_TRY(sat_skinny_lstm(HP + off * H, lstm_w[4 * l + 1], inp, lstm_w[4 * l], In, lstm_w[4 * l + 2], lstm_w[4 * l + 3],
+                                    nullptr, 0, B, H, cst, GA + off * 4 * H, 4L * H, CS + off * H, HS + off * H,
+                                    more ? HP + (off + B) * H : nullptr, more ? B : 0, s));
+            inp = HS + off * H;
+            In = H;
+        }
+        // ids[b][t] = s(b, t); its embedding row is step t+1's input (the last step's draw is a target only)
+        SAT_TRY(sample_step(inp, lin_w, lin_b, B, B, H, V, logits + off * ldl, ldl, 1.0f, seed, t, rank, nullptr, 0, ids + t, ids_stride,
+                            more ? embed : nullptr, E, more ? X + (off + B) * E : nullptr, E, workspace, s));
+    }
+    return SAT_OK;
+}
+
 // ---- Show-Attend-Tell (model2.py:38-85, the model train.py:37 builds) with scheduled sampling ------------------------------------
 // The input of step t >= 1 is [emb | ctx_t]: with probability ss_prob the embedding half holds a token drawn from softmax(logits of
 // step t-1), logits = classifier(context2out(ctx_{t-1}) + hidden2tout(h_{t-1})); the context half is always step t's own context.

@@ -7,6 +7,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from .pack import PackInfo
 from .watch import ResidencyWatch
 
 LSTM_NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
@@ -112,6 +113,55 @@ def _fit(lib, ws, dev, B, T, layers, backward):
     return ws
 
 
+def _new_tapes(layers, N, B, E, dev, captions):
+    """empty tapes of a forward over N packed rows: X[0] the layer-0 input, X[l + 1] layer l's h_t (HS), per layer (GA, CS, HP);
+    and the per-layer cell state [B, H]"""
+    tapes = {"X": [torch.empty(N, E, device=dev)], "layers": [], "captions": captions}
+    cst = []
+    for _, w_hh, _, _ in layers:
+        H = w_hh.shape[1]
+        tapes["layers"].append((torch.empty(N, 4 * H, device=dev), torch.empty(N, H, device=dev), torch.empty(N, H, device=dev)))
+        tapes["X"].append(torch.empty(N, H, device=dev))
+        cst.append(torch.empty(B, H, device=dev))
+    return tapes, cst
+
+
+def _step_loop_pointers(layers, tapes, cst):
+    """the `lstm_w` and `tapes` arguments (lists of device pointers) of the calls that run the decoder step by step"""
+    wflat = [t.data_ptr() for layer in layers for t in layer]
+    ptrs = [t.data_ptr() for (GA, CS, HP), HS, c in zip(tapes["layers"], tapes["X"][1:], cst) for t in (GA, CS, HS, HP, c)]
+    return wflat, ptrs
+
+
+def rollout_forward(lib, features, params, steps, seed, rank, ws=None, logits=None):
+    """The SAMPLED forward of self-critical training (`sat_rollout_decoder_fwd`, one library call): `steps` steps of all B rows, the
+    input of step t >= 1 the token drawn from step t-1's logits.  Returns (ids i64 [B, steps], logits f32 [steps * B, pad4(V)],
+    tapes, PackInfo of [steps] * B): the tapes are a teacher-forced forward's on ids[:, :steps-1], so `decoder_backward` applies.
+    ws, logits: as for `decoder_forward`."""
+    dev = features.device
+    embed_w, lin_w, lin_b = params["embed.weight"], params["linear.weight"], params["linear.bias"]
+    layers = lstm_layers(params)
+    E, V = embed_w.shape[1], lin_w.shape[0]
+    B, steps = features.shape[0], int(steps)
+    if steps < 1:
+        raise ValueError("steps must be >= 1")
+    pi = PackInfo.get([steps] * B, dev)
+    ws = _fit(lib, ws, dev, B, steps, layers, backward=False)
+    ids = torch.empty(B, steps, dtype=torch.int64, device=dev)
+    tapes, cst = _new_tapes(layers, pi.N, B, E, dev, ids[:, :steps - 1])
+    if logits is None:
+        logits = L.logits_buffer(pi.N, V, dev)
+    wflat, ptrs = _step_loop_pointers(layers, tapes, cst)
+    sws_bytes = lib.sat_rollout_decoder_fwd_ws_bytes(B, V)
+    sws = torch.empty(max(sws_bytes // 4, 4), device=dev)
+    L.check(lib.sat_rollout_decoder_fwd(L.ptr(features), L.ptr(embed_w), B, steps, E, V, (C.c_void_p * len(wflat))(*wflat), len(layers),
+                                        layers[0][1].shape[1], L.ptr(lin_w), L.ptr(lin_b), (C.c_void_p * len(ptrs))(*ptrs),
+                                        L.ptr(tapes["X"][0]), L.ptr(logits), logits.stride(0), int(seed), int(rank), ids.data_ptr(),
+                                        ids.stride(0), L.ptr(sws), sws_bytes, L.stream()), "sat_rollout_decoder_fwd")
+    ws.ran_ss_fwd()
+    return ids, logits, tapes, pi
+
+
 def decoder_forward(lib, features, params, captions, pi, ws=None, logits=None, ce=None, mixed_ws=None, ss=None, store_logits=True):
     """embed+cat+pack -> L x LSTM -> vocab logits (models.py:49-53).  Returns (logits f32 [N, pad4(V)], tapes).
     params: the decoder's tensors by parameter name; ws: the `LSTMWorkspaces` of the calls (None: the autograd path's); logits:
@@ -134,22 +184,15 @@ def decoder_forward(lib, features, params, captions, pi, ws=None, logits=None, c
         raise ValueError("captions has %d columns but lengths need %d" % (captions.shape[1], T - 1))
     cap_ptr, cap_stride = (captions.data_ptr(), captions.stride(0)) if T > 1 else (None, 0)
     ws = _fit(lib, ws, dev, B, T, layers, backward=False)
-    X = torch.empty(N, E, device=dev)
-    tapes = {"X": [X], "layers": [], "captions": captions}
-    cst = []
-    for w_ih, w_hh, _, _ in layers:
-        H = w_hh.shape[1]
-        tapes["layers"].append((torch.empty(N, 4 * H, device=dev), torch.empty(N, H, device=dev), torch.empty(N, H, device=dev)))
-        tapes["X"].append(torch.empty(N, H, device=dev))
-        cst.append(torch.empty(B, H, device=dev))
+    tapes, cst = _new_tapes(layers, N, B, E, dev, captions)
+    X = tapes["X"][0]
     if logits is None:
         logits = L.logits_buffer(N, V, dev)
     if ss is not None:
         prob, seed, rank = ss
         used = torch.empty(B, max(T - 1, 1), dtype=torch.int64, device=dev)[:, :T - 1]
         tapes["captions"] = used
-        wflat = [t.data_ptr() for layer in layers for t in layer]
-        ptrs = [t.data_ptr() for (GA, CS, HP), HS, c in zip(tapes["layers"], tapes["X"][1:], cst) for t in (GA, CS, HS, HP, c)]
+        wflat, ptrs = _step_loop_pointers(layers, tapes, cst)
         sws_bytes = lib.sat_ss_decoder_fwd_ws_bytes(B, V)
         sws = torch.empty(max(sws_bytes // 4, 4), device=dev)
         L.check(lib.sat_ss_decoder_fwd(L.ptr(features), L.ptr(embed_w), cap_ptr, captions.stride(0), pi.bs_c, L.ptr(pi.prefix_dev),

@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .pack import PackInfo
-from .decoder import decoder_backward, decoder_forward
+from .decoder import decoder_backward, decoder_forward, rollout_forward
 from .resnet import RESNET152, ConvStackProgram, ResNetStack, weights_signature
 from .watch import IdGuard  # noqa: F401  (also imported from here by callers)
 
@@ -459,10 +459,33 @@ class _DecoderFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits):
-        g = {n: torch.empty_like(p) for n, p in ctx.params.items()}
-        g["features"] = torch.empty(ctx.pi.B, ctx.params["embed.weight"].shape[1], device=dlogits.device)
-        decoder_backward(L.load(), L.pad_rows4(dlogits), ctx.tapes, ctx.params, ctx.pi, g, None)
+        g = _decoder_grads(ctx, dlogits)
         return (g["features"], None, None, None, None, *(g[n] for n in ctx.names))
+
+
+def _decoder_grads(ctx, dlogits):
+    """`decoder_backward` on the tapes a decoder Function's forward left in ctx: gradients by parameter name, plus "features" """
+    g = {n: torch.empty_like(p) for n, p in ctx.params.items()}
+    g["features"] = torch.empty(ctx.pi.B, ctx.params["embed.weight"].shape[1], device=dlogits.device)
+    decoder_backward(L.load(), L.pad_rows4(dlogits), ctx.tapes, ctx.params, ctx.pi, g, None)
+    return g
+
+
+class _RolloutFn(torch.autograd.Function):
+    """The sampled rollout of self-critical training; its backward is the teacher-forced backward on the tokens drawn"""
+
+    @staticmethod
+    def forward(ctx, features, steps, seed, rank, out, names, *tensors):
+        params = dict(zip(names, tensors))
+        out["ids"], logits, tapes, pi = rollout_forward(L.load(), features, params, steps, seed, rank)
+        ctx.tapes, ctx.pi, ctx.names, ctx.params = tapes, pi, names, params
+        V = params["linear.weight"].shape[0]
+        return logits if logits.shape[1] == V else logits[:, :V]
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        g = _decoder_grads(ctx, dlogits)
+        return (g["features"], None, None, None, None, None, *(g[n] for n in ctx.names))
 
 
 class DecoderRNN(nn.Module):
@@ -477,6 +500,7 @@ class DecoderRNN(nn.Module):
         self.ss_prob = 0                  # scheduled sampling (models.py:38; schedule: trainer.ss_prob_for_epoch), training mode only
         self.ss_rank = 0                  # data-parallel rank: a stream of draws of its own per rank
         self.last_ss_inputs = self.last_ss_seed = None   # tokens fed [B, T-1] and seed of the last sampled forward
+        self.last_rollout_seed = None     # seed of the last `rollout`
         self._id_guard = None
         self.init_weights()
 
@@ -516,6 +540,22 @@ class DecoderRNN(nn.Module):
         if ss is not None:
             self.last_ss_inputs, self.last_ss_seed = ss["used"], ss["seed"]
         return out
+
+    def rollout(self, features, steps=20):
+        """`sample` with a DRAW from softmax(logits) where `sample` takes the arg-max, in training form (self-critical sequence
+        training, Rennie et al. 2017): (ids i64 [B, steps], logits f32 [steps * B, V]), logits row t * B + b those of step t of row
+        b.  The logits carry autograd: their backward is the teacher-forced backward on ids[:, :steps-1].  Training mode only.  The
+        seed comes from torch's CPU generator (`draw_ss_seed`) and is kept as `last_rollout_seed`; the draws are `ss_rank`'s stream.
+        Rows keep running behind their <end>: `scst_loss` masks them."""
+        if not self.training:
+            raise RuntimeError("DecoderRNN.rollout is a training forward (decoder.train()); eval mode decodes with sample()")
+        features = _f32c(features, "features")
+        seed = draw_ss_seed()
+        names, tensors = zip(*self.named_parameters())
+        out = {}
+        logits = _RolloutFn.apply(features, int(steps), seed, int(self.ss_rank), out, names, *tensors)
+        self.last_rollout_seed = seed
+        return out["ids"], logits
 
     @torch.no_grad()
     def sample(self, features, states=None):
@@ -636,6 +676,14 @@ class ShowAndTell(nn.Module):
 
     def forward(self, images, captions, lengths):
         return self.decoder(self.encoder(images), captions, lengths)
+
+    def scst_forward(self, images, image_index, scorer, end_id=2):
+        """The self-critical loss of one batch (`scst.SelfCritical`) behind the encoder's forward, so that `loss.backward()` also
+        trains fc / bn.  image_index: the corpus image of every row, as for `CiderScorer.score`.  The `SelfCritical` object (its
+        last_reward, last_baseline, last_ids) is kept as `last_scst`."""
+        from .scst import SelfCritical
+        self.last_scst = SelfCritical(scorer, end_id)
+        return self.last_scst(self.decoder, self.encoder(images), image_index)
 
     @torch.no_grad()
     def sample(self, images, state=None):

@@ -16,9 +16,10 @@ as each bucket's gradients become final and overlapped with the rest of the back
 import torch
 
 from . import _lib as L
-from .decoder import LSTMWorkspaces, VocabCE, decoder_backward, decoder_forward
+from .decoder import LSTMWorkspaces, VocabCE, decoder_backward, decoder_forward, rollout_forward
 from .models import ShowAndTell, draw_ss_seed, fc_bn1d_backward, fc_bn1d_forward
 from .pack import PackInfo
+from .scst import SelfCritical, ce_rows_weighted, scst_weights
 from .watch import ResidencyWatch, StatusRing
 
 
@@ -155,7 +156,7 @@ class TrainStep:
         streams under this batch's decoder work (prefetch_encoder)."""
         images, captions, lengths = batch
         lib, model, flat = self.lib, self.model, self.flat
-        enc, dec = model.encoder, model.decoder
+        dec = model.decoder
         if not model.training:
             raise RuntimeError("TrainStep needs model.train() (batch-statistics BatchNorm, train.py never calls eval())")
         L.require_gpu(captions, "captions")
@@ -176,33 +177,12 @@ class TrainStep:
         l1 = [l - 1 for l in lengths]                                        # train.py:134
         pi = PackInfo.get(l1, dev)
         N, V, E = pi.N, dec.vocab_size, dec.embed_size
-        key = (B, N)
-        bufs = self._bufs.get(key)
-        if bufs is None:
-            self._bufs.clear()
-            F = enc.resnet.feature_dim
-            wsb = lib.sat_fc_bn1d_ws_bytes(B, F, E)
-            bufs = self._bufs[key] = dict(
-                targets=torch.empty(N, dtype=torch.int64, device=dev), logits=L.logits_buffer(N, V, dev),
-                row_loss=torch.empty(N, device=dev), feats=torch.empty(B, E, device=dev),
-                xhat=torch.empty(B, E, device=dev), rstd=torch.empty(E, device=dev),
-                head_ws=torch.empty(max(wsb // 4, B * E), device=dev), d_feat=torch.empty(B, E, device=dev),
-                pooled=torch.empty(B, F, device=dev))
+        bufs = self._step_bufs(B, N, dev)
         # targets = pack(captions[:,1:], lengths-1)                           train.py:135
         L.check(lib.sat_pack_targets(captions.data_ptr(), captions.stride(0), L.ptr(pi.prefix_dev), pi.T, N,
                                      L.ptr(bufs["targets"]), st), "sat_pack_targets")
         # ---- forward (train.py:139) ----
-        cached_features = images.dim() == 2      # [B,E] precomputed encoder features: decoder-only training
-        fc, bn = enc.resnet.fc, enc.bn
-        if cached_features:
-            feats_in = images.contiguous()
-            pooled = None
-        else:
-            pooled = self._encoder_pooled(images, bufs["pooled"], next_images)
-            fc_bn1d_forward(lib, pooled, fc.weight, fc.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, True,
-                            bufs["feats"], bufs["xhat"], bufs["rstd"], bufs["head_ws"])
-            L.counter_add(bn.num_batches_tracked)
-            feats_in = bufs["feats"]
+        feats_in, pooled = self._head_forward(images, bufs, next_images)
         params = dict(dec.named_parameters())
         loss_slot = flat.grads[flat.loss_slot:flat.loss_slot + 1]
         ce = mixed_ws = None
@@ -234,8 +214,45 @@ class TrainStep:
         g = {name: flat.grad("decoder." + name) for name in params}
         g["features"] = bufs["d_feat"]
         decoder_backward(lib, logits, tapes, params, pi, g, self.lstm_ws, on_stage=on_bucket_ready, ce=ce, mixed_ws=mixed_ws)
-        if not cached_features:
-            fc_bn1d_backward(lib, bufs["d_feat"], pooled, bufs["xhat"], bufs["rstd"], bn.weight,
+        self._head_backward(bufs, pooled, feats_in)
+        if on_bucket_ready is not None:
+            on_bucket_ready(2)   # encoder head + embedding gradients (and the loss slot) are final
+        return loss_slot
+
+    def _step_bufs(self, B, N, dev):
+        """the buffers a step of B images and N packed rows owns (one set is kept: another (B, N) replaces it)"""
+        bufs = self._bufs.get((B, N))
+        if bufs is None:
+            self._bufs.clear()
+            enc, dec = self.model.encoder, self.model.decoder
+            E, V, F = dec.embed_size, dec.vocab_size, enc.resnet.feature_dim
+            wsb = self.lib.sat_fc_bn1d_ws_bytes(B, F, E)
+            bufs = self._bufs[(B, N)] = dict(
+                targets=torch.empty(N, dtype=torch.int64, device=dev), logits=L.logits_buffer(N, V, dev),
+                row_loss=torch.empty(N, device=dev), feats=torch.empty(B, E, device=dev),
+                xhat=torch.empty(B, E, device=dev), rstd=torch.empty(E, device=dev),
+                head_ws=torch.empty(max(wsb // 4, B * E), device=dev), d_feat=torch.empty(B, E, device=dev),
+                pooled=torch.empty(B, F, device=dev))
+        return bufs
+
+    def _head_forward(self, images, bufs, next_images):
+        """(features [B, E], pooled): the frozen stack (from the look-ahead when prefetched) and fc + BatchNorm1d; `images` [B, E]
+        are precomputed encoder features (decoder-only training): passed through, pooled None"""
+        if images.dim() == 2:
+            return images.contiguous(), None
+        enc = self.model.encoder
+        fc, bn = enc.resnet.fc, enc.bn
+        pooled = self._encoder_pooled(images, bufs["pooled"], next_images)
+        fc_bn1d_forward(self.lib, pooled, fc.weight, fc.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, True,
+                        bufs["feats"], bufs["xhat"], bufs["rstd"], bufs["head_ws"])
+        L.counter_add(bn.num_batches_tracked)
+        return bufs["feats"], pooled
+
+    def _head_backward(self, bufs, pooled, feats_in):
+        """the head's backward from bufs["d_feat"] into the flat buffer (not with cached features), then the step's fault flag"""
+        lib, flat = self.lib, self.flat
+        if pooled is not None:
+            fc_bn1d_backward(lib, bufs["d_feat"], pooled, bufs["xhat"], bufs["rstd"], self.model.encoder.bn.weight,
                              flat.grad("encoder.resnet.fc.weight"), flat.grad("encoder.resnet.fc.bias"),
                              flat.grad("encoder.bn.weight"), flat.grad("encoder.bn.bias"), bufs["head_ws"])
         self.last_d_features = bufs["d_feat"]
@@ -246,9 +263,38 @@ class TrainStep:
         # engine's sticky word, into slot 1 of the trailing floats -- it rides the last bucket's all-reduce, and clamp + Adam
         # read it on the device (optimizer_step): a step that any rank lost never reaches the parameters of any rank
         words, nw = self.lstm_ws.fault_words
-        L.check(lib.sat_step_fault_flag(words, nw, L.ptr(self._fault_sticky), L.ptr(self.fault_slot), st), "sat_step_fault_flag")
-        if on_bucket_ready is not None:
-            on_bucket_ready(2)   # encoder head + embedding gradients (and the loss slot) are final
+        L.check(lib.sat_step_fault_flag(words, nw, L.ptr(self._fault_sticky), L.ptr(self.fault_slot), L.stream()), "sat_step_fault_flag")
+
+    def scst_forward_backward(self, images, image_index, scorer, end_id=2, steps=20, next_images=None):
+        """`forward_backward` for the self-critical loss (`scst.SelfCritical`, Rennie et al. 2017): same look-ahead, cached [B, E]
+        features accepted, gradients straight into the flat buffer, loss into the loss slot, fault flag.  The decoder part is the
+        sampled rollout (`sat_rollout_decoder_fwd`), the greedy decode as baseline, CIDEr of both on the device, `sat_scst_weights`
+        + `sat_ce_rows_weighted` in place on the step's logits, and the teacher-forced backward on the tokens drawn.  The decoder
+        arithmetic of this step is EXACT F32 whatever `decoder_gemm_dtype` says: the draws are taken from exact-f32 logits and
+        the backward runs on them (the bf16 decoder GEMMs are not wired into this step).  Rewards, baseline and ids of the step
+        are kept on `last_scst`."""
+        lib, model, flat = self.lib, self.model, self.flat
+        dec = model.decoder
+        if not model.training:
+            raise RuntimeError("TrainStep needs model.train() (batch-statistics BatchNorm, train.py never calls eval())")
+        dev = images.device
+        B, steps = images.shape[0], int(steps)
+        bufs = self._step_bufs(B, B * steps, dev)
+        feats_in, pooled = self._head_forward(images, bufs, next_images)
+        params = dict(dec.named_parameters())
+        loss_slot = flat.grads[flat.loss_slot:flat.loss_slot + 1]
+        seed = draw_ss_seed()
+        ids, logits, tapes, pi = rollout_forward(lib, feats_in, params, steps, seed, dec.ss_rank, self.lstm_ws, logits=bufs["logits"])
+        dec.last_rollout_seed = seed
+        sc = self.last_scst = SelfCritical(scorer, end_id)
+        sc.last_reward, sc.last_baseline, sc.last_greedy_ids = sc.rewards(dec, feats_in, ids, image_index)
+        sc.last_ids = ids
+        w, _, _ = scst_weights(ids, sc.last_reward, sc.last_baseline, end_id)
+        ce_rows_weighted(logits[:, :dec.vocab_size], ids, w, write_grad=True, loss_out=loss_slot)
+        g = {name: flat.grad("decoder." + name) for name in params}
+        g["features"] = bufs["d_feat"]
+        decoder_backward(lib, logits, tapes, params, pi, g, self.lstm_ws)
+        self._head_backward(bufs, pooled, feats_in)
         return loss_slot
 
     def check_ids(self):
@@ -371,6 +417,13 @@ class TrainStep:
         following batch's images, optional) starts that batch's frozen conv stack under this one's decoder work."""
         n_tokens = sum(int(l) - 1 for l in lengths)
         loss = self.forward_backward((images, captions, lengths), 1.0 / n_tokens, next_images=next_images).clone()
+        self.optimizer_step(lr)
+        return loss
+
+    def scst_step(self, images, image_index, scorer, lr=None, next_images=None, end_id=2, steps=20):
+        """One whole self-critical iteration (`scst_forward_backward` + `optimizer_step`); returns the loss as a 1-element device
+        tensor (no host sync).  The decoder arithmetic of this step is exact f32 whatever `decoder_gemm_dtype` is."""
+        loss = self.scst_forward_backward(images, image_index, scorer, end_id, steps, next_images).clone()
         self.optimizer_step(lr)
         return loss
 
