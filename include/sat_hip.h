@@ -732,6 +732,32 @@ int sat_scst_weights(const int64_t* ids, int64_t stride, int B, int T, int64_t e
 int sat_ce_rows_weighted(float* logits /*[N,ldl]*/, int64_t ldl, const int64_t* ids, int64_t ids_stride, int B, int N, int V,
                          const float* w /*[N]*/, int write_grad, float* row_loss /*[N]*/, float* loss_out /*[1] or NULL*/,
                          sat_stream_t stream);
+/* The rollout of the Show-Attend-Tell decoder (added within ABI 18): the training-form recurrence of model2.py:38-85 for all B rows
+ * over all `steps` steps as ONE call, no host synchronisation -- sat_ss_attend_fwd's loop (the same five launches per step: weight_hh
+ * projection from h_{t-1} with h_{-1} = h0, attention with its context written into X's context half, LSTMCell, output layer, vocab
+ * projection with exact-f32 logits stored) with batch_sizes = [B] * steps, packed row n = t*B + b.  The embedding half of step 0 is
+ * embed[start_id], of step t >= 1 embed[ids[b][t-1]].
+ *   greedy == 0: ids[b][t] = s(b, t) drawn from step t's own logits with sat_rollout_decoder_fwd's convention exactly (counter
+ *     (v >> 2, b, t, 2*rank), word v & 3; every row draws at every step, no mask draw, no teacher).
+ *   greedy != 0: ids[b][t] = the first maximal column of step t's logits (sat_vocab_argmax's rule); seed and rank are ignored.  This
+ *     is the greedy decode of the policy the draws come from (h0 / c0 from init_lstm, every step its own context), not model2.py's
+ *     `sample` (zero state, lagging context): the baseline of a self-critical loss.
+ * Rows keep running behind <end>; sat_scst_weights masks them.  feats, ctx_enc, h0, c0, w (SAT_SSA_* order), tapes as for
+ * sat_ss_attend_fwd; prefix: DEVICE int32 [steps+1], prefix[t] = t*B (as for sat_pack_tokens).  Outputs: ids [B][ids_stride >=
+ * steps]; fed [B][fed_stride >= steps] = [start_id | ids[:, :steps-1]], the tokens fed; toks [steps*B], fed packed; logits [steps*B,
+ * ldl] (ldl % 4 == 0, pad columns untouched); the eight SAT_SSA_* tapes holding exactly what the teacher-forced forward on `fed`
+ * leaves in them (Zin included; Z as sat_ss_attend_fwd leaves it, the per-step output-layer rows), so that forward's backward
+ * applies unchanged.  ids and fed must not overlap.
+ * SAT_ERR_ARG (null pointers; steps < 1; start_id outside [0, V); B*steps > INT_MAX; the size rules of sat_ss_attend_fwd),
+ * SAT_ERR_UNSUPPORTED and SAT_ERR_WORKSPACE come back before anything is enqueued.  workspace:
+ * sat_rollout_attend_fwd_ws_bytes(B, P, C, E, H, V) = sat_ss_attend_fwd's layout with the draw region max(sat_ss_decoder_fwd_ws_bytes,
+ * sat_vocab_argmax_ws_bytes)(B, V); 0 for non-positive sizes. */
+int64_t sat_rollout_attend_fwd_ws_bytes(int B, int P, int C, int E, int H, int V);
+int sat_rollout_attend_fwd(const float* feats, const float* ctx_enc, const float* h0, const float* c0,
+                           const int32_t* prefix /*[steps+1] device*/, int B, int steps, int P, int C, int E, int H, int V,
+                           const float* const* w /*[host]*/, float* const* tapes /*[host]*/, int64_t* toks, float* logits, int64_t ldl,
+                           int greedy, int64_t start_id, uint64_t seed, int rank, int64_t* ids, int64_t ids_stride, int64_t* fed,
+                           int64_t fed_stride, float* workspace, int64_t ws_bytes, sat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * clip_gradient (train.py:88-91) + optim.Adam step (train.py:56,146) over one flat buffer.

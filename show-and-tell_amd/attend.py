@@ -8,7 +8,8 @@
                sat_attention_fwd (tanh / softmax / weighted mean, model2.py:73-78), sat_lstmcell_fwd (model2.py:58);
                output_layer batched over all packed rows after the loop (model2.py:80-85); in training with ss_prob > 0
                (scheduled sampling, train.py:109-113) the whole loop, output layer and Gumbel-max draws per step, is one
-               `sat_ss_attend_fwd` call
+               `sat_ss_attend_fwd` call; `rollout` (self-critical training, `scst_forward`) feeds the decoder its own tokens --
+               drawn, or the arg-max -- through the same per-step launches as one `sat_rollout_attend_fwd` call
     backward : hand-written (sat_attention_bwd, LSTMCell BPTT, batched weight-gradient GEMMs) behind torch.autograd, so
                `loss.backward()` (train.py:144) works unchanged; `finetune(allow=True)` (model2.py:87-89) adds the conv-stack
                backward (f32 mode): dgrad = the forward conv kernel on flipped weights, wgrad = split-K GEMMs over the flat
@@ -457,6 +458,65 @@ def _ss_attend_forward(ctx, lib, m, f2, fmean, ctx_enc, h0, c0, HSX, captions, p
     return logits
 
 
+class _AttendRolloutFn(torch.autograd.Function):
+    """The rollout of the decoder half (self-critical training): `sat_rollout_attend_fwd` feeds every step the token it took from
+    the previous step's logits -- a draw, or the arg-max -- and leaves the tapes of the teacher-forced forward on those tokens, so
+    the backward is `attend_backward` on `fed`."""
+
+    @staticmethod
+    def forward(ctx, model, features, fmean, steps, greedy, start_id, seed, rank, out, *params):
+        """out: dict that receives "ids" [B, steps], "fed" [B, steps] (the tokens fed) and "alphas", the packed attention tape"""
+        lib = L.load()
+        m = model
+        dev = features.device
+        B, P, C = features.shape
+        E, H, V = m.embed_size, m.hidden_size, m.vocab_size
+        pi = PackInfo.get([steps] * B, dev)
+        N = pi.N
+        f2 = features.view(B * P, C)
+        ctx_enc = torch.empty(B * P, C, device=dev)
+        _gemm(lib, 0, 1, f2, C, m.image_att_w, C, ctx_enc, C, B * P, C, C)                      # model2.py:46
+        HSX = torch.empty(B + N, H, device=dev)            # [h_0 ; h of every packed row], as in _AttendFn.forward
+        h0, c0 = HSX[:B], torch.empty(B, H, device=dev)
+        _gemm(lib, 0, 0, fmean, C, m.init_hidden.weight, C, h0, H, B, H, C, m.init_hidden.bias)  # model2.py:67-71
+        _gemm(lib, 0, 0, fmean, C, m.init_memory.weight, C, c0, H, B, H, C, m.init_memory.bias)
+        tp = dict(PROJ=torch.empty(N, C, device=dev), ALPHA=torch.empty(N, P, device=dev), X=torch.empty(N, H, device=dev),
+                  GATES=torch.empty(N, 4 * H, device=dev), CS=torch.empty(N, H, device=dev), HS=HSX[B:],
+                  Zin=torch.empty(N, C + H, device=dev), Z=torch.empty(N, E, device=dev))
+        st = L.stream()
+        Wz = torch.empty(E, C + H, device=dev)                 # [W_c2o | W_h2o]: the backward's dZin = dZ Wz
+        L.check(lib.sat_rows_copy(L.ptr(m.context2out.weight), C, None, 0, E, E, C, L.ptr(Wz), C + H, st), "sat_rows_copy")
+        L.check(lib.sat_rows_copy(L.ptr(m.hidden2tout.weight), H, None, 0, E, E, H, Wz.data_ptr() + C * 4, C + H, st), "sat_rows_copy")
+        named = dict(m.named_parameters())
+        w = (L.C.c_void_p * len(_SS_WEIGHTS))(*[named[k].data_ptr() for k in _SS_WEIGHTS])
+        tapes = (L.C.c_void_p * len(_SS_TAPES))(*[tp[k].data_ptr() for k in _SS_TAPES])
+        toks = torch.empty(N, dtype=torch.int64, device=dev)
+        ids = torch.empty(B, steps, dtype=torch.int64, device=dev)
+        fed = torch.empty(B, steps, dtype=torch.int64, device=dev)
+        logits = L.logits_buffer(N, V, dev)
+        wsb = lib.sat_rollout_attend_fwd_ws_bytes(B, P, C, E, H, V)
+        ws = torch.empty(wsb // 4, device=dev)
+        L.check(lib.sat_rollout_attend_fwd(f2.data_ptr(), ctx_enc.data_ptr(), h0.data_ptr(), c0.data_ptr(), pi.prefix_dev.data_ptr(),
+                                           B, steps, P, C, E, H, V, w, tapes, toks.data_ptr(), logits.data_ptr(), logits.shape[1],
+                                           1 if greedy else 0, start_id, seed, rank, ids.data_ptr(), ids.stride(0), fed.data_ptr(),
+                                           fed.stride(0), ws.data_ptr(), wsb, st), "sat_rollout_attend_fwd")
+        if not greedy:
+            # The loop's Z rows came from per-step split-K GEMMs (the draws need each step's logits).  The backward reads Z once, for
+            # the classifier's weight gradient: give it the tape `_AttendFn.forward` leaves -- the output layer over all packed rows
+            # as ONE GEMM with the two biases added in turn -- so that the gradients are, bit for bit, those of `decode` on `fed`.
+            _gemm(lib, 0, 0, tp["Zin"], C + H, Wz, C + H, tp["Z"], E, N, E, C + H, m.context2out.bias, m.hidden2tout.bias)
+        out["ids"], out["fed"], out["alphas"] = ids, fed, tp["ALPHA"]
+        ctx.m, ctx.pi, ctx.captions = m, pi, fed
+        ctx.tapes = dict(f2=f2, fmean=fmean, ctx_enc=ctx_enc, h0=h0, c0=c0, Wz=Wz, toks=toks, HSX=HSX, **tp)
+        return logits if logits.shape[1] == V else logits[:, :V]
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        from .attend_bwd import attend_backward
+        grads, d_feats, d_fmean = attend_backward(ctx.m, ctx.pi, ctx.captions, ctx.tapes, dlogits, want_dfeat=ctx.needs_input_grad[1])
+        return (None, d_feats, d_fmean if ctx.needs_input_grad[2] else None) + (None,) * 6 + tuple(grads)
+
+
 class _VggFn(torch.autograd.Function):
     """the conv stack WITH a backward (fine-tuning, model2.py:87-89 `finetune(allow=True)`): f32 parity mode, or bf16 forward /
     bf16 input-gradient convs with f32 master weights and f32 weight gradients (compute_dtype='bf16')"""
@@ -517,6 +577,8 @@ class ShowAttendTellModel(nn.Module):
         self.last_ss_inputs = self.last_ss_seed = None   # tokens fed [B, T] and seed of the last sampled forward
         self.alpha_c = 0                  # weight of the doubly stochastic attention penalty (Xu et al. 2015, section 4.2.1); 0 = off
         self.last_alphas = self.last_attention_penalty = None    # set by every decode / forward
+        self.last_rollout_inputs = self.last_rollout_seed = None # tokens fed [B, steps] and seed of the last `rollout`
+        self.last_scst = None                                    # the `SelfCritical` object of the last `scst_forward`
         self._programs, self._guard = {}, None
         self._pf_list = []          # features in flight: [(images, feats, fmean, event, weights signature, instance)]
         self.register_load_state_dict_post_hook(lambda mod, k: mod._programs.clear())
@@ -658,6 +720,58 @@ class ShowAttendTellModel(nn.Module):
         if ss is not None:
             self.last_ss_inputs, self.last_ss_seed = ss["used"], ss["seed"]
         return out
+
+    def rollout(self, features, fmean, steps=20, greedy=False, start_id=1):
+        """The decoder half of `forward` fed its OWN tokens (self-critical sequence training, Rennie et al. 2017): step 0 takes
+        <start>, step t >= 1 the token of step t-1 -- a DRAW from softmax(logits of step t-1), or with `greedy` their arg-max.
+        Returns (ids i64 [B, steps], logits f32 [steps * B, V]), logits row t * B + b those of step t of row b.  One
+        `sat_rollout_attend_fwd` call, nothing read back.  Training mode only.
+
+        Sampled: the logits carry autograd -- their backward is the teacher-forced backward on the tokens fed, which stay as
+        `last_rollout_inputs` ([B, steps] = [start_id | ids[:, :steps-1]]).  The seed comes from torch's CPU generator
+        (`draw_ss_seed`) and is kept as `last_rollout_seed`; the draws are `ss_rank`'s stream.  Rows keep running behind their
+        <end>: `scst_loss` masks them.
+
+        greedy=True: no graph (the logits come back detached), no seed consumed, `last_rollout_seed` untouched.  This is the
+        arg-max decode of the policy the draws come from -- h0 / c0 from init_lstm and every step its own context -- and so the
+        baseline of a self-critical loss; `sample()` keeps model2.py:91-111's zero state and lagging context and is another decode.
+
+        Either way `last_alphas` is the packed [steps * B, P] attention tape: `.view(steps, B, P)` is where the model looked for
+        each word it emitted.  `ss_prob` and `alpha_c` do not act on a rollout, and `last_attention_penalty` is set to None:
+        `sat_attention_coverage` counts every step a row is alive in, and here every row is alive behind its <end>, so the penalty
+        would pull the maps of steps the loss masks towards covering the image.  (A length-masked penalty is a separate change.)"""
+        if not self.training:
+            raise RuntimeError("ShowAttendTellModel.rollout is a training forward (model.train()); eval mode decodes with sample()")
+        L.require_gpu(features, "features")
+        L.require_gpu(fmean, "fmean")
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("steps must be >= 1")
+        if features.dtype != torch.float32 or fmean.dtype != torch.float32:
+            raise TypeError("features and fmean must be float32")
+        features, fmean = features.contiguous(), fmean.contiguous()
+        out = {}
+        if greedy:
+            with torch.no_grad():
+                logits = _AttendRolloutFn.apply(self, features, fmean, steps, True, int(start_id), 0, 0, out, *self._params())
+        else:
+            from .models import draw_ss_seed
+            seed = draw_ss_seed()
+            logits = _AttendRolloutFn.apply(self, features, fmean, steps, False, int(start_id), seed, int(self.ss_rank), out,
+                                            *self._params())
+            self.last_rollout_seed = seed
+        self.last_rollout_inputs, self.last_alphas, self.last_attention_penalty = out["fed"], out["alphas"], None
+        return out["ids"], logits
+
+    def scst_forward(self, images, image_index, scorer, end_id=2, steps=20):
+        """The self-critical loss of one batch (`scst.SelfCritical.attend`) behind the conv stack: sampled rollout, arg-max rollout
+        of the same policy as the baseline, CIDEr of both, weighted cross entropy.  image_index: the corpus image of every row, as
+        for `CiderScorer.score`.  With `finetune(allow=True)` `loss.backward()` also reaches the conv stack.  The `SelfCritical`
+        object (its last_reward, last_baseline, last_ids, last_greedy_ids) is kept as `last_scst`."""
+        from .scst import SelfCritical
+        feats, fmean = self._encode(images)
+        self.last_scst = SelfCritical(scorer, end_id)
+        return self.last_scst.attend(self, feats, fmean, image_index, steps)
 
     @torch.no_grad()
     def sample(self, images, states=None, return_alphas=False):

@@ -71,20 +71,32 @@ __global__ __launch_bounds__(256) void ss_init_used_kernel(const int64_t* __rest
     used[b * used_stride + j] = captions[b * cap_stride + j];
 }
 
+// the select of one sampling step for rows 0 .. m_sel-1, from the partials sat_skinny_sample left in `workspace` for M rows
+int select_step(int M, int m_sel, int V, float ss_prob, uint64_t seed, int t, int rank, const int64_t* teacher, long teacher_stride,
+                int64_t* ids, long ids_stride, const float* embed, int E, float* x, long x_stride, float* workspace, hipStream_t s) {
+    if (m_sel < 1) return SAT_OK;
+    const int ncg = sat_cdiv(V, 16);
+    hipLaunchKernelGGL(ss_select_kernel, dim3(m_sel), dim3(256), 0, s, workspace, (const int*)(workspace + (long)M * ncg), ncg,
+                       (unsigned)t, 2u * (unsigned)rank + 1u, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), ss_prob, teacher,
+                       teacher_stride, ids, ids_stride, embed, E, V, x, x_stride);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
+// the projection of one sampling step: M rows (+ optional logits store), Gumbel-max partials into `workspace`
+int sample_project(const float* h, const float* lin_w, const float* lin_b, int M, int H, int V, float* logits, long ldl, uint64_t seed,
+                   int t, int rank, float* workspace, hipStream_t s) {
+    return sat_skinny_sample(h, lin_w, lin_b, M, H, V, logits, ldl, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), (unsigned)t,
+                             2u * (unsigned)rank, workspace, (int*)(workspace + (long)M * sat_cdiv(V, 16)), s);
+}
+
 // one sampling step: projection of M rows (+ optional logits store) and the draw for the first m_sel <= M of them
 int sample_step(const float* h, const float* lin_w, const float* lin_b, int M, int m_sel, int H, int V, float* logits, long ldl,
                 float ss_prob, uint64_t seed, int t, int rank, const int64_t* teacher, long teacher_stride, int64_t* ids,
                 long ids_stride, const float* embed, int E, float* x, long x_stride, float* workspace, hipStream_t s) {
-    const int ncg = sat_cdiv(V, 16);
-    float* pmax = workspace;
-    int* pidx = (int*)(workspace + (long)M * ncg);
-    const unsigned k0 = (unsigned)(seed & 0xffffffffu), k1 = (unsigned)(seed >> 32);
-    SAT_TRY(sat_skinny_sample(h, lin_w, lin_b, M, H, V, logits, ldl, k0, k1, (unsigned)t, 2u * (unsigned)rank, pmax, pidx, s));
-    if (m_sel < 1) return SAT_OK;
-    hipLaunchKernelGGL(ss_select_kernel, dim3(m_sel), dim3(256), 0, s, pmax, pidx, ncg, (unsigned)t, 2u * (unsigned)rank + 1u, k0,
-                       k1, ss_prob, teacher, teacher_stride, ids, ids_stride, embed, E, V, x, x_stride);
-    SAT_LAUNCH_CHECK();
-    return SAT_OK;
+    SAT_TRY(sample_project(h, lin_w, lin_b, M, H, V, logits, ldl, seed, t, rank, workspace, s));
+    return select_step(M, m_sel, V, ss_prob, seed, t, rank, teacher, teacher_stride, ids, ids_stride, embed, E, x, x_stride, workspace,
+                       s);
 }
 
 }  // namespace
@@ -225,12 +237,13 @@ constexpr long kWsAlign = 256;
 
 long ws_round(long n) { return (n + kWsAlign - 1) / kWsAlign * kWsAlign; }
 
-// byte offsets of the pieces of sat_ss_attend_fwd's workspace; the last entry is the total
+// byte offsets of the pieces of the attention loop's workspace; the last entry is the total
 struct SsAttendWs {
     long sample, att, skinny, cell, zbias, total;
 };
 
-SsAttendWs ss_attend_ws(int B, int P, int C, int E, int H, int V) {
+// draw_bytes: the draw partials [B][cdiv(V,16)] (value, column) of sat_skinny_sample or sat_vocab_argmax
+SsAttendWs ss_attend_ws(int B, int P, int C, int E, int H, int V, long draw_bytes) {
     long sk = 0;                                          // split-K slabs of the two per-step GEMMs, for every row count <= B
     for (int m = 1; m <= B; ++m) {
         const long a = sat_skinny_gemm_ws_bytes(m, C, H), b = sat_skinny_gemm_ws_bytes(m, E, C);
@@ -239,7 +252,7 @@ SsAttendWs ss_attend_ws(int B, int P, int C, int E, int H, int V) {
     }
     SsAttendWs w;
     w.sample = 0;
-    w.att = w.sample + ws_round(sat_ss_decoder_fwd_ws_bytes(B, V));
+    w.att = w.sample + ws_round(draw_bytes);
     w.skinny = w.att + ws_round(sat_attention_ws_bytes(B, P));
     w.cell = w.skinny + ws_round(sk);
     w.zbias = w.cell + ws_round((long)B * H * sizeof(float));
@@ -247,11 +260,82 @@ SsAttendWs ss_attend_ws(int B, int P, int C, int E, int H, int V) {
     return w;
 }
 
+long rollout_draw_bytes(int B, int V) {
+    const long a = sat_ss_decoder_fwd_ws_bytes(B, V), b = sat_vocab_argmax_ws_bytes(B, V);
+    return a > b ? a : b;
+}
+
+// what sat_attention_fwd would refuse only after earlier steps had been enqueued
+bool attention_fits(int P, int C) { return (long)2 * C * 4 <= 60 * 1024 && (long)(((P + 3) & ~3) + 8 + 8 * 64) * 4 <= 60 * 1024; }
+
+// the weights, tapes and workspace pieces of one decoder loop (sat_ss_attend_fwd, sat_rollout_attend_fwd)
+struct AttendLoop {
+    const float *feats, *ctx_enc, *w_whh, *b_whh, *w_att, *embed, *w_ih, *w_hh, *b_ih, *b_hh, *w_c2o, *w_h2o, *w_cls, *b_cls;
+    float *PROJ, *ALPHA, *X, *GATES, *CS, *HS, *Zin, *Z;
+    float *sample_ws, *att_ws, *sk_ws, *cell, *zbias;
+    long att_bytes, sk_bytes;
+    int P, C, E, H, V;
+    sat_stream_t stream;
+};
+
+AttendLoop attend_loop(const float* feats, const float* ctx_enc, int P, int C, int E, int H, int V, const float* const* w,
+                       float* const* tapes, float* workspace, const SsAttendWs& lay, sat_stream_t stream) {
+    char* base = (char*)workspace;
+    AttendLoop a;
+    a.feats = feats; a.ctx_enc = ctx_enc;
+    a.w_whh = w[SAT_SSA_WEIGHT_HH_W]; a.b_whh = w[SAT_SSA_WEIGHT_HH_B]; a.w_att = w[SAT_SSA_WEIGHT_ATT];
+    a.embed = w[SAT_SSA_EMBEDDING];
+    a.w_ih = w[SAT_SSA_CELL_W_IH]; a.w_hh = w[SAT_SSA_CELL_W_HH]; a.b_ih = w[SAT_SSA_CELL_B_IH]; a.b_hh = w[SAT_SSA_CELL_B_HH];
+    a.w_c2o = w[SAT_SSA_C2O_W]; a.w_h2o = w[SAT_SSA_H2O_W]; a.w_cls = w[SAT_SSA_CLS_W]; a.b_cls = w[SAT_SSA_CLS_B];
+    a.PROJ = tapes[SAT_SSA_PROJ]; a.ALPHA = tapes[SAT_SSA_ALPHA]; a.X = tapes[SAT_SSA_X]; a.GATES = tapes[SAT_SSA_GATES];
+    a.CS = tapes[SAT_SSA_CS]; a.HS = tapes[SAT_SSA_HS]; a.Zin = tapes[SAT_SSA_ZIN]; a.Z = tapes[SAT_SSA_Z];
+    a.sample_ws = (float*)(base + lay.sample);
+    a.att_ws = (float*)(base + lay.att);
+    a.sk_ws = (float*)(base + lay.skinny);
+    a.cell = (float*)(base + lay.cell);
+    a.zbias = (float*)(base + lay.zbias);
+    a.att_bytes = lay.skinny - lay.att;
+    a.sk_bytes = lay.cell - lay.skinny;
+    a.P = P; a.C = C; a.E = E; a.H = H; a.V = V;
+    a.stream = stream;
+    return a;
+}
+
+// One step of the loop for the n rows at packed offset `off`, five launches: weight_hh(h_{t-1}) (model2.py:74), the attention with
+// its context into X's context half (model2.py:55-57, 73-78), the LSTMCell, the output layer (model2.py:80-84) Z = ctx W_c2o^T +
+// h W_h2o^T + (b_c2o + b_h2o), and the vocab projection into lg -- with the Gumbel-max partials of counter (.., t_draw, 2*rank) left
+// in sample_ws (draw), or alone.
+int attend_step(const AttendLoop& a, const float* hprev, long off, int n, float* lg, long ldl, bool draw, uint64_t seed, int t_draw,
+                int rank) {
+    const int P = a.P, C = a.C, E = a.E, H = a.H, Hin = a.H;
+    hipStream_t s = (hipStream_t)a.stream;
+    float* x = a.X + off * Hin;
+    SAT_TRY(sat_skinny_gemm2_f32(hprev, H, a.w_whh, H, H, nullptr, 0, nullptr, 0, 0, 0, n, C, a.b_whh, a.PROJ + off * C, C, a.sk_ws,
+                                 a.sk_bytes, a.stream));
+    SAT_TRY(sat_attention_fwd(a.ctx_enc, a.feats, a.PROJ + off * C, C, a.w_att, n, P, C, a.ALPHA + off * P, x + E, Hin, a.att_ws,
+                              a.att_bytes, a.stream));
+    SAT_TRY(sat_lstmcell_fwd(x, hprev, a.cell, a.w_ih, a.w_hh, a.b_ih, a.b_hh, n, Hin, H, a.HS + off * H, a.GATES + off * 4L * H,
+                             a.CS + off * H, a.stream));
+    SAT_TRY(sat_skinny_gemm2_f32(x + E, Hin, a.w_c2o, C, C, a.HS + off * H, H, a.w_h2o, H, H, 0, n, E, a.zbias, a.Z + off * E, E,
+                                 a.sk_ws, a.sk_bytes, a.stream));
+    if (draw) return sample_project(a.Z + off * E, a.w_cls, a.b_cls, n, E, a.V, lg, ldl, seed, t_draw, rank, a.sample_ws, s);
+    return sat_skinny_store(a.Z + off * E, E, a.w_cls, E, 0, n, a.V, E, 1, lg, ldl, 0, a.b_cls, s);
+}
+
+// after the loop: the output layer's input tape [ctx | h] of every row (attend_backward's dWz) and the packed tokens actually fed
+// (its embedding scatter)
+int attend_finish(const AttendLoop& a, const int64_t* fed, long fed_stride, const int32_t* prefix, int T, long N, int64_t* toks) {
+    const int C = a.C, H = a.H;
+    SAT_TRY(sat_rows_copy(a.X + a.E, H, nullptr, 0, N, (int)N, C, a.Zin, C + H, a.stream));
+    SAT_TRY(sat_rows_copy(a.HS, H, nullptr, 0, N, (int)N, H, a.Zin + C, C + H, a.stream));
+    return sat_pack_tokens(fed, fed_stride, prefix, T, (int)N, 0, toks, a.stream);
+}
+
 }  // namespace
 
 extern "C" int64_t sat_ss_attend_fwd_ws_bytes(int B, int P, int C, int E, int H, int V) {
     if (B < 1 || P < 1 || C < 1 || E < 1 || H < 1 || V < 1) return 0;
-    return ss_attend_ws(B, P, C, E, H, V).total;
+    return ss_attend_ws(B, P, C, E, H, V, sat_ss_decoder_fwd_ws_bytes(B, V)).total;
 }
 
 extern "C" int sat_ss_attend_fwd(const float* feats, const float* ctx_enc, const float* h0, const float* c0, const int64_t* captions,
@@ -274,64 +358,97 @@ extern "C" int sat_ss_attend_fwd(const float* feats, const float* ctx_enc, const
         if (batch_sizes[t] < 1 || (t > 0 && batch_sizes[t] > batch_sizes[t - 1])) return SAT_ERR_ARG;
         N += batch_sizes[t];
     }
-    // what sat_attention_fwd would refuse only after earlier steps had been enqueued
-    if ((long)2 * C * 4 > 60 * 1024 || (long)(((P + 3) & ~3) + 8 + 8 * 64) * 4 > 60 * 1024) return SAT_ERR_UNSUPPORTED;
-    const SsAttendWs lay = ss_attend_ws(B, P, C, E, H, V);
+    if (!attention_fits(P, C)) return SAT_ERR_UNSUPPORTED;
+    const SsAttendWs lay = ss_attend_ws(B, P, C, E, H, V, sat_ss_decoder_fwd_ws_bytes(B, V));
     if (ws_bytes < lay.total) return SAT_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    char* base = (char*)workspace;
-    float* sample_ws = (float*)(base + lay.sample);
-    float* att_ws = (float*)(base + lay.att);
-    float* sk_ws = (float*)(base + lay.skinny);
-    float* cell = (float*)(base + lay.cell);
-    float* zbias = (float*)(base + lay.zbias);
-    const long att_bytes = lay.skinny - lay.att, sk_bytes = lay.cell - lay.skinny;
-    const float *w_whh = w[SAT_SSA_WEIGHT_HH_W], *b_whh = w[SAT_SSA_WEIGHT_HH_B], *w_att = w[SAT_SSA_WEIGHT_ATT];
-    const float* embed = w[SAT_SSA_EMBEDDING];
-    const float *w_ih = w[SAT_SSA_CELL_W_IH], *w_hh = w[SAT_SSA_CELL_W_HH], *b_ih = w[SAT_SSA_CELL_B_IH], *b_hh = w[SAT_SSA_CELL_B_HH];
-    const float *w_c2o = w[SAT_SSA_C2O_W], *w_h2o = w[SAT_SSA_H2O_W], *w_cls = w[SAT_SSA_CLS_W], *b_cls = w[SAT_SSA_CLS_B];
-    float *PROJ = tapes[SAT_SSA_PROJ], *ALPHA = tapes[SAT_SSA_ALPHA], *X = tapes[SAT_SSA_X], *GATES = tapes[SAT_SSA_GATES];
-    float *CS = tapes[SAT_SSA_CS], *HS = tapes[SAT_SSA_HS], *Zin = tapes[SAT_SSA_ZIN], *Z = tapes[SAT_SSA_Z];
-    const int Hin = H;
+    const AttendLoop a = attend_loop(feats, ctx_enc, P, C, E, H, V, w, tapes, workspace, lay, stream);
 
-    SAT_TRY(sat_rows_add(w[SAT_SSA_C2O_B], E, w[SAT_SSA_H2O_B], E, 1, E, zbias, E, stream));
+    SAT_TRY(sat_rows_add(w[SAT_SSA_C2O_B], E, w[SAT_SSA_H2O_B], E, 1, E, a.zbias, E, stream));
     // used = the teacher's tokens; X's embedding half = their rows (draws overwrite both, step by step)
     hipLaunchKernelGGL(ss_init_used_kernel, dim3(sat_cdiv((long)B * T, 256)), dim3(256), 0, s, captions, (long)cap_stride, B, T, used,
                        (long)used_stride);
     SAT_LAUNCH_CHECK();
     SAT_TRY(sat_pack_tokens(used, used_stride, prefix, T, (int)N, 0, toks, stream));
-    SAT_TRY(sat_rows_copy(embed, E, toks, 1, V, (int)N, E, X, Hin, stream));
-    hipError_t e = hipMemcpyAsync(cell, c0, (size_t)B * H * sizeof(float), hipMemcpyDeviceToDevice, s);
+    SAT_TRY(sat_rows_copy(a.embed, E, toks, 1, V, (int)N, E, a.X, H, stream));
+    hipError_t e = hipMemcpyAsync(a.cell, c0, (size_t)B * H * sizeof(float), hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) return (int)e;
     long off = 0, prev = 0;
     for (int t = 0; t < T; ++t) {
         const int n = batch_sizes[t];
         const int n_next = (t + 1 < T) ? batch_sizes[t + 1] : 0;
-        const float* hprev = t == 0 ? h0 : HS + prev * H;
-        float* x = X + off * Hin;
-        // model2.py:74 weight_hh(hidden), then the attention with its context into X's context half (model2.py:55-57, 73-78)
-        SAT_TRY(sat_skinny_gemm2_f32(hprev, H, w_whh, H, H, nullptr, 0, nullptr, 0, 0, 0, n, C, b_whh, PROJ + off * C, C, sk_ws,
-                                     sk_bytes, stream));
-        SAT_TRY(sat_attention_fwd(ctx_enc, feats, PROJ + off * C, C, w_att, n, P, C, ALPHA + off * P, x + E, Hin, att_ws, att_bytes,
-                                  stream));
-        SAT_TRY(sat_lstmcell_fwd(x, hprev, cell, w_ih, w_hh, b_ih, b_hh, n, Hin, H, HS + off * H, GATES + off * 4L * H, CS + off * H,
-                                 stream));
-        // output_layer (model2.py:80-84) of this step's rows: Z = ctx W_c2o^T + h W_h2o^T + (b_c2o + b_h2o)
-        SAT_TRY(sat_skinny_gemm2_f32(x + E, Hin, w_c2o, C, C, HS + off * H, H, w_h2o, H, H, 0, n, E, zbias, Z + off * E, E, sk_ws,
-                                     sk_bytes, stream));
-        float* lg = logits + off * ldl;
-        if (n_next) {
-            // the input of step t+1: a draw from this step's logits where mask(b, t+1) holds, the teacher's token elsewhere
-            SAT_TRY(sample_step(Z + off * E, w_cls, b_cls, n, n_next, E, V, lg, ldl, ss_prob, seed, t + 1, rank, captions + t + 1,
-                                cap_stride, used + t + 1, used_stride, embed, E, X + (off + n) * Hin, Hin, sample_ws, s));
-        } else {
-            SAT_TRY(sat_skinny_store(Z + off * E, E, w_cls, E, 0, n, V, E, 1, lg, ldl, 0, b_cls, s));
-        }
+        // the last step projects only; before it, the input of step t+1 is a draw from this step's logits where mask(b, t+1) holds,
+        // the teacher's token elsewhere
+        SAT_TRY(attend_step(a, t == 0 ? h0 : a.HS + prev * H, off, n, logits + off * ldl, ldl, n_next > 0, seed, t + 1, rank));
+        SAT_TRY(select_step(n, n_next, V, ss_prob, seed, t + 1, rank, captions + t + 1, cap_stride, used + t + 1, used_stride, a.embed,
+                            E, a.X + (off + n) * H, H, a.sample_ws, s));
         prev = off;
         off += n;
     }
-    // the output layer's input tape [ctx | h] of every row (attend_backward's dWz) and the tokens actually fed (its embedding scatter)
-    SAT_TRY(sat_rows_copy(X + E, Hin, nullptr, 0, N, (int)N, C, Zin, C + H, stream));
-    SAT_TRY(sat_rows_copy(HS, H, nullptr, 0, N, (int)N, H, Zin + C, C + H, stream));
-    return sat_pack_tokens(used, used_stride, prefix, T, (int)N, 0, toks, stream);
+    return attend_finish(a, used, used_stride, prefix, T, N, toks);
+}
+
+// ---- sampled / arg-max rollout of the attention decoder (self-critical sequence training on the model train.py:37 builds) --------
+// The loop above with batch_sizes = [B] * steps, <start> at step 0 and ids[b][t-1] fed to step t >= 1, where ids[b][t] comes from step
+// t's OWN logits (counter t, as sat_rollout_decoder_fwd): the Gumbel-max draw, or with `greedy` the first maximal column -- the
+// greedy decode of the very policy the draws come from (h0 / c0 from init_lstm, no lagging context), which is what a self-critical
+// baseline needs.  fed = [start_id | ids[:, :steps-1]]; the tapes are those of the teacher-forced forward on fed.
+extern "C" int64_t sat_rollout_attend_fwd_ws_bytes(int B, int P, int C, int E, int H, int V) {
+    if (B < 1 || P < 1 || C < 1 || E < 1 || H < 1 || V < 1) return 0;
+    return ss_attend_ws(B, P, C, E, H, V, rollout_draw_bytes(B, V)).total;
+}
+
+extern "C" int sat_rollout_attend_fwd(const float* feats, const float* ctx_enc, const float* h0, const float* c0,
+                                      const int32_t* prefix, int B, int steps, int P, int C, int E, int H, int V,
+                                      const float* const* w, float* const* tapes, int64_t* toks, float* logits, int64_t ldl, int greedy,
+                                      int64_t start_id, uint64_t seed, int rank, int64_t* ids, int64_t ids_stride, int64_t* fed,
+                                      int64_t fed_stride, float* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    if (!feats || !ctx_enc || !h0 || !c0 || !prefix || !w || !tapes || !toks || !logits || !ids || !fed || !workspace)
+        return SAT_ERR_ARG;
+    if (B < 1 || steps < 1 || P < 1 || C < 4 || (C & 3) || E < 4 || (E & 3) || H != E + C || V < 1) return SAT_ERR_ARG;
+    if (!greedy && rank < 0) return SAT_ERR_ARG;
+    if (start_id < 0 || start_id >= V || (long)B * steps > 0x7fffffffL) return SAT_ERR_ARG;
+    if (ids_stride < steps || fed_stride < steps || ldl < V || (ldl & 3)) return SAT_ERR_ARG;
+    for (int k = 0; k < SAT_SSA_NUM_WEIGHTS; ++k)
+        if (!w[k]) return SAT_ERR_ARG;
+    for (int k = 0; k < SAT_SSA_NUM_TAPES; ++k)
+        if (!tapes[k]) return SAT_ERR_ARG;
+    if (!attention_fits(P, C)) return SAT_ERR_UNSUPPORTED;
+    const long draw_bytes = rollout_draw_bytes(B, V);
+    const SsAttendWs lay = ss_attend_ws(B, P, C, E, H, V, draw_bytes);
+    if (ws_bytes < lay.total) return SAT_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const AttendLoop a = attend_loop(feats, ctx_enc, P, C, E, H, V, w, tapes, workspace, lay, stream);
+    const long N = (long)B * steps;
+
+    SAT_TRY(sat_rows_add(w[SAT_SSA_C2O_B], E, w[SAT_SSA_H2O_B], E, 1, E, a.zbias, E, stream));
+    // step 0 feeds <start>: toks[0 .. B) = start_id (0 + start_id), fed's column 0 = those, X's embedding half = their rows
+    hipError_t e = hipMemsetAsync(toks, 0, (size_t)B * sizeof(int64_t), s);
+    if (e != hipSuccess) return (int)e;
+    SAT_TRY(sat_counter_add(toks, B, start_id, stream));
+    hipLaunchKernelGGL(ss_init_used_kernel, dim3(sat_cdiv((long)B, 256)), dim3(256), 0, s, toks, 1L, B, 1, fed, (long)fed_stride);
+    SAT_LAUNCH_CHECK();
+    SAT_TRY(sat_rows_copy(a.embed, E, toks, 1, V, B, E, a.X, H, stream));
+    e = hipMemcpyAsync(a.cell, c0, (size_t)B * H * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return (int)e;
+    for (int t = 0; t < steps; ++t) {
+        const long off = (long)t * B;
+        const bool more = t + 1 < steps;
+        float* x_next = more ? a.X + (off + B) * H : nullptr;
+        SAT_TRY(attend_step(a, t == 0 ? h0 : a.HS + (off - B) * H, off, B, logits + off * ldl, ldl, !greedy, seed, t, rank));
+        // ids[b][t]; its embedding row is step t+1's input (the last step's token is a target only)
+        if (!greedy) {
+            SAT_TRY(select_step(B, B, V, 1.0f, seed, t, rank, nullptr, 0, ids + t, ids_stride, more ? a.embed : nullptr, E, x_next, H,
+                                a.sample_ws, s));
+        } else {
+            SAT_TRY(sat_vocab_argmax(a.Z + off * E, a.w_cls, a.b_cls, B, E, V, ids + t, ids_stride, a.sample_ws, draw_bytes, stream));
+            if (more) SAT_TRY(sat_rows_copy(a.embed, E, ids + t, ids_stride, V, B, E, x_next, H, stream));
+        }
+    }
+    if (steps > 1) {                                          // fed[:, 1:] = ids[:, :steps-1]
+        hipLaunchKernelGGL(ss_init_used_kernel, dim3(sat_cdiv((long)B * (steps - 1), 256)), dim3(256), 0, s, ids, (long)ids_stride, B,
+                           steps - 1, fed + 1, (long)fed_stride);
+        SAT_LAUNCH_CHECK();
+    }
+    return attend_finish(a, fed, fed_stride, prefix, steps, N, toks);
 }

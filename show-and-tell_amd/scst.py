@@ -10,7 +10,12 @@ With `len[b]` the sampled tokens of row b up to and including its first <end> an
     loss = sum over b, t < len[b] of (reward[b] - baseline[b]) / M * -log softmax(logits[t * B + b])[ids[b][t]]
 
 `sat_scst_weights` makes the per-row weights, `sat_ce_rows_weighted` the loss and d(loss)/d(logits); the arithmetic is stated at
-both in include/sat_hip.h.  `TrainStep.scst_step` is the fused form.  There is no CPU path."""
+both in include/sat_hip.h.  `TrainStep.scst_step` is the fused form.  There is no CPU path.
+
+For the attention model (`ShowAttendTellModel`, the model `train.py:37` builds):
+
+    loss = sc.attend(model, features, fmean, image_index)    # `model.rollout` sampled, and with greedy=True as the baseline
+    loss = model.scst_forward(images, image_index, scorer)   # the same behind the conv stack"""
 import torch
 
 from . import _lib as L
@@ -114,6 +119,21 @@ class SelfCritical:
     def __call__(self, decoder, features, image_index, steps=20):
         ids, logits = decoder.rollout(features, steps)
         reward, baseline, greedy = self.rewards(decoder, features, ids, image_index)
+        loss = scst_loss(logits, ids, reward, baseline, self.end_id)
+        self.last_reward, self.last_baseline, self.last_ids, self.last_greedy_ids = reward, baseline, ids, greedy
+        return loss
+
+    def attend(self, model, features, fmean, image_index, steps=20):
+        """The same for the attention model (`ShowAttendTellModel`): `model.rollout(features, fmean, steps)` sampled, and
+        `model.rollout(..., greedy=True)` -- the arg-max decode of the same policy, which consumes no seed -- as the baseline.
+        Leaves the same last_* fields as `__call__`."""
+        ids, logits = model.rollout(features, fmean, steps)
+        fed, alphas = model.last_rollout_inputs, model.last_alphas        # the sampled rollout's: what the backward belongs to
+        greedy, _ = model.rollout(features, fmean, steps, greedy=True)
+        model.last_rollout_inputs, model.last_alphas = fed, alphas
+        kept_s, kept_g = kept_tokens(ids, self.end_id), kept_tokens(greedy, self.end_id)
+        _, reward = self.scorer.score(ids, image_index, end_id=self.end_id, kept=kept_s)
+        _, baseline = self.scorer.score(greedy, image_index, end_id=self.end_id, kept=kept_g)
         loss = scst_loss(logits, ids, reward, baseline, self.end_id)
         self.last_reward, self.last_baseline, self.last_ids, self.last_greedy_ids = reward, baseline, ids, greedy
         return loss
