@@ -700,6 +700,59 @@ int sat_cider_score(const sat_cider_corpus* corpus /*[host]*/, const int64_t* id
                     double* scores /*[B]*/, double* mean /*[1]*/, sat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * BLEU-1..4 and ROUGE-L of decoded id rows against reference captions (added within ABI 18): the other plain-arithmetic metrics
+ * of language_eval (eval.py:17-56).  Rows, `kept` / end_id, image_index and the flat corpus are those of sat_cider_score: ids is
+ * [B] rows of T <= 64 int64, `stride` elements apart; row b has L tokens, L = kept[b] clamped to [0, T] or, with kept NULL, the
+ * position of its first end_id; image_index[b] is clamped into the corpus; an id outside [0, 2^31) equals no reference token and
+ * still counts in L.  One wave per row, n-grams compared token by token (no trie, no table); no allocation, no host sync.
+ *
+ * sat_bleu_comps: cook_test + compute_score(option='closest') (pycocoevalcap/bleu/bleu_scorer.py:60-83, 198-256), per row
+ *   testlen    = L
+ *   reflen     = the length l of a reference of the image that minimises (|l - L|, l): a tie goes to the shorter
+ *   guess[k]   = max(0, L - k)                                                            k = 0..3, (k+1)-grams
+ *   correct[k] = sum over the row's DISTINCT (k+1)-grams g of min(count of g in the row, max over the image's references of
+ *                the count of g in that reference) -- the maximum may come from another reference for each g
+ *   comps[b]   = { testlen, reflen, guess[0..3], correct[0..3] }                         int64 [B][10]: exact
+ *   p          = 1;  for k = 0..3:  p = p * ((correct[k] + 1e-15) / (guess[k] + 1e-9));  s[k] = pow(p, 1 / (k + 1))
+ *   ratio      = (testlen + 1e-15) / (reflen + 1e-9);  if ratio < 1:  s[k] = s[k] * exp(1 - 1 / ratio)
+ *   sentence[b] = s                                                                      f64 [B][4]: the per-image bleu_list
+ *   mean[k]    = sum over b of sentence[b][k] (fixed order) / B                          f64 [4], or NULL: not computed
+ *   totals[j] += sum over b of comps[b][j]                                               device int64 [10], or NULL: untouched
+ *   (64-bit integer atomics: integer sums, so the same bits in any order.  The caller zeroes totals where a corpus begins.)
+ * sat_bleu_finalize: bleu[k], f64 [4], the same p / pow / ratio / exp arithmetic on totals: the corpus-level Bleu_1..4 of every
+ *   row added since totals was zeroed.  One wave.
+ * sat_rouge_l_score: Rouge.calc_score (pycocoevalcap/rouge/rouge.py:45-75).  The reference splits with split(" "), so an EMPTY
+ *   caption (row or reference) is ONE token, which equals only the token of another empty caption; with len() counted that way
+ *   lcs(r)   = length of the longest common subsequence of the row and reference r      an integer: exact
+ *   prec_max = max over the image's references of lcs(r) / len(row);  rec_max = max over them of lcs(r) / len(r)
+ *   score    = ((1 + beta*beta) * prec_max * rec_max) / (rec_max + beta*beta * prec_max), or 0 when either maximum is 0
+ *   scores[b] = score, f64 [B];  mean[0] = sum of the B scores (fixed order) / B.
+ *   The LCS is bit-parallel: the row's positions are the bits of one 64-bit word V (all ones at first); per reference token with
+ *   match mask M:  U = V & M;  V = (V + U) | (V - U);  lcs = zero bits of V below len(row).
+ * Two calls give the same bits.
+ * SAT_ERR_ARG before anything is enqueued: a NULL pointer (kept, and sat_bleu_comps's mean and totals, excepted); n_refs,
+ * n_images, n_tokens, max_ref_tokens, B or T <= 0; stride < T; beta not finite or <= 0.  SAT_ERR_UNSUPPORTED: T > 64,
+ * max_ref_tokens > 128.
+ */
+typedef struct sat_ref_corpus {
+    const int32_t* ref_tokens;     /* [n_tokens] device: the reference captions back to back (sat_cider_corpus's array) */
+    const int32_t* ref_offsets;    /* [n_refs + 1] device: caption r is ref_tokens[ref_offsets[r] .. ref_offsets[r+1]) */
+    const int32_t* image_offsets;  /* [n_images + 1] device: image i owns captions image_offsets[i] .. image_offsets[i+1] */
+    int64_t n_tokens;
+    int32_t n_refs, n_images;
+    int32_t max_ref_tokens;        /* the longest reference caption, as the host counted it */
+    int32_t reserved;
+} sat_ref_corpus;
+int sat_bleu_comps(const sat_ref_corpus* corpus /*[host]*/, const int64_t* ids, int64_t stride, int B, int T,
+                   const int32_t* kept /*[B] or NULL*/, int64_t end_id, const int32_t* image_index /*[B]*/,
+                   int64_t* comps /*[B][10]*/, double* sentence /*[B][4]*/, double* mean /*[4] or NULL*/,
+                   int64_t* totals /*[10] or NULL*/, sat_stream_t stream);
+int sat_bleu_finalize(const int64_t* totals /*[10]*/, double* bleu /*[4]*/, sat_stream_t stream);
+int sat_rouge_l_score(const sat_ref_corpus* corpus /*[host]*/, const int64_t* ids, int64_t stride, int B, int T,
+                      const int32_t* kept /*[B] or NULL*/, int64_t end_id, const int32_t* image_index /*[B]*/, double beta,
+                      double* scores /*[B]*/, double* mean /*[1]*/, sat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Self-critical sequence training (Rennie et al. 2017; added within ABI 18): a caption SAMPLED from the model is trained with its
  * cross entropy weighted by CIDEr(sampled) - CIDEr(greedy).  Nothing here synchronises or reads back; every entry point returns
  * SAT_ERR_ARG for null or impossible arguments and SAT_ERR_WORKSPACE for a short workspace before anything is enqueued.

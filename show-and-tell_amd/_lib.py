@@ -43,6 +43,12 @@ class SatCiderCorpus(C.Structure):
                 ("n_nodes", C.c_int32), ("n_refs", C.c_int32), ("n_images", C.c_int32), ("max_ref_tokens", C.c_int32)]
 
 
+class SatRefCorpus(C.Structure):
+    """mirror of `struct sat_ref_corpus` (include/sat_hip.h)"""
+    _fields_ = [("ref_tokens", _vp), ("ref_offsets", _vp), ("image_offsets", _vp), ("n_tokens", C.c_int64),
+                ("n_refs", C.c_int32), ("n_images", C.c_int32), ("max_ref_tokens", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SatOp(C.Structure):
     """mirror of `struct sat_op` (include/sat_hip.h); no instance attributes besides the fields, so a misspelt field raises"""
     __slots__ = ()
@@ -181,6 +187,9 @@ SIGNATURES = {
     "sat_cider_table_insert": (_i, [_vp, _i, _vp, _vp, _i64, _vp, _vp]),
     "sat_cider_ref_stats": (_i, [C.POINTER(SatCiderCorpus), _vp, _vp]),
     "sat_cider_score": (_i, [C.POINTER(SatCiderCorpus), _vp, _i64, _i, _i, _vp, _i64, _vp, C.c_double, _vp, _vp, _vp]),
+    "sat_bleu_comps": (_i, [C.POINTER(SatRefCorpus), _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sat_bleu_finalize": (_i, [_vp, _vp, _vp]),
+    "sat_rouge_l_score": (_i, [C.POINTER(SatRefCorpus), _vp, _i64, _i, _i, _vp, _i64, _vp, C.c_double, _vp, _vp, _vp]),
     "sat_rollout_decoder_fwd_ws_bytes": (_i64, [_i, _i]),
     "sat_rollout_decoder_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_vp), _i, _i, _vp, _vp, C.POINTER(_vp), _vp, _vp, _i64,
                                      C.c_uint64, _i, _vp, _i64, _vp, _i64, _vp]),
@@ -204,7 +213,8 @@ SIGNATURES = {
 ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_attention_coverage_ws_bytes", "sat_attention_coverage",
                     "sat_attention_bwd_ex", "sat_beam_backtrack_rows", "sat_cider_table_insert", "sat_cider_ref_stats", "sat_cider_score",
                     "sat_rollout_decoder_fwd_ws_bytes", "sat_rollout_decoder_fwd", "sat_scst_weights", "sat_ce_rows_weighted",
-                    "sat_rollout_attend_fwd_ws_bytes", "sat_rollout_attend_fwd")
+                    "sat_rollout_attend_fwd_ws_bytes", "sat_rollout_attend_fwd", "sat_bleu_comps", "sat_bleu_finalize",
+                    "sat_rouge_l_score")
 
 _lib = None
 

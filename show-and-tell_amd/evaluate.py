@@ -11,8 +11,9 @@ the already truncated rows.
 
 Of `language_eval` (eval.py:15-55) the one number the reference's trainer acts on is here: with a `CiderScorer` (cider.py) and
 the batch's `image_index`, `validation_step` also returns CIDEr (`lang_stats['CIDEr']`, train.py:169-177) of the decoded rows,
-per caption and as the batch mean, still without a host sync.  The reference words must already be tokenised: the PTB tokenizer
-(Java) and BLEU, METEOR, ROUGE and SPICE stay out of scope."""
+per caption and as the batch mean, still without a host sync.  With a `BleuScorer` / `RougeLScorer` (langstats.py) it returns
+the per-caption Bleu_1..4 (and accumulates the corpus totals) and ROUGE_L the same way.  The reference words must already be
+tokenised: the PTB tokenizer, METEOR and SPICE (Java) stay out of scope."""
 import torch
 
 from . import _lib as L
@@ -63,12 +64,18 @@ def kept_tokens(ids, end_id):
 
 
 @torch.no_grad()
-def validation_step(model, images, captions, lengths, state=None, end_id=2, beam_size=1, scorer=None, image_index=None):
+def validation_step(model, images, captions, lengths, state=None, end_id=2, beam_size=1, scorer=None, image_index=None,
+                    bleu=None, rouge=None):
     """One iteration of the loop body eval.py:71-118 (the caller has put the model in eval mode, eval.py:65).
     Returns dict(loss f32[1], ids i64[B,20], kept i32[B]) -- all on the device, nothing synchronised.  With a `CiderScorer`
-    and `image_index` (the corpus image of every row) the dict gains cider f64[1] and cider_scores f64[B] of `ids`."""
-    if (scorer is None) != (image_index is None):
-        raise ValueError("scorer and image_index go together")
+    and `image_index` (the corpus image of every row) the dict gains cider f64[1] and cider_scores f64[B] of `ids`; with a
+    `BleuScorer` as `bleu`, bleu_scores f64[B,4] (and `bleu.update` has run on the rows: `bleu.compute()` after the last batch
+    is the corpus Bleu_1..4); with a `RougeLScorer` as `rouge`, rouge_l f64[1] and rouge_l_scores f64[B]."""
+    if bleu is None and rouge is None:
+        if (scorer is None) != (image_index is None):
+            raise ValueError("scorer and image_index go together")
+    elif image_index is None:
+        raise ValueError("bleu and rouge need image_index, the corpus image of every row")
     if model.training:
         raise RuntimeError("validation_step expects model.eval() (eval.py:65)")
     targets, _ = pack_validation_targets(captions, lengths)
@@ -85,6 +92,10 @@ def validation_step(model, images, captions, lengths, state=None, end_id=2, beam
     out = {"loss": loss, "ids": ids, "kept": kept_tokens(ids, end_id)}
     if scorer is not None:
         out["cider"], out["cider_scores"] = scorer.score(ids, image_index, end_id=end_id, kept=out["kept"])
+    if bleu is not None:
+        out["bleu_scores"] = bleu.update(ids, image_index, end_id=end_id, kept=out["kept"])
+    if rouge is not None:
+        out["rouge_l"], out["rouge_l_scores"] = rouge.score(ids, image_index, end_id=end_id, kept=out["kept"])
     return out
 
 
