@@ -252,8 +252,13 @@ def check(rc, what=""):
 
 
 def ptr(t):
-    """device pointer of a torch tensor (or None)."""
-    return None if t is None else t.data_ptr()
+    """device pointer of a torch tensor; None and a raw address pass through."""
+    return t if t is None or isinstance(t, int) else t.data_ptr()
+
+
+def rows(t, row0=0):
+    """device pointer of row `row0` of a 2-D contiguous f32 tensor"""
+    return t.data_ptr() + row0 * t.shape[1] * 4
 
 
 def stream():
@@ -294,3 +299,24 @@ def counter_add(t, value=1):
     """t += value for an int64 device tensor (BatchNorm's `num_batches_tracked`), through the library: no torch operator computes
     anything on the product path"""
     check(load().sat_counter_add(t.data_ptr(), t.numel(), value, stream()), "sat_counter_add")
+
+
+_SKINNY_WS = {}
+_SKINNY_ROWS = int(os.environ.get("SAT_SKINNY_ROWS", "128"))   # per-step GEMMs with at most this many rows take the split-K kernel
+
+
+def gemm(lib, amode, bmode, A, lda, B, ldb, Cout, ldc, M, N, K, bias=None, bias2=None):
+    """C[M,N] = op(A) op(B) + bias (+ bias2), f32; A, B, Cout: tensors or raw addresses.  A 64 x 64-tiled GEMM of a 64-row decode
+    step runs on N/64 workgroups; those go to sat_skinny_gemm_f32, which splits K over waves and grid slices instead."""
+    if amode == 0 and M <= _SKINNY_ROWS and bias2 is None and ldc == N and K % 4 == 0 and lda % 4 == 0 and (bmode == 1 or ldb % 4 == 0):
+        import torch
+        need = lib.sat_skinny_gemm_ws_bytes(M, N, K)
+        dev = torch.cuda.current_device()
+        ws = _SKINNY_WS.get(dev)
+        if ws is None or ws.numel() * 4 < need:
+            ws = _SKINNY_WS[dev] = torch.empty(max(need // 4, 1 << 20), dtype=torch.float32, device="cuda")
+        check(lib.sat_skinny_gemm_f32(ptr(A), lda, ptr(B), ldb, bmode, M, N, K, ptr(bias), ptr(Cout), ldc,
+                                      ws.data_ptr(), ws.numel() * 4, stream()), "sat_skinny_gemm_f32")
+        return
+    check(lib.sat_gemm_f32(amode, bmode, ptr(A), lda, ptr(B), ldb, ptr(Cout), ldc, ptr(bias), ptr(bias2), M, N, K, stream()),
+          "sat_gemm_f32")

@@ -6,15 +6,16 @@ d_alpha on the device."""
 import torch
 
 from . import _lib as L
-from .attend import _gemm
 
-
-def _rows(t, r0):
-    return t.data_ptr() + r0 * t.shape[1] * 4
+# the decoder's parameters (state_dict names) in the order `attend_backward` returns their gradients
+PARAM_ORDER = ("image_att_w", "init_hidden.weight", "init_hidden.bias", "init_memory.weight", "init_memory.bias",
+               "weight_hh.weight", "weight_hh.bias", "weight_att", "embedding.weight", "lstmcell.weight_ih", "lstmcell.weight_hh",
+               "lstmcell.bias_ih", "lstmcell.bias_hh", "context2out.weight", "context2out.bias", "hidden2tout.weight",
+               "hidden2tout.bias", "classifier.weight", "classifier.bias")
 
 
 def attend_backward(m, pi, captions, tp, dlogits, want_dfeat=False, d_alpha_extra=None, d_alpha_scale=None):
-    """Returns (gradients in `attend.PARAM_ORDER`, d_features [B,P,C] or None, d_fmean [B,C] or None); the last two only when
+    """Returns (gradients in `PARAM_ORDER`, d_features [B,P,C] or None, d_fmean [B,C] or None); the last two only when
     the conv stack is being fine-tuned (model2.py:87-89).  d_alpha_extra [B,P] / d_alpha_scale (device scalar): a second consumer
     of the attention maps (the coverage penalty) -- every step's d_alpha gains d_alpha_scale * d_alpha_extra[b] for its rows b."""
     lib, st = L.load(), L.stream()
@@ -31,13 +32,13 @@ def attend_backward(m, pi, captions, tp, dlogits, want_dfeat=False, d_alpha_extr
     g = {}
     # ---- output_layer (model2.py:80-85), batched over all packed rows ----
     g["classifier.weight"] = torch.empty(V, E, device=dev)
-    _gemm(lib, 2, 1, dlogits, ldl, Z, E, g["classifier.weight"], E, V, E, N)                # dW = dlogits^T Z
+    L.gemm(lib, 2, 1, dlogits, ldl, Z, E, g["classifier.weight"], E, V, E, N)                # dW = dlogits^T Z
     g["classifier.bias"] = torch.empty(V, device=dev)
     L.check(lib.sat_colsum_f32(dlogits.data_ptr(), ldl, N, V, g["classifier.bias"].data_ptr(), st), "sat_colsum_f32")
     dZ = torch.empty(N, E, device=dev)
-    _gemm(lib, 0, 1, dlogits, ldl, m.classifier.weight, E, dZ, E, N, E, V)                   # dZ = dlogits W_cls
+    L.gemm(lib, 0, 1, dlogits, ldl, m.classifier.weight, E, dZ, E, N, E, V)                   # dZ = dlogits W_cls
     dWz = torch.empty(E, C + H, device=dev)
-    _gemm(lib, 2, 1, dZ, E, Zin, C + H, dWz, C + H, E, C + H, N)
+    L.gemm(lib, 2, 1, dZ, E, Zin, C + H, dWz, C + H, E, C + H, N)
     g["context2out.weight"], g["hidden2tout.weight"] = torch.empty(E, C, device=dev), torch.empty(E, H, device=dev)
     L.check(lib.sat_rows_copy(dWz.data_ptr(), C + H, None, 0, E, E, C, g["context2out.weight"].data_ptr(), C, st), "sat_rows_copy")
     L.check(lib.sat_rows_copy(dWz.data_ptr() + C * 4, C + H, None, 0, E, E, H, g["hidden2tout.weight"].data_ptr(), H, st), "sat_rows_copy")
@@ -45,7 +46,7 @@ def attend_backward(m, pi, captions, tp, dlogits, want_dfeat=False, d_alpha_extr
     L.check(lib.sat_colsum_f32(dZ.data_ptr(), E, N, E, g["context2out.bias"].data_ptr(), st), "sat_colsum_f32")
     g["hidden2tout.bias"] = g["context2out.bias"].clone()
     dZin = torch.empty(N, C + H, device=dev)
-    _gemm(lib, 0, 1, dZ, E, Wz, C + H, dZin, C + H, N, C + H, E)                             # d[ctx | h] = dZ [W_c2o | W_h2o]
+    L.gemm(lib, 0, 1, dZ, E, Wz, C + H, dZin, C + H, N, C + H, E)                             # d[ctx | h] = dZ [W_c2o | W_h2o]
     DH = torch.empty(N, H, device=dev)
     L.check(lib.sat_rows_copy(dZin.data_ptr() + C * 4, C + H, None, 0, N, N, H, DH.data_ptr(), H, st), "sat_rows_copy")
     # ---- the recurrence, last step first (model2.py:54-62) ----
@@ -62,26 +63,26 @@ def attend_backward(m, pi, captions, tp, dlogits, want_dfeat=False, d_alpha_extr
     for t in reversed(range(T)):
         bs, r0 = pi.batch_sizes[t], pi.prefix[t]
         n_carry = pi.batch_sizes[t + 1] if t + 1 < T else 0
-        cprev = c0.data_ptr() if t == 0 else _rows(CS, pi.prefix[t - 1])
-        L.check(lib.sat_lstmcell_bwd_point(_rows(DH, r0), dh_carry.data_ptr() if n_carry else None, n_carry, _rows(GATES, r0),
-                                           _rows(CS, r0), cprev, dc_state.data_ptr(), _rows(DG, r0), bs, H, st), "sat_lstmcell_bwd_point")
-        _gemm(lib, 0, 1, _rows(DG, r0), 4 * H, m.lstmcell.weight_ih, Hin, _rows(DX, r0), Hin, bs, Hin, 4 * H)   # d[emb | ctx]
+        cprev = c0.data_ptr() if t == 0 else L.rows(CS, pi.prefix[t - 1])
+        L.check(lib.sat_lstmcell_bwd_point(L.rows(DH, r0), dh_carry.data_ptr() if n_carry else None, n_carry, L.rows(GATES, r0),
+                                           L.rows(CS, r0), cprev, dc_state.data_ptr(), L.rows(DG, r0), bs, H, st), "sat_lstmcell_bwd_point")
+        L.gemm(lib, 0, 1, L.rows(DG, r0), 4 * H, m.lstmcell.weight_ih, Hin, L.rows(DX, r0), Hin, bs, Hin, 4 * H)   # d[emb | ctx]
         # d context = its LSTMCell-input half + its output_layer half (summed where the attention backward reads it); the
         # projection weight_hh(h_{t-1}) comes from the forward's tape
         if d_alpha_extra is None:
-            L.check(lib.sat_attention_bwd(ctx_enc.data_ptr(), f2.data_ptr(), _rows(PROJ, r0), C, watt.data_ptr(), _rows(ALPHA, r0),
-                                          _rows(DX, r0) + E * 4, Hin, _rows(dZin, r0), C + H, bs, P, C, d_ctx_enc.data_ptr(),
-                                          _rows(DPROJ, r0), _rows(DWATT, r0), d_feats.data_ptr() if d_feats is not None else None,
+            L.check(lib.sat_attention_bwd(ctx_enc.data_ptr(), f2.data_ptr(), L.rows(PROJ, r0), C, watt.data_ptr(), L.rows(ALPHA, r0),
+                                          L.rows(DX, r0) + E * 4, Hin, L.rows(dZin, r0), C + H, bs, P, C, d_ctx_enc.data_ptr(),
+                                          L.rows(DPROJ, r0), L.rows(DWATT, r0), d_feats.data_ptr() if d_feats is not None else None,
                                           att_ws.data_ptr(), att_ws.numel() * 4, st), "sat_attention_bwd")
         else:                                              # row index = image index: the same [B, P] serves every step
-            L.check(lib.sat_attention_bwd_ex(ctx_enc.data_ptr(), f2.data_ptr(), _rows(PROJ, r0), C, watt.data_ptr(), _rows(ALPHA, r0),
-                                             _rows(DX, r0) + E * 4, Hin, _rows(dZin, r0), C + H, d_alpha_extra.data_ptr(), P,
-                                             d_alpha_scale.data_ptr(), bs, P, C, d_ctx_enc.data_ptr(), _rows(DPROJ, r0),
-                                             _rows(DWATT, r0), d_feats.data_ptr() if d_feats is not None else None,
+            L.check(lib.sat_attention_bwd_ex(ctx_enc.data_ptr(), f2.data_ptr(), L.rows(PROJ, r0), C, watt.data_ptr(), L.rows(ALPHA, r0),
+                                             L.rows(DX, r0) + E * 4, Hin, L.rows(dZin, r0), C + H, d_alpha_extra.data_ptr(), P,
+                                             d_alpha_scale.data_ptr(), bs, P, C, d_ctx_enc.data_ptr(), L.rows(DPROJ, r0),
+                                             L.rows(DWATT, r0), d_feats.data_ptr() if d_feats is not None else None,
                                              att_ws.data_ptr(), att_ws.numel() * 4, st), "sat_attention_bwd_ex")
         # dh_{t-1} = DG_t W_hh (through the LSTMCell) + DPROJ_t W_whh (through the attention projection): one launch
-        L.check(lib.sat_skinny_gemm2_f32(_rows(DG, r0), 4 * H, m.lstmcell.weight_hh.data_ptr(), H, 4 * H,
-                                         _rows(DPROJ, r0), C, m.weight_hh.weight.data_ptr(), H, C, 1, bs, H, None,
+        L.check(lib.sat_skinny_gemm2_f32(L.rows(DG, r0), 4 * H, m.lstmcell.weight_hh.data_ptr(), H, 4 * H,
+                                         L.rows(DPROJ, r0), C, m.weight_hh.weight.data_ptr(), H, C, 1, bs, H, None,
                                          dh_carry.data_ptr(), H, sk_ws.data_ptr(), sk_ws.numel() * 4, st), "sat_skinny_gemm2_f32")
     g["weight_att"] = torch.empty(C, device=dev)
     L.check(lib.sat_colsum_f32(DWATT.data_ptr(), C, N, C, g["weight_att"].data_ptr(), st), "sat_colsum_f32")
@@ -92,25 +93,25 @@ def attend_backward(m, pi, captions, tp, dlogits, want_dfeat=False, d_alpha_extr
     L.check(lib.sat_rows_copy(tp["HSX"].data_ptr(), H, pi.prev_rows().data_ptr(), 1, B + N, N, H, HPREV.data_ptr(), H, st),
             "sat_rows_copy")
     g["lstmcell.weight_ih"] = torch.empty(4 * H, Hin, device=dev)
-    _gemm(lib, 2, 1, DG, 4 * H, X, Hin, g["lstmcell.weight_ih"], Hin, 4 * H, Hin, N)
+    L.gemm(lib, 2, 1, DG, 4 * H, X, Hin, g["lstmcell.weight_ih"], Hin, 4 * H, Hin, N)
     g["lstmcell.weight_hh"] = torch.empty(4 * H, H, device=dev)
-    _gemm(lib, 2, 1, DG, 4 * H, HPREV, H, g["lstmcell.weight_hh"], H, 4 * H, H, N)
+    L.gemm(lib, 2, 1, DG, 4 * H, HPREV, H, g["lstmcell.weight_hh"], H, 4 * H, H, N)
     g["lstmcell.bias_ih"] = torch.empty(4 * H, device=dev)
     L.check(lib.sat_colsum_f32(DG.data_ptr(), 4 * H, N, 4 * H, g["lstmcell.bias_ih"].data_ptr(), st), "sat_colsum_f32")
     g["lstmcell.bias_hh"] = g["lstmcell.bias_ih"].clone()
     g["weight_hh.weight"] = torch.empty(C, H, device=dev)
-    _gemm(lib, 2, 1, DPROJ, C, HPREV, H, g["weight_hh.weight"], H, C, H, N)
+    L.gemm(lib, 2, 1, DPROJ, C, HPREV, H, g["weight_hh.weight"], H, C, H, N)
     g["weight_hh.bias"] = torch.empty(C, device=dev)
     L.check(lib.sat_colsum_f32(DPROJ.data_ptr(), C, N, C, g["weight_hh.bias"].data_ptr(), st), "sat_colsum_f32")
     # ---- init_lstm (model2.py:67-71): dh0 = dh_carry, dc0 = dc_state ----
     for name, d in (("init_hidden", dh_carry), ("init_memory", dc_state)):
         g[name + ".weight"] = torch.empty(H, C, device=dev)
-        _gemm(lib, 2, 1, d, H, fmean, C, g[name + ".weight"], C, H, C, B)
+        L.gemm(lib, 2, 1, d, H, fmean, C, g[name + ".weight"], C, H, C, B)
         g[name + ".bias"] = torch.empty(H, device=dev)
         L.check(lib.sat_colsum_f32(d.data_ptr(), H, B, H, g[name + ".bias"].data_ptr(), st), "sat_colsum_f32")
     # ---- image_att_w (model2.py:46): context_encode = features @ W  =>  dW = features^T d_ctx_enc ----
     g["image_att_w"] = torch.empty(C, C, device=dev)
-    _gemm(lib, 2, 1, f2, C, d_ctx_enc, C, g["image_att_w"], C, C, C, f2.shape[0])
+    L.gemm(lib, 2, 1, f2, C, d_ctx_enc, C, g["image_att_w"], C, C, C, f2.shape[0])
     g["weight_att"] = g["weight_att"].view(C, 1)
     # ---- embedding (dense gradient, nn.Embedding default): deterministic scatter of the per-row input gradients ----
     toks = tp["toks"]
@@ -121,14 +122,13 @@ def attend_backward(m, pi, captions, tp, dlogits, want_dfeat=False, d_alpha_extr
     if want_dfeat:
         # context_encode = features @ W  =>  d features += d_ctx_enc @ W^T
         tmp = torch.empty_like(ctx_enc)
-        _gemm(lib, 0, 0, d_ctx_enc, C, m.image_att_w, C, tmp, C, f2.shape[0], C, C)
+        L.gemm(lib, 0, 0, d_ctx_enc, C, m.image_att_w, C, tmp, C, f2.shape[0], C, C)
         L.check(lib.sat_rows_add(d_feats.data_ptr(), C, tmp.data_ptr(), C, f2.shape[0], C, d_feats.data_ptr(), C, st), "sat_rows_add")
         # init_lstm: h0 = fmean Wh^T + b, c0 = fmean Wc^T + b  =>  d fmean = dh0 Wh + dc0 Wc
         da, db_ = torch.empty(B, C, device=dev), torch.empty(B, C, device=dev)
-        _gemm(lib, 0, 1, dh_carry, H, m.init_hidden.weight, C, da, C, B, C, H)
-        _gemm(lib, 0, 1, dc_state, H, m.init_memory.weight, C, db_, C, B, C, H)
+        L.gemm(lib, 0, 1, dh_carry, H, m.init_hidden.weight, C, da, C, B, C, H)
+        L.gemm(lib, 0, 1, dc_state, H, m.init_memory.weight, C, db_, C, B, C, H)
         d_fmean = torch.empty(B, C, device=dev)
         L.check(lib.sat_rows_add(da.data_ptr(), C, db_.data_ptr(), C, B, C, d_fmean.data_ptr(), C, st), "sat_rows_add")
         d_feats = d_feats.view(B, P, C)
-    from .attend import PARAM_ORDER
     return [g[k] for k in PARAM_ORDER], d_feats, d_fmean

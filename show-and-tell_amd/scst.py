@@ -106,22 +106,29 @@ class SelfCritical:
         self.scorer, self.end_id = scorer, int(end_id)
         self.last_reward = self.last_baseline = self.last_ids = self.last_greedy_ids = None
 
+    def _score(self, ids, greedy_ids, image_index):
+        """(reward, baseline): the scorer's per-row score of the sampled rows and of the greedy rows, each up to its <end>"""
+        kept_s, kept_g = kept_tokens(ids, self.end_id), kept_tokens(greedy_ids, self.end_id)
+        _, reward = self.scorer.score(ids, image_index, end_id=self.end_id, kept=kept_s)
+        _, baseline = self.scorer.score(greedy_ids, image_index, end_id=self.end_id, kept=kept_g)
+        return reward, baseline
+
+    def _finish(self, logits, ids, greedy_ids, reward, baseline):
+        loss = scst_loss(logits, ids, reward, baseline, self.end_id)
+        self.last_reward, self.last_baseline, self.last_ids, self.last_greedy_ids = reward, baseline, ids, greedy_ids
+        return loss
+
     def rewards(self, decoder, features, ids, image_index):
         """(reward, baseline, greedy ids) for sampled `ids`: CIDEr of the sampled rows and of the greedy decode"""
         greedy = decoder.sample(features)
         if greedy.dim() == 1:                                # squeezed at batch 1 (models.py:67)
             greedy = greedy.view(1, -1)
-        kept_s, kept_g = kept_tokens(ids, self.end_id), kept_tokens(greedy, self.end_id)
-        _, reward = self.scorer.score(ids, image_index, end_id=self.end_id, kept=kept_s)
-        _, baseline = self.scorer.score(greedy, image_index, end_id=self.end_id, kept=kept_g)
-        return reward, baseline, greedy
+        return self._score(ids, greedy, image_index) + (greedy,)
 
     def __call__(self, decoder, features, image_index, steps=20):
         ids, logits = decoder.rollout(features, steps)
         reward, baseline, greedy = self.rewards(decoder, features, ids, image_index)
-        loss = scst_loss(logits, ids, reward, baseline, self.end_id)
-        self.last_reward, self.last_baseline, self.last_ids, self.last_greedy_ids = reward, baseline, ids, greedy
-        return loss
+        return self._finish(logits, ids, greedy, reward, baseline)
 
     def attend(self, model, features, fmean, image_index, steps=20):
         """The same for the attention model (`ShowAttendTellModel`): `model.rollout(features, fmean, steps)` sampled, and
@@ -131,9 +138,5 @@ class SelfCritical:
         fed, alphas = model.last_rollout_inputs, model.last_alphas        # the sampled rollout's: what the backward belongs to
         greedy, _ = model.rollout(features, fmean, steps, greedy=True)
         model.last_rollout_inputs, model.last_alphas = fed, alphas
-        kept_s, kept_g = kept_tokens(ids, self.end_id), kept_tokens(greedy, self.end_id)
-        _, reward = self.scorer.score(ids, image_index, end_id=self.end_id, kept=kept_s)
-        _, baseline = self.scorer.score(greedy, image_index, end_id=self.end_id, kept=kept_g)
-        loss = scst_loss(logits, ids, reward, baseline, self.end_id)
-        self.last_reward, self.last_baseline, self.last_ids, self.last_greedy_ids = reward, baseline, ids, greedy
-        return loss
+        reward, baseline = self._score(ids, greedy, image_index)
+        return self._finish(logits, ids, greedy, reward, baseline)

@@ -477,3 +477,28 @@ def test_attend_beam_search_width_one_is_golden_greedy_and_wider_matches_oracle(
         assert same.all() or gap < 1e-4, (K, end_id, same, gap)
     with pytest.raises(ValueError):
         model.sample_beam_features(feats, 9)
+
+
+def test_greedy_and_width_one_beam_agree_from_a_given_state_and_leave_it_alone():
+    """The decode step `sample_features` and `sample_beam_features` share, from a NON-zero (h, c), at the smallest legal dims
+    (E 4, C 8, H 12, P 5, V 11; B 3): width-1 beam == greedy, ids and attention maps bit for bit (the token comes from different
+    kernels: `sat_vocab_argmax` / `sat_vocab_logits_fwd` + `sat_beam_step`); the caller's tensors are not written; a `states` of
+    the wrong shape is a ValueError from both, before anything runs on it.  Seed: picked from 0..299 by a float64 replay -- its
+    decode changes token 36 times over three tokens, and the smallest top-two log-probability gap is 1.2e-3, far above f32 rounding,
+    so the two selections cannot legitimately disagree."""
+    torch.manual_seed(179)
+    B, P, C, E, H, V = 3, 5, 8, 4, 12, 11
+    model = sat.ShowAttendTellModel(H, C, V, E, None, feature_size=(P, C), compute_dtype="f32", vgg_cfg=[C]).cuda().eval()
+    feats = torch.randn(B, P, C).cuda()
+    h, c = torch.randn(B, H).cuda(), torch.randn(B, H).cuda()
+    h_was, c_was = h.clone(), c.clone()
+    ids, alphas = model.sample_features(feats, (h, c), return_alphas=True)
+    ids_b, alphas_b = model.sample_beam_features(feats, 1, (h, c), return_alphas=True)
+    assert ids.shape == (B, 20) and alphas.shape == (B, 20, P)
+    assert torch.equal(ids, ids_b) and torch.equal(alphas, alphas_b)
+    assert torch.equal(h, h_was) and torch.equal(c, c_was)
+    for bad in ((h[:2], c[:2]), (h, c[:, :8]), (h, c, c), (h,)):
+        with pytest.raises(ValueError):
+            model.sample_features(feats, bad)
+        with pytest.raises(ValueError):
+            model.sample_beam_features(feats, 1, bad)
