@@ -648,6 +648,41 @@ int sat_ss_attend_fwd(const float* feats, const float* ctx_enc, const float* h0,
  * `stride` elements between rows (model.sample's [B,20], or one hypothesis plane of the beam ids). */
 int sat_kept_tokens(const int64_t* ids, int64_t stride, int B, int T, int64_t end_id, int32_t* kept /*[B]*/,
                     sat_stream_t stream);
+/* Stochastic decode (added within ABI 18): a token per row drawn after temperature, top-k and nucleus (top-p) filtering -- the
+ * decode mode beside the arg-max (sat_greedy_decode) and the beam (sat_beam_decode).  No sort, no host read.
+ * sat_sample_filtered: R rows of V logits (row stride ldl >= V floats; columns [V, ldl) are never candidates, whatever they hold).
+ *   Total order of a row: its candidates -- columns with a logit above -inf (a NaN is no candidate) -- by float value descending,
+ *     equal values by ascending column; +0.0 and -0.0 are equal.
+ *   top-k: with 0 < top_k < number of candidates only the first top_k of that order stay (0 or >= V: off).
+ *   nucleus: tau = (double)temperature, w_v = exp((x_v - x_max) / tau), Z = sum of w over what top-k left; with top_p < 1 the
+ *     shortest prefix of the order whose cumulative w reaches (double)top_p * Z stays, at least one token (top_p == 1: off).  The
+ *     masses are summed as integers floor(w * 2^48): a prefix sum loses < V * 2^-48 (1.2e-10 at the largest V), so a decision
+ *     further than 1e-6 * Z from top_p * Z is that of exact arithmetic; closer, the one boundary token may go either way.
+ *   draw: ids[r*ids_stride] = first argmax over the KEPT columns of x_v / temperature + G(r, t, v), G as for sat_vocab_sample below
+ *     (Philox4x32-10, counter (v >> 2, r, t, 2*rank), word v & 3, key from seed); evaluated for kept columns only.  With
+ *     temperature 1, top_k 0, top_p 1 this is s(r, t) of sat_vocab_sample / the rollouts on the same logits.
+ *   kept[r] (nullable) = size of the kept set (a prefix of the total order: the count identifies it); logp[r] (nullable) =
+ *     ln(w_tok / sum of w over the kept set), evaluated in f64 and rounded once.
+ *   A row needs one finite logit; without one the token is undefined but inside [0, V).  ids, kept and logp depend on (row
+ *   contents, temperature, top_k, top_p, seed, rank, r, t) only -- not on R, ldl or the launch -- and are the same in every run.
+ *   SAT_ERR_ARG: logits, ids or workspace NULL; R < 1; V < 1; ldl < V; ids_stride < 1; temperature not finite or <= 0; top_k < 0;
+ *   top_p outside (0, 1]; t < 0; rank < 0.  SAT_ERR_UNSUPPORTED: V > 32768.  SAT_ERR_WORKSPACE: ws_bytes <
+ *   sat_sample_filtered_ws_bytes(R, V) (0 for non-positive sizes).  All before anything is enqueued.
+ * sat_sample_decode: sat_greedy_decode's loop and state handling (h / c in and out, h_tmp, x_tmp) with sat_sample_filtered (t = the
+ *   step, row r = b) where it takes the arg-max: per step sat_lstm_step per layer, sat_vocab_logits_fwd (exact f32, stored),
+ *   the filtered draw, sat_embed_rows.  Nullable outputs: logp [B][steps], kept [B][steps], logits_out [steps*B][ldl] (row t*B + b =
+ *   step t of row b; ldl >= V).  Rows keep running behind <end> (sat_kept_tokens truncates).  Errors as above and as
+ *   sat_greedy_decode's, before anything is enqueued; workspace: sat_sample_decode_ws_bytes (0 for non-positive sizes). */
+int64_t sat_sample_filtered_ws_bytes(int R, int V);
+int sat_sample_filtered(const float* logits /*[R, ldl]*/, int64_t ldl, int R, int V, float temperature, int top_k, float top_p,
+                        uint64_t seed, int t, int rank, int64_t* ids, int64_t ids_stride, float* logp /*[R] or NULL*/,
+                        int32_t* kept /*[R] or NULL*/, void* workspace, int64_t ws_bytes, sat_stream_t stream);
+int64_t sat_sample_decode_ws_bytes(int B, int E, int H, int V, int num_layers);
+int sat_sample_decode(const float* features, const float* embed, const float* const* lstm_w /*[host]*/, int num_layers,
+                      const float* lin_w, const float* lin_b, int B, int E, int H, int V, int steps, float temperature, int top_k,
+                      float top_p, uint64_t seed, int rank, float* h, float* c, float* h_tmp, float* x_tmp, int64_t* ids,
+                      int64_t ids_stride, float* logp, int32_t* kept, float* logits_out, int64_t ldl, void* workspace,
+                      int64_t ws_bytes, sat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * CIDEr of decoded id rows against reference captions (added within ABI 18).

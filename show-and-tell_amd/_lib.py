@@ -198,6 +198,11 @@ SIGNATURES = {
     "sat_rollout_attend_fwd_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
     "sat_rollout_attend_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _i64,
                                     _i, _i64, C.c_uint64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "sat_sample_filtered_ws_bytes": (_i64, [_i, _i]),
+    "sat_sample_filtered": (_i, [_vp, _i64, _i, _i, _f, _i, _f, C.c_uint64, _i, _i, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "sat_sample_decode_ws_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "sat_sample_decode": (_i, [_vp, _vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _f, C.c_uint64, _i, _vp, _vp, _vp,
+                               _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "sat_clamp_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp]),
     "sat_clamp_adam_step_guarded": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp, _vp]),
     "sat_step_fault_flag": (_i, [C.POINTER(_vp), _i, _vp, _vp, _vp]),
@@ -214,7 +219,8 @@ ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_at
                     "sat_attention_bwd_ex", "sat_beam_backtrack_rows", "sat_cider_table_insert", "sat_cider_ref_stats", "sat_cider_score",
                     "sat_rollout_decoder_fwd_ws_bytes", "sat_rollout_decoder_fwd", "sat_scst_weights", "sat_ce_rows_weighted",
                     "sat_rollout_attend_fwd_ws_bytes", "sat_rollout_attend_fwd", "sat_bleu_comps", "sat_bleu_finalize",
-                    "sat_rouge_l_score")
+                    "sat_rouge_l_score", "sat_sample_filtered_ws_bytes", "sat_sample_filtered", "sat_sample_decode_ws_bytes",
+                    "sat_sample_decode")
 
 _lib = None
 

@@ -26,7 +26,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .attend_bwd import PARAM_ORDER, attend_backward
-from .models import draw_ss_seed, lookahead_stream
+from .models import check_sample_args, draw_ss_seed, lookahead_stream
 from .pack import PackInfo
 from .scst import SelfCritical
 from .vgg import VGG16_FEATURES, VggFeatures, VggProgram, _VggFn  # noqa: F401  (VggFeatures is re-exported by the package)
@@ -338,6 +338,7 @@ class ShowAttendTellModel(nn.Module):
         self.last_alphas = self.last_attention_penalty = None    # set by every decode / forward
         self.last_rollout_inputs = self.last_rollout_seed = None # tokens fed [B, steps] and seed of the last `rollout`
         self.last_scst = None                                    # the `SelfCritical` object of the last `scst_forward`
+        self.last_sample_seed = None                             # seed of the last `sample_stochastic`
         self._programs, self._guard = {}, None
         self._pf_list = []          # features in flight: [(images, feats, fmean, event, weights signature, instance)]
         self.register_load_state_dict_post_hook(lambda mod, k: mod._programs.clear())
@@ -568,6 +569,80 @@ class ShowAttendTellModel(nn.Module):
         if return_alphas:
             return ids, amaps.transpose(0, 1).contiguous()
         return ids
+
+    @torch.no_grad()
+    def sample_stochastic(self, images, states=None, **kw):
+        """`sample_stochastic_features` behind the conv stack (arguments checked before it runs)."""
+        check_sample_args(kw.get("temperature", 1.0), kw.get("top_k", 0), kw.get("top_p", 1.0), kw.get("num_samples", 1), kw.get("seed"))
+        feats, _ = self._encode(images)
+        return self.sample_stochastic_features(feats, states, **kw)
+
+    @torch.no_grad()
+    def sample_stochastic_features(self, features, states=None, steps=20, start_id=1, temperature=1.0, top_k=0, top_p=1.0,
+                                   num_samples=1, seed=None, return_logprobs=False, return_logits=False, return_alphas=False):
+        """`sample_features` with a DRAW where it takes the arg-max: every step's token comes from softmax(logits / temperature)
+        restricted to the top_k most likely tokens (0: all) and then to the nucleus, the shortest most-likely-first prefix holding
+        top_p of the remaining mass (1: all).  The loop is `sample_features`' own -- `_EvalDecoder.step`, the classifier as one
+        exact-f32 GEMM, `sat_sample_filtered` with t = the step, `_EvalDecoder.feed` -- with model2.py:91-111's zero state and
+        lagging context, so top_k=1 decodes what `sample` decodes (up to ties between logits).  No tapes; eval or train mode.
+
+        Returns ids i64 [B, steps], or [B, S, steps] with num_samples = S > 1 (features and states repeated per image, draw row
+        b * S + s).  Then, in this order, as asked: return_logprobs a dict(logp f32, kept i32) shaped like ids; return_logits the
+        exact-f32 logits [steps, B*S, V]; return_alphas the attention maps f32 [B, steps, P] ([B, S, steps, P]).  seed=None takes
+        `draw_ss_seed()`; the seed used stays on `last_sample_seed`; the draws are `ss_rank`'s stream."""
+        tau, top_k, top_p, S, seed = check_sample_args(temperature, top_k, top_p, num_samples, seed)
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("steps must be >= 1")
+        m, dev = self, features.device
+        B, P, C = features.shape
+        E, H, V = m.embed_size, m.hidden_size, m.vocab_size
+        _check_states(states, B, H)
+        L.require_gpu(features, "features")
+        lib, st = L.load(), L.stream()
+        R = B * S
+        feats = features.contiguous()
+        if S > 1:
+            feats = feats.repeat_interleave(S, 0).contiguous()
+        f2 = feats.view(R * P, C)
+        ctx_enc = _context_encode(lib, m, f2)
+        if states is None:
+            h, c = torch.zeros(R, H, device=dev), torch.zeros(R, H, device=dev)
+        else:
+            h = states[0].to(dev).float().repeat_interleave(S, 0).contiguous().clone()
+            c = states[1].to(dev).float().repeat_interleave(S, 0).contiguous().clone()
+        if seed is None:
+            seed = draw_ss_seed()
+        d = _EvalDecoder(lib, m, f2, ctx_enc, h, c)
+        ids = torch.full((R, steps), int(start_id), dtype=torch.int64, device=dev)
+        start = torch.full((R,), int(start_id), dtype=torch.int64, device=dev)
+        ldl = L.pad4(V)
+        logits = torch.zeros(steps if return_logits else 1, R, ldl, device=dev)
+        logp = torch.empty(steps, R, device=dev) if return_logprobs else None
+        kept = torch.empty(steps, R, dtype=torch.int32, device=dev) if return_logprobs else None
+        wsb = lib.sat_sample_filtered_ws_bytes(R, V)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        amaps = torch.empty(steps, R, P, device=dev) if return_alphas else None
+        for i in range(steps):
+            d.step(amaps[i].data_ptr() if return_alphas else None, start if i == 0 else None)
+            lg = logits[i if return_logits else 0]
+            L.check(lib.sat_vocab_logits_fwd(L.ptr(d.Z), L.ptr(m.classifier.weight), L.ptr(m.classifier.bias), R, E, V, lg.data_ptr(),
+                                             ldl, st), "sat_vocab_logits_fwd")
+            col = ids[:, i]
+            L.check(lib.sat_sample_filtered(lg.data_ptr(), ldl, R, V, tau, top_k, top_p, seed, i, int(self.ss_rank), col.data_ptr(),
+                                            ids.stride(0), logp[i].data_ptr() if return_logprobs else None,
+                                            kept[i].data_ptr() if return_logprobs else None, L.ptr(ws), wsb, st), "sat_sample_filtered")
+            d.feed(col.data_ptr(), ids.stride(0), d.ctxb)
+        self.last_sample_seed = seed
+        shape = (B, S, steps) if S > 1 else (B, steps)
+        out = [ids.view(shape)]
+        if return_logprobs:
+            out.append(dict(logp=logp.t().contiguous().view(shape), kept=kept.t().contiguous().view(shape)))
+        if return_logits:
+            out.append(logits[:, :, :V])
+        if return_alphas:
+            out.append(amaps.transpose(0, 1).contiguous().view(shape + (P,)))
+        return out[0] if len(out) == 1 else tuple(out)
 
     @torch.no_grad()
     def sample_beam_features(self, features, beam_size=5, states=None, end_id=None, steps=20, start_id=1, return_all=False,

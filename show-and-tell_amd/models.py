@@ -445,6 +445,32 @@ def draw_ss_seed():
     return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
 
 
+def _as_f32(value):
+    """value as the float32 the kernel receives (None when it is no number)"""
+    try:
+        return float(torch.tensor(float(value), dtype=torch.float32))
+    except (TypeError, ValueError, OverflowError):
+        return None
+
+
+def check_sample_args(temperature, top_k, top_p, num_samples, seed):
+    """The arguments of `sample_stochastic` as (temperature, top_k, top_p, num_samples, seed or None); a ValueError names the bad
+    one.  Host arithmetic only: runs before the library is loaded."""
+    import math
+    tau, p = _as_f32(temperature), _as_f32(top_p)
+    if isinstance(temperature, bool) or tau is None or not math.isfinite(tau) or tau <= 0:
+        raise ValueError("temperature must be a finite number > 0 (as float32), got %r" % (temperature,))
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0 or top_k > 2 ** 31 - 1:
+        raise ValueError("top_k must be an int >= 0 (0: no top-k filter), got %r" % (top_k,))
+    if isinstance(top_p, bool) or p is None or not 0 < p <= 1 or not 0 < float(top_p) <= 1:
+        raise ValueError("top_p must be in (0, 1] (1: no nucleus filter), got %r" % (top_p,))
+    if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
+        raise ValueError("num_samples must be an int >= 1, got %r" % (num_samples,))
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or seed < 0 or seed >= 2 ** 64):
+        raise ValueError("seed must be None or an int in [0, 2^64), got %r" % (seed,))
+    return tau, top_k, p, num_samples, seed
+
+
 class _DecoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, captions, pi, ss, names, *tensors):
@@ -501,6 +527,7 @@ class DecoderRNN(nn.Module):
         self.ss_rank = 0                  # data-parallel rank: a stream of draws of its own per rank
         self.last_ss_inputs = self.last_ss_seed = None   # tokens fed [B, T-1] and seed of the last sampled forward
         self.last_rollout_seed = None     # seed of the last `rollout`
+        self.last_sample_seed = None      # seed of the last `sample_stochastic`
         self._id_guard = None
         self.init_weights()
 
@@ -580,6 +607,59 @@ class DecoderRNN(nn.Module):
                                       L.ptr(self.linear.weight), L.ptr(self.linear.bias), B, E, H, V, 20, L.ptr(h), L.ptr(c),
                                       L.ptr(h_tmp), L.ptr(xe), ids.data_ptr(), ids.stride(0), L.ptr(ws), wsb, st), "sat_greedy_decode")
         return ids.squeeze()                # models.py:67: [20] at batch 1
+
+    @torch.no_grad()
+    def sample_stochastic(self, features, states=None, temperature=1.0, top_k=0, top_p=1.0, num_samples=1, seed=None,
+                          return_logprobs=False, return_logits=False):
+        """`sample` with a DRAW where it takes the arg-max: every step's token comes from softmax(logits / temperature) restricted
+        to the top_k most likely tokens (0: all) and then to the nucleus, the shortest most-likely-first prefix that holds top_p of
+        the remaining mass (1: all).  20 steps as ONE `sat_sample_decode` call, no tapes, eval or train mode; rows keep running
+        behind their <end> (`kept_tokens` truncates).
+
+        Returns ids i64 [B, 20]; with num_samples = S > 1 ids [B, S, 20] -- features and `states` (as for `sample`) are repeated
+        per image and the draw row is b * S + s, so the S captions of an image differ.  (No squeeze: [1, 20] at batch 1.)
+        return_logprobs: also a dict(logp=f32 [.., 20], the log-probability of every drawn token under the filtered distribution,
+        kept=i32 [.., 20], the number of tokens the filters left).  return_logits: also the exact-f32 logits [20, B*S, V] of
+        every step (last).  seed: None draws one from torch's CPU generator (`draw_ss_seed`: `torch.manual_seed` reproduces it);
+        the seed used stays on `last_sample_seed`.  The draws are `ss_rank`'s stream and follow sat_vocab_sample's convention: with
+        (temperature, top_k, top_p) = (1, 0, 1) the tokens are those `rollout` draws from the same seed; top_k=1 takes every step's
+        arg-max (`sample`, up to ties between logits: its projection is another kernel with another summation order)."""
+        tau, top_k, top_p, S, seed = check_sample_args(temperature, top_k, top_p, num_samples, seed)
+        lib = L.load()
+        features = _f32c(features, "features")
+        dev = features.device
+        B = features.shape[0]
+        H, V, E, steps = self.hidden_size, self.vocab_size, self.embed_size, 20
+        h0, c0 = self._initial_states(states, B, dev)
+        if S > 1:
+            features = features.repeat_interleave(S, 0).contiguous()
+            h0, c0 = h0.repeat_interleave(S, 1), c0.repeat_interleave(S, 1)
+        R = B * S
+        if seed is None:
+            seed = draw_ss_seed()
+        h, c = h0.clone().contiguous(), c0.clone().contiguous()
+        h_tmp, xe = torch.empty_like(h), torch.empty(R, E, device=dev)
+        ids = torch.empty(R, steps, dtype=torch.int64, device=dev)
+        logp = torch.empty(R, steps, device=dev) if return_logprobs else None
+        kept = torch.empty(R, steps, dtype=torch.int32, device=dev) if return_logprobs else None
+        ldl = L.pad4(V)
+        logits = torch.zeros(steps * R, ldl, device=dev) if return_logits else None
+        wsb = lib.sat_sample_decode_ws_bytes(R, E, H, V, self.num_layers)
+        ws = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
+        off = (-ws.data_ptr()) % 256
+        L.check(lib.sat_sample_decode(L.ptr(features), L.ptr(self.embed.weight), self._lstm_ptrs(), self.num_layers,
+                                      L.ptr(self.linear.weight), L.ptr(self.linear.bias), R, E, H, V, steps, tau, top_k, top_p, seed,
+                                      int(self.ss_rank), L.ptr(h), L.ptr(c), L.ptr(h_tmp), L.ptr(xe), ids.data_ptr(), ids.stride(0),
+                                      L.ptr(logp), L.ptr(kept), L.ptr(logits), ldl, ws.data_ptr() + off, wsb, L.stream()),
+                "sat_sample_decode")
+        self.last_sample_seed = seed
+        shape = (B, S, steps) if S > 1 else (B, steps)
+        out = [ids.view(shape)]
+        if return_logprobs:
+            out.append(dict(logp=logp.view(shape), kept=kept.view(shape)))
+        if return_logits:
+            out.append(logits.view(steps, R, ldl)[:, :, :V])
+        return out[0] if len(out) == 1 else tuple(out)
 
     def _lstm_ptrs(self):
         """HOST array of the LSTM's device pointers, (w_ih, w_hh, b_ih, b_hh) per layer: the `lstm_w` argument of the decode calls"""
@@ -693,6 +773,13 @@ class ShowAndTell(nn.Module):
     @torch.no_grad()
     def sample_beam(self, images, beam_size=5, end_id=None, return_all=False):
         return self.decoder.sample_beam(self.encoder(images), beam_size, end_id, return_all=return_all)
+
+    @torch.no_grad()
+    def sample_stochastic(self, images, state=None, **kw):
+        """`DecoderRNN.sample_stochastic` behind the encoder: temperature, top_k, top_p, num_samples, seed, return_logprobs,
+        return_logits as there (checked before the encoder runs)."""
+        check_sample_args(kw.get("temperature", 1.0), kw.get("top_k", 0), kw.get("top_p", 1.0), kw.get("num_samples", 1), kw.get("seed"))
+        return self.decoder.sample_stochastic(self.encoder(images), state, **kw)
 
 
 Encoder = EncoderCNN      # names BASELINE.json uses
