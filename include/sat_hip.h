@@ -614,6 +614,21 @@ int sat_ss_decoder_fwd(const float* features /*[B,E]*/, const float* embed /*[V,
                        const float* const* lstm_w /*[host]*/, int num_layers, int H, const float* lin_w, const float* lin_b,
                        float* const* tapes /*[host]*/, float* X, float* logits, int64_t ldl, float ss_prob, uint64_t seed, int rank,
                        int64_t* used, int64_t used_stride, float* workspace, int64_t ws_bytes, sat_stream_t stream);
+/* Dropout on a dense f32 tape, forward and backward: y[r][j] = keep(r, j) ? x[r][j] * scale : 0 for r < rows, j < cols; x rows ldx
+ * floats apart, y rows ldy apart, columns [cols, ld) of y untouched; y == x (in place) is allowed, any other overlap is not.  The
+ * backward is the same call with the same (p, seed, rank, site) on the gradient: the mask is regenerated, never stored.
+ * Random numbers: Philox4x32-10 as above, key (seed & 0xffffffff, seed >> 32); element (r, j) reads word j & 3 of counter
+ * (j >> 2, r, 0x80000000 | site, 2*rank).  The high bit of counter word 2 keeps these streams apart from every scheduled-sampling,
+ * rollout and stochastic-decode draw (those carry the step index t there), so a seed reused by accident cannot correlate a mask
+ * with a token draw.  keep(r, j) = (word >> 8) >= thr, thr = (uint32_t)lrint((double)p * 16777216.0), computed once on the host
+ * side of the call: an integer comparison, so a host reference and the device cannot differ by a rounding.  scale =
+ * (float)(1.0 / (1.0 - (double)p)); the product is one f32 multiply.  p == 0: thr = 0, scale = 1, an exact copy (in place: returns
+ * without a launch).  site: which activation of a model (the models' numbering: DESIGN.md); rank: the data-parallel rank.
+ * SAT_ERR_ARG, before anything is enqueued, unless 0 <= p < 1 (finite), rows, cols >= 0, ldx, ldy >= cols, 0 <= site < 2^31 and
+ * rank >= 0; rows == 0 or cols == 0: SAT_OK without a launch.  Any cols and any leading dimension work: rows whose bases are
+ * 16-byte aligned (pointers and leading dimensions) move as 16-byte loads and stores, the rest element by element. */
+int sat_dropout_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int rows, int cols, float p, uint64_t seed, int rank, int site,
+                    sat_stream_t stream);
 /* Scheduled sampling in the Show-Attend-Tell training forward (model2.py:38-85, the model train.py:37 builds; schedule
  * train.py:109-113).  Same random numbers as above; rows b < batch_sizes[t+1] of step t+1 >= 1 are fed, in the embedding half of
  * the LSTMCell input [emb | ctx], used[b][t+1] = mask(b, t+1) ? s(b, t+1) : captions[b][t+1], s drawn from the logits of step t

@@ -203,6 +203,7 @@ SIGNATURES = {
     "sat_sample_decode_ws_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "sat_sample_decode": (_i, [_vp, _vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _f, C.c_uint64, _i, _vp, _vp, _vp,
                                _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "sat_dropout_f32": (_i, [_vp, _i64, _vp, _i64, _i, _i, _f, C.c_uint64, _i, _i, _vp]),
     "sat_clamp_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp]),
     "sat_clamp_adam_step_guarded": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp, _vp]),
     "sat_step_fault_flag": (_i, [C.POINTER(_vp), _i, _vp, _vp, _vp]),
@@ -220,7 +221,7 @@ ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_at
                     "sat_rollout_decoder_fwd_ws_bytes", "sat_rollout_decoder_fwd", "sat_scst_weights", "sat_ce_rows_weighted",
                     "sat_rollout_attend_fwd_ws_bytes", "sat_rollout_attend_fwd", "sat_bleu_comps", "sat_bleu_finalize",
                     "sat_rouge_l_score", "sat_sample_filtered_ws_bytes", "sat_sample_filtered", "sat_sample_decode_ws_bytes",
-                    "sat_sample_decode")
+                    "sat_sample_decode", "sat_dropout_f32")
 
 _lib = None
 

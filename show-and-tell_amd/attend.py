@@ -26,7 +26,8 @@ import torch.nn as nn
 
 from . import _lib as L
 from .attend_bwd import PARAM_ORDER, attend_backward
-from .models import check_sample_args, draw_ss_seed, lookahead_stream
+from .decoder import dropout_rows
+from .models import check_dropout_p, check_sample_args, draw_ss_seed, lookahead_stream, refuse_dropout_with
 from .pack import PackInfo
 from .scst import SelfCritical
 from .vgg import VGG16_FEATURES, VggFeatures, VggProgram, _VggFn  # noqa: F401  (VggFeatures is re-exported by the package)
@@ -126,7 +127,9 @@ class _AttendFn(torch.autograd.Function):
     def forward(ctx, model, features, fmean, captions, pi, ss, ex, *params):
         """ss: None (teacher forcing) or dict(prob, seed, rank) -- scheduled sampling through `sat_ss_attend_fwd`; receives
         "used", the tokens fed [B, T].  ex: dict(alpha_c) -- receives "alphas", the packed [N, P] attention tape; with
-        alpha_c > 0 the doubly stochastic penalty is a second output (`_attend_outputs`)."""
+        alpha_c > 0 the doubly stochastic penalty is a second output (`_attend_outputs`); dropout: None or (p, seed, rank) -- the Z
+        tape is dropped in place (site 0) between the output layer and the classifier, its only readers being the classifier GEMM
+        and the backward's dW = dlogits^T Z (teacher forcing only)."""
         lib, m, st, dev = L.load(), model, L.stream(), features.device
         s = _DecoderSetup(lib, m, features, fmean, pi.N, with_wz=ss is not None)
         if ss is not None:
@@ -156,9 +159,12 @@ class _AttendFn(torch.autograd.Function):
             L.check(lib.sat_rows_copy(L.ptr(HS), H, None, 0, N, N, H, Zin.data_ptr() + C * 4, C + H, st), "sat_rows_copy")
             s.Wz = _output_weight(lib, m)
             L.gemm(lib, 0, 0, Zin, C + H, s.Wz, C + H, Z, E, N, E, C + H, m.context2out.bias, m.hidden2tout.bias)
+            if ex.get("dropout") is not None:               # where the reference keeps its unused nn.Dropout (model2.py:34)
+                dropout_rows(lib, Z, *ex["dropout"], 0)
             logits = L.logits_buffer(N, V, dev)
             L.gemm(lib, 0, 0, Z, E, m.classifier.weight, E, logits, logits.shape[1], N, V, E, m.classifier.bias)
         s.record(ctx, pi, captions)
+        ctx.tapes["dropout"] = ex.get("dropout") if ss is None else None
         return _attend_outputs(ctx, lib, ex, logits, m.vocab_size)
 
     @staticmethod
@@ -339,6 +345,10 @@ class ShowAttendTellModel(nn.Module):
         self.last_rollout_inputs = self.last_rollout_seed = None # tokens fed [B, steps] and seed of the last `rollout`
         self.last_scst = None                                    # the `SelfCritical` object of the last `scst_forward`
         self.last_sample_seed = None                             # seed of the last `sample_stochastic`
+        # dropout on Z = context2out(ctx) + hidden2tout(h) in front of the classifier, training mode only: where model2.py:34 builds
+        # an nn.Dropout(p=0.5) it never calls (masks: include/sat_hip.h `sat_dropout_f32`, site 0, rank `ss_rank`); 0 = off
+        self.dropout_p = 0.0
+        self.last_dropout_seed = None                            # seed of the last forward that dropped anything
         self._programs, self._guard = {}, None
         self._pf_list = []          # features in flight: [(images, feats, fmean, event, weights signature, instance)]
         self.register_load_state_dict_post_hook(lambda mod, k: mod._programs.clear())
@@ -440,8 +450,20 @@ class ShowAttendTellModel(nn.Module):
         d = dict(self.named_parameters())
         return [d[k] for k in PARAM_ORDER]
 
+    def dropout_plan(self, sampling=False, what="ss_prob > 0 (scheduled sampling)"):
+        """`dropout_p` as float32 when a training forward drops, else None (eval mode or 0).  Host checks only, nothing drawn:
+        ValueError for a probability outside [0, 1), NotImplementedError when the mask is active and `sampling` says the forward
+        is one of the step loops that project inside one library call (`what`)."""
+        p = check_dropout_p(self.dropout_p, "dropout_p")
+        if not (self.training and p > 0):
+            return None
+        if sampling:
+            refuse_dropout_with(["dropout_p"], what)
+        return p
+
     def forward(self, images, captions, lengths):
         """model2.py:38-65: logits f32 [sum(lengths), V], rows in time-major packed order."""
+        self.dropout_plan(sampling=self.training and self.ss_prob > 0)        # refuse before the conv stack runs
         feats, fmean = self._encode(images)
         return self.decode(feats, fmean, captions, lengths)
 
@@ -454,7 +476,11 @@ class ShowAttendTellModel(nn.Module):
         logits' row n).  With `alpha_c > 0` it also leaves `last_attention_penalty`, a 0-dim tensor WITH a graph equal to
         alpha_c * mean_{b,p} (1 - sum_t alpha[b,t,p])^2 (doubly stochastic attention), None otherwise; a training loop adds it:
         `loss = criterion(out, targets) + model.last_attention_penalty`.  The mean is over this call's B images: under data
-        parallelism B is the rank's own batch."""
+        parallelism B is the rank's own batch.
+
+        In training mode with `dropout_p` > 0 the output layer's Z is dropped in front of the classifier; the mask's seed (one
+        `draw_ss_seed()`) stays on `last_dropout_seed`.  Together with ss_prob > 0 that raises NotImplementedError."""
+        p_drop = self.dropout_plan(sampling=self.training and self.ss_prob > 0)
         L.require_gpu(captions, "captions")
         if len(lengths) != features.shape[0]:
             raise ValueError("len(lengths) != batch size")
@@ -470,6 +496,9 @@ class ShowAttendTellModel(nn.Module):
         if self.training and self.ss_prob > 0:
             ss = dict(prob=float(self.ss_prob), seed=draw_ss_seed(), rank=int(self.ss_rank))
         ex = dict(alpha_c=float(self.alpha_c))
+        if p_drop is not None:
+            self.last_dropout_seed = draw_ss_seed()
+            ex["dropout"] = (p_drop, self.last_dropout_seed, int(self.ss_rank))
         out = _AttendFn.apply(self, features, fmean, captions, pi, ss, ex, *self._params())
         self.last_attention_penalty = None
         if ex["alpha_c"] > 0:
@@ -500,6 +529,7 @@ class ShowAttendTellModel(nn.Module):
         would pull the maps of steps the loss masks towards covering the image.  (A length-masked penalty is a separate change.)"""
         if not self.training:
             raise RuntimeError("ShowAttendTellModel.rollout is a training forward (model.train()); eval mode decodes with sample()")
+        self.dropout_plan(sampling=True, what="a rollout")
         L.require_gpu(features, "features")
         L.require_gpu(fmean, "fmean")
         steps = int(steps)
@@ -525,6 +555,7 @@ class ShowAttendTellModel(nn.Module):
         of the same policy as the baseline, CIDEr of both, weighted cross entropy.  image_index: the corpus image of every row, as
         for `CiderScorer.score`.  With `finetune(allow=True)` `loss.backward()` also reaches the conv stack.  The `SelfCritical`
         object (its last_reward, last_baseline, last_ids, last_greedy_ids) is kept as `last_scst`."""
+        self.dropout_plan(sampling=True, what="a rollout (scst_forward)")     # refuse before the conv stack runs
         feats, fmean = self._encode(images)
         self.last_scst = SelfCritical(scorer, end_id)
         return self.last_scst.attend(self, feats, fmean, image_index, steps)

@@ -6,6 +6,7 @@ d_alpha on the device."""
 import torch
 
 from . import _lib as L
+from .decoder import dropout_rows
 
 # the decoder's parameters (state_dict names) in the order `attend_backward` returns their gradients
 PARAM_ORDER = ("image_att_w", "init_hidden.weight", "init_hidden.bias", "init_memory.weight", "init_memory.bias",
@@ -17,7 +18,8 @@ PARAM_ORDER = ("image_att_w", "init_hidden.weight", "init_hidden.bias", "init_me
 def attend_backward(m, pi, captions, tp, dlogits, want_dfeat=False, d_alpha_extra=None, d_alpha_scale=None):
     """Returns (gradients in `PARAM_ORDER`, d_features [B,P,C] or None, d_fmean [B,C] or None); the last two only when
     the conv stack is being fine-tuned (model2.py:87-89).  d_alpha_extra [B,P] / d_alpha_scale (device scalar): a second consumer
-    of the attention maps (the coverage penalty) -- every step's d_alpha gains d_alpha_scale * d_alpha_extra[b] for its rows b."""
+    of the attention maps (the coverage penalty) -- every step's d_alpha gains d_alpha_scale * d_alpha_extra[b] for its rows b.
+    tp["dropout"] = (p, seed, rank): the forward dropped Z in front of the classifier; dZ gets the same mask, regenerated."""
     lib, st = L.load(), L.stream()
     dev = dlogits.device
     f2, fmean, ctx_enc = tp["f2"], tp["fmean"], tp["ctx_enc"]
@@ -37,6 +39,8 @@ def attend_backward(m, pi, captions, tp, dlogits, want_dfeat=False, d_alpha_extr
     L.check(lib.sat_colsum_f32(dlogits.data_ptr(), ldl, N, V, g["classifier.bias"].data_ptr(), st), "sat_colsum_f32")
     dZ = torch.empty(N, E, device=dev)
     L.gemm(lib, 0, 1, dlogits, ldl, m.classifier.weight, E, dZ, E, N, E, V)                   # dZ = dlogits W_cls
+    if tp.get("dropout") is not None:                   # back through the mask, before every reader of dZ
+        dropout_rows(lib, dZ, *tp["dropout"], 0)
     dWz = torch.empty(E, C + H, device=dev)
     L.gemm(lib, 2, 1, dZ, E, Zin, C + H, dWz, C + H, E, C + H, N)
     g["context2out.weight"], g["hidden2tout.weight"] = torch.empty(E, C, device=dev), torch.empty(E, H, device=dev)

@@ -133,6 +133,19 @@ def _step_loop_pointers(layers, tapes, cst):
     return wflat, ptrs
 
 
+def dropout_rows(lib, t, p, seed, rank, site):
+    """`sat_dropout_f32` in place on the dense f32 [rows, cols] tensor t (a tape in the forward, its gradient in the backward: the
+    mask is a function of the arguments, include/sat_hip.h); nothing is launched for p == 0"""
+    if p > 0:
+        L.check(lib.sat_dropout_f32(L.ptr(t), t.stride(0), L.ptr(t), t.stride(0), t.shape[0], t.shape[1], float(p), int(seed),
+                                    int(rank), int(site), L.stream()), "sat_dropout_f32")
+
+
+def _layer_dropout(dropout, l, num_layers):
+    """probability on the output of LSTM layer l (its site is l + 1): p_out on the top layer's, p_lstm on every other's"""
+    return 0.0 if dropout is None else dropout[0 if l == num_layers - 1 else 1]
+
+
 def rollout_forward(lib, features, params, steps, seed, rank, ws=None, logits=None):
     """The SAMPLED forward of self-critical training (`sat_rollout_decoder_fwd`, one library call): `steps` steps of all B rows, the
     input of step t >= 1 the token drawn from step t-1's logits.  Returns (ids i64 [B, steps], logits f32 [steps * B, pad4(V)],
@@ -162,7 +175,8 @@ def rollout_forward(lib, features, params, steps, seed, rank, ws=None, logits=No
     return ids, logits, tapes, pi
 
 
-def decoder_forward(lib, features, params, captions, pi, ws=None, logits=None, ce=None, mixed_ws=None, ss=None, store_logits=True):
+def decoder_forward(lib, features, params, captions, pi, ws=None, logits=None, ce=None, mixed_ws=None, ss=None, store_logits=True,
+                    dropout=None):
     """embed+cat+pack -> L x LSTM -> vocab logits (models.py:49-53).  Returns (logits f32 [N, pad4(V)], tapes).
     params: the decoder's tensors by parameter name; ws: the `LSTMWorkspaces` of the calls (None: the autograd path's); logits:
     a buffer to fill (else a new one, `L.logits_buffer`); store_logits=False with `ss`: draws only, no f32 logits.
@@ -171,7 +185,14 @@ def decoder_forward(lib, features, params, captions, pi, ws=None, logits=None, c
     (`sat_ss_decoder_fwd`, one library call for the whole loop; the draws are functions of (seed, rank, row, step, token),
     include/sat_hip.h).  tapes["captions"] is then the tokens fed, i64 [B, T-1], so the backward is unchanged.
     ce: a `VocabCE`: the bf16 throughput mode's projection + CE (the loop above then draws without storing f32 logits);
-    mixed_ws: workspace of the LSTM layers' batched GEMMs on the bf16 matrix pipe (teacher forcing)."""
+    mixed_ws: workspace of the LSTM layers' batched GEMMs on the bf16 matrix pipe (teacher forcing).
+    dropout: None or (p_out, p_lstm, seed, rank), teacher forcing only: layer l's output tape X[l + 1] is dropped IN PLACE behind
+    the layer's call, with p_out for the top layer (in front of the projection) and p_lstm for the others (nn.LSTM(dropout=)),
+    site l + 1.  In place is safe: the recurrence carries h through the HP tape, and X[l + 1] is read only by the next layer's
+    batched input GEMMs and the projection, forward and backward -- all of which must see the dropped values.  The tuple stays in
+    tapes["dropout"] for `decoder_backward`."""
+    if dropout is not None and ss is not None:
+        raise NotImplementedError("dropout inside the scheduled-sampling loop (sat_ss_decoder_fwd) is not built")
     dev = features.device
     embed_w, lin_w, lin_b = params["embed.weight"], params["linear.weight"], params["linear.bias"]
     layers = lstm_layers(params)
@@ -185,6 +206,7 @@ def decoder_forward(lib, features, params, captions, pi, ws=None, logits=None, c
     cap_ptr, cap_stride = (captions.data_ptr(), captions.stride(0)) if T > 1 else (None, 0)
     ws = _fit(lib, ws, dev, B, T, layers, backward=False)
     tapes, cst = _new_tapes(layers, N, B, E, dev, captions)
+    tapes["dropout"] = dropout
     X = tapes["X"][0]
     if logits is None:
         logits = L.logits_buffer(N, V, dev)
@@ -216,6 +238,8 @@ def decoder_forward(lib, features, params, captions, pi, ws=None, logits=None, c
             else:
                 L.check(lib.sat_lstm_fwd(*args, st), "sat_lstm_fwd")
             ws.ran(l, backward=False)
+            if dropout is not None:
+                dropout_rows(lib, HS, _layer_dropout(dropout, l, len(layers)), dropout[2], dropout[3], l + 1)
         if ce is None:
             L.check(lib.sat_vocab_logits_fwd(L.ptr(tapes["X"][-1]), L.ptr(lin_w), L.ptr(lin_b), N, lin_w.shape[1],
                                              V, L.ptr(logits), logits.stride(0), st), "sat_vocab_logits_fwd")
@@ -232,7 +256,8 @@ def decoder_backward(lib, dlogits, tapes, params, pi, grads, ws, on_stage=None, 
     """Backward of decoder_forward.  `dlogits`: f32 [N, pad4(V)] with zero pad columns (unused with `ce`: the gradient is in
     ce.ws).  grads: preallocated f32 tensors to fill, by parameter name, plus "features"; ws: as decoder_forward's.
     on_stage(i) is called when gradient group i is final (0 vocab projection, 1 LSTM) -- the data-parallel
-    wrapper launches that bucket's all-reduce there, under the remaining backward kernels."""
+    wrapper launches that bucket's all-reduce there, under the remaining backward kernels.  With tapes["dropout"] the gradient of
+    every dropped tape gets the same mask (regenerated, in place) before the layer that produced the tape reads it."""
     dev = dlogits.device
     st = L.stream()
     N, T, B = pi.N, pi.T, pi.B
@@ -252,8 +277,11 @@ def decoder_backward(lib, dlogits, tapes, params, pi, grads, ws, on_stage=None, 
     if on_stage is not None:
         on_stage(0)
     ws = _fit(lib, ws, dev, B, T, layers, backward=True)
+    dropout = tapes.get("dropout")
     for l in reversed(range(len(layers))):
         w_ih, w_hh, _, _ = layers[l]
+        if dropout is not None:                 # dH is d(dropped X[l + 1]): back through the mask of site l + 1
+            dropout_rows(lib, dH, _layer_dropout(dropout, l, len(layers)), dropout[2], dropout[3], l + 1)
         H, In = w_hh.shape[1], w_ih.shape[1]
         GA, CS, HP = tapes["layers"][l]
         DG = torch.empty(N, 4 * H, device=dev)

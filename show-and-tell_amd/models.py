@@ -471,12 +471,30 @@ def check_sample_args(temperature, top_k, top_p, num_samples, seed):
     return tau, top_k, p, num_samples, seed
 
 
+def check_dropout_p(value, name):
+    """A dropout probability as the float32 the kernel receives; a ValueError names the attribute `name` unless it is a finite
+    number in [0, 1).  Host arithmetic only: runs before the library is loaded."""
+    import math
+    p = _as_f32(value)
+    if isinstance(value, bool) or p is None or not math.isfinite(p) or not 0 <= p < 1:
+        raise ValueError("%s must be a finite number in [0, 1) (as float32), got %r" % (name, value))
+    return p
+
+
+def refuse_dropout_with(active, what):
+    """Dropout inside the step loops that project within one library call (scheduled sampling, the rollouts) is not built:
+    `active` names the dropout attributes that are on, `what` the caller's side of the combination"""
+    if active:
+        raise NotImplementedError("%s with %s: the dropout mask is applied between library calls, and this loop projects inside "
+                                  "one (set %s to 0 for it)" % (" / ".join(active), what, " / ".join(active)))
+
+
 class _DecoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, features, captions, pi, ss, names, *tensors):
+    def forward(ctx, features, captions, pi, ss, dropout, names, *tensors):
         params = dict(zip(names, tensors))
         sampling = None if ss is None else (ss["prob"], ss["seed"], ss["rank"])
-        logits, tapes = decoder_forward(L.load(), features, params, captions, pi, ss=sampling)
+        logits, tapes = decoder_forward(L.load(), features, params, captions, pi, ss=sampling, dropout=dropout)
         if ss is not None:              # scheduled sampling: ss = dict(prob, seed, rank) receives "used", the tokens fed
             ss["used"] = tapes["captions"]
         ctx.tapes, ctx.pi, ctx.names, ctx.params = tapes, pi, names, params
@@ -486,7 +504,7 @@ class _DecoderFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits):
         g = _decoder_grads(ctx, dlogits)
-        return (g["features"], None, None, None, None, *(g[n] for n in ctx.names))
+        return (g["features"], None, None, None, None, None, *(g[n] for n in ctx.names))
 
 
 def _decoder_grads(ctx, dlogits):
@@ -528,6 +546,11 @@ class DecoderRNN(nn.Module):
         self.last_ss_inputs = self.last_ss_seed = None   # tokens fed [B, T-1] and seed of the last sampled forward
         self.last_rollout_seed = None     # seed of the last `rollout`
         self.last_sample_seed = None      # seed of the last `sample_stochastic`
+        # dropout, training mode only (masks: include/sat_hip.h `sat_dropout_f32`; rank `ss_rank`): `dropout_p` on the top layer's
+        # output in front of `linear` (site num_layers), `lstm_dropout_p` on the output of every layer but the last as
+        # nn.LSTM(dropout=) does (layer l: site l + 1; nothing to act on with one layer)
+        self.dropout_p = self.lstm_dropout_p = 0.0
+        self.last_dropout_seed = None     # seed of the last forward that dropped anything
         self._id_guard = None
         self.init_weights()
 
@@ -547,7 +570,10 @@ class DecoderRNN(nn.Module):
         """Decode image feature vectors and generate caption logits (models.py:47-54): f32 [sum(lengths), V],
         rows in time-major packed order.  In training mode with ss_prob > 0 the input of step t >= 2 is, with probability
         ss_prob, a token drawn from softmax(logits of step t-1) (scheduled sampling; seed drawn from torch's CPU generator);
-        the tokens fed and the seed are kept as `last_ss_inputs` / `last_ss_seed`."""
+        the tokens fed and the seed are kept as `last_ss_inputs` / `last_ss_seed`.  In training mode `dropout_p` / `lstm_dropout_p`
+        drop activations (see `__init__`); the masks' seed, one `draw_ss_seed()` per forward that drops, stays on
+        `last_dropout_seed`.  Dropout together with ss_prob > 0 raises NotImplementedError."""
+        dropout = self.dropout_plan(sampling=self.training and self.ss_prob > 0)
         features = _f32c(features, "features")
         L.require_gpu(captions, "captions")
         if len(lengths) != features.shape[0]:
@@ -562,11 +588,30 @@ class DecoderRNN(nn.Module):
         ss = None
         if self.training and self.ss_prob > 0:
             ss = dict(prob=float(self.ss_prob), seed=draw_ss_seed(), rank=int(self.ss_rank))
+        if dropout is not None:
+            dropout = self.draw_dropout(dropout)
         names, tensors = zip(*self.named_parameters())
-        out = _DecoderFn.apply(features, captions, pi, ss, names, *tensors)
+        out = _DecoderFn.apply(features, captions, pi, ss, dropout, names, *tensors)
         if ss is not None:
             self.last_ss_inputs, self.last_ss_seed = ss["used"], ss["seed"]
         return out
+
+    def dropout_plan(self, sampling=False, what="ss_prob > 0 (scheduled sampling)"):
+        """(p_out, p_lstm) of a training forward, or None when nothing is dropped (eval mode, both probabilities 0, or only
+        `lstm_dropout_p` on a one-layer LSTM).  Host checks only, nothing drawn: ValueError for a probability outside [0, 1),
+        NotImplementedError when masks are active and `sampling` says the forward is one of the step loops (`what`)."""
+        p_out, p_lstm = check_dropout_p(self.dropout_p, "dropout_p"), check_dropout_p(self.lstm_dropout_p, "lstm_dropout_p")
+        if not self.training:
+            return None
+        active = [n for n, p in (("dropout_p", p_out), ("lstm_dropout_p", p_lstm if self.num_layers > 1 else 0.0)) if p > 0]
+        if sampling:
+            refuse_dropout_with(active, what)
+        return (p_out, p_lstm if self.num_layers > 1 else 0.0) if active else None
+
+    def draw_dropout(self, plan):
+        """`decoder_forward`'s dropout argument (p_out, p_lstm, seed, rank) for an active `dropout_plan`: draws the forward's seed"""
+        self.last_dropout_seed = draw_ss_seed()
+        return plan + (self.last_dropout_seed, int(self.ss_rank))
 
     def rollout(self, features, steps=20):
         """`sample` with a DRAW from softmax(logits) where `sample` takes the arg-max, in training form (self-critical sequence
@@ -576,6 +621,7 @@ class DecoderRNN(nn.Module):
         Rows keep running behind their <end>: `scst_loss` masks them."""
         if not self.training:
             raise RuntimeError("DecoderRNN.rollout is a training forward (decoder.train()); eval mode decodes with sample()")
+        self.dropout_plan(sampling=True, what="a rollout")
         features = _f32c(features, "features")
         seed = draw_ss_seed()
         names, tensors = zip(*self.named_parameters())
@@ -762,6 +808,7 @@ class ShowAndTell(nn.Module):
         trains fc / bn.  image_index: the corpus image of every row, as for `CiderScorer.score`.  The `SelfCritical` object (its
         last_reward, last_baseline, last_ids) is kept as `last_scst`."""
         from .scst import SelfCritical
+        self.decoder.dropout_plan(sampling=True, what="a rollout (scst_forward)")            # before the encoder runs
         self.last_scst = SelfCritical(scorer, end_id)
         return self.last_scst(self.decoder, self.encoder(images), image_index)
 

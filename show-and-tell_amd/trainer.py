@@ -159,6 +159,7 @@ class TrainStep:
         dec = model.decoder
         if not model.training:
             raise RuntimeError("TrainStep needs model.train() (batch-statistics BatchNorm, train.py never calls eval())")
+        dropout = dec.dropout_plan(sampling=dec.ss_prob > 0)         # host checks, before anything is launched or drawn
         L.require_gpu(captions, "captions")
         dev = images.device
         st = L.stream()
@@ -202,8 +203,13 @@ class TrainStep:
             # scheduled sampling (model.training is required above): the step loop with its draws; exact-f32 logits for sat_ce_rows,
             # or in the bf16 mode draws only and the mode's projection + CE over every row (`ce`)
             ss = (dec.ss_prob, draw_ss_seed(), dec.ss_rank)
+        if dropout is not None:
+            dropout = dec.draw_dropout(dropout)
         logits, tapes = decoder_forward(lib, feats_in, params, captions[:, :-1], pi, self.lstm_ws, logits=bufs["logits"], ce=ce,
-                                        mixed_ws=mixed_ws, ss=ss)
+                                        mixed_ws=mixed_ws, ss=ss, dropout=dropout)
+        # a step that dropped keeps the top layer's dropped tape [N, H] (what `linear` read) until the next step: the tests compare its
+        # zero pattern with the mask of `last_dropout_seed`
+        self.last_dropped_tape = tapes["X"][-1] if dropout is not None else None
         if ss is not None:
             dec.last_ss_inputs, dec.last_ss_seed = tapes["captions"], ss[1]
         if ce is None:
@@ -277,6 +283,7 @@ class TrainStep:
         dec = model.decoder
         if not model.training:
             raise RuntimeError("TrainStep needs model.train() (batch-statistics BatchNorm, train.py never calls eval())")
+        dec.dropout_plan(sampling=True, what="a rollout (scst_step)")
         dev = images.device
         B, steps = images.shape[0], int(steps)
         bufs = self._step_bufs(B, B * steps, dev)
