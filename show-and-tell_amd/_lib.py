@@ -296,6 +296,13 @@ def pad_rows4(d):
     return out
 
 
+def workspace256(nbytes, device):
+    """(uint8 tensor, address): `nbytes` of workspace whose address is a multiple of 256; the tensor keeps it alive"""
+    import torch
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256
+
+
 def require_gpu(t, name="tensor"):
     if not t.is_cuda:
         raise RuntimeError("show-and-tell_amd: %s must live on the MI355X (got a %s tensor); the HIP path has no CPU fallback"

@@ -10,8 +10,8 @@
                (model2.py:80-85); with ss_prob > 0 (scheduled sampling, train.py:109-113) the whole loop, output layer and
                Gumbel-max draws per step, is one `sat_ss_attend_fwd` call.  `_AttendRolloutFn` (`rollout`, `scst_forward`: self-
                critical training) feeds the decoder its own tokens -- drawn, or the arg-max -- as one `sat_rollout_attend_fwd` call
-    eval     : `_EvalDecoder`, one decode step over R rows; `sample_features` (R = B) and `sample_beam_features` (R = B * K) pick
-               the tokens
+    eval     : `_EvalDecoder` -- the setup for R rows, one decode step and the loop around it; `sample_features` (R = B),
+               `sample_stochastic_features` (R = B * S) and `sample_beam_features` (R = B * K) each supply the choice of a step's tokens
     backward : `attend_bwd.py`, hand-written (sat_attention_bwd, LSTMCell BPTT, batched weight-gradient GEMMs) behind
                torch.autograd, so `loss.backward()` (train.py:144) works unchanged
 
@@ -27,7 +27,7 @@ import torch.nn as nn
 from . import _lib as L
 from .attend_bwd import PARAM_ORDER, attend_backward
 from .decoder import dropout_rows
-from .models import check_dropout_p, check_sample_args, draw_ss_seed, lookahead_stream, refuse_dropout_with
+from .models import check_dropout_p, check_sample_args, draw_ss_seed, lookahead_stream, refuse_dropout_with, stochastic_result
 from .pack import PackInfo
 from .scst import SelfCritical
 from .vgg import VGG16_FEATURES, VggFeatures, VggProgram, _VggFn  # noqa: F401  (VggFeatures is re-exported by the package)
@@ -260,20 +260,52 @@ class _AttendRolloutFn(torch.autograd.Function):
 
 
 class _EvalDecoder:
-    """The eval-mode decode step of `sample` / `sample_beam` (model2.py:91-111) over R rows and its buffers: the state h, c (h2 is
-    where the LSTMCell writes; the two swap), this step's context ctxb, the LSTMCell input X = [embedding | context] and the output
-    layer's Z [R, E], which the caller's token selection reads."""
+    """The eval-mode decode of `sample` / `sample_stochastic` / `sample_beam` (model2.py:91-111) over R = B * rows rows: the setup
+    all three share, one decode step, and the loop around it, which leaves only the choice of a step's tokens to its caller.
 
-    def __init__(self, lib, m, f2, ctx_enc, h, c):
-        dev = f2.device
-        (R, H), C, E = h.shape, f2.shape[1], m.embed_size
-        self.lib, self.m, self.f2, self.ctx_enc, self.h, self.c = lib, m, f2, ctx_enc, h, c
-        self.dims = R, f2.shape[0] // R, C, E, H, m.vocab_size
+    Setup: `states` is checked before anything touches the device; the features (repeated `rows` times per image, row b * rows + r)
+    as f2 [R * P, C] and their attention encoding; the state h, c as PRIVATE copies of `states` (zeros for None) -- the caller's
+    tensors are never written; h2 is where the LSTMCell writes (the two swap); this step's context ctxb, the LSTMCell input X =
+    [embedding | context] and the output layer's Z [R, E], which the token choice reads; the `start` column step 0 feeds; with
+    return_alphas the maps of every step, amaps [steps, R, P] (step i's slice is the attention kernel's alpha output)."""
+
+    def __init__(self, m, features, states, rows, steps, start_id, return_alphas):
+        B, P, C = features.shape
+        E, H = m.embed_size, m.hidden_size
+        _check_states(states, B, H)
+        L.require_gpu(features, "features")
+        lib, dev, R = L.load(), features.device, B * rows
+        feats = features.contiguous()
+        if rows > 1:
+            feats = feats.repeat_interleave(rows, 0).contiguous()
+        self.lib, self.m, self.steps = lib, m, steps
+        self.f2 = f2 = feats.view(R * P, C)
+        self.ctx_enc = _context_encode(lib, m, f2)
+        if states is None:
+            self.h, self.c = torch.zeros(R, H, device=dev), torch.zeros(R, H, device=dev)
+        elif rows > 1:
+            self.h, self.c = (s.to(dev).float().repeat_interleave(rows, 0).contiguous() for s in states)
+        else:
+            self.h, self.c = (s.to(dev).float().contiguous().clone() for s in states)
+        self.dims = R, P, C, E, H, m.vocab_size
         self.h2 = torch.empty(R, H, device=dev)
         self.proj, self.X = torch.empty(R, C, device=dev), torch.empty(R, H, device=dev)
         self.ctxb, self.Zin, self.Z = torch.empty(R, C, device=dev), torch.empty(R, C + H, device=dev), torch.empty(R, E, device=dev)
         self.Wz = _output_weight(lib, m)
         self.att_ws = torch.empty(f2.shape[0], device=dev)        # R * P
+        self.start = torch.full((R,), int(start_id), dtype=torch.int64, device=dev)
+        self.amaps = torch.empty(steps, R, P, device=dev) if return_alphas else None
+
+    def run(self, pick):
+        """The decode loop.  `pick(i)` chooses step i's tokens from this step's Z (and may re-order the state); it returns what is
+        fed with them: (device pointer of the R int64 tokens, their stride, the context rows)."""
+        for i in range(self.steps):
+            self.step(self.amaps[i].data_ptr() if self.amaps is not None else None, self.start if i == 0 else None)
+            self.feed(*pick(i))
+
+    def maps(self, lead):
+        """the recorded maps, rows first: f32 [*lead, steps, P] (lead: the shape the R rows are viewed as)"""
+        return self.amaps.transpose(0, 1).contiguous().view(tuple(lead) + (self.steps, self.dims[1]))
 
     def step(self, alpha=None, first=None):
         """h, c -> the next h, c and Z.  alpha: None or the device pointer that receives this step's maps [R, P]; first: the
@@ -573,33 +605,22 @@ class ShowAttendTellModel(nn.Module):
 
     @torch.no_grad()
     def sample_features(self, features, states=None, steps=20, start_id=1, return_alphas=False):
-        """`sample` given the features [B, P, C]: `_EvalDecoder.step` on B rows, `sat_vocab_argmax` picks each step's token."""
-        lib = L.load()
-        m, dev, st = self, features.device, L.stream()
-        B, P, C = features.shape
-        E, H, V = m.embed_size, m.hidden_size, m.vocab_size
-        _check_states(states, B, H)
-        f2 = features.contiguous().view(B * P, C)
-        ctx_enc = _context_encode(lib, m, f2)
-        if states is None:
-            h, c = torch.zeros(B, H, device=dev), torch.zeros(B, H, device=dev)
-        else:
-            h, c = states[0].to(dev).float().contiguous().clone(), states[1].to(dev).float().contiguous().clone()
-        d = _EvalDecoder(lib, m, f2, ctx_enc, h, c)
-        ids = torch.full((B, steps), int(start_id), dtype=torch.int64, device=dev)
-        start = torch.full((B,), int(start_id), dtype=torch.int64, device=dev)
+        """`sample` given the features [B, P, C]: `_EvalDecoder.run` on B rows, `sat_vocab_argmax` picks each step's token."""
+        d = _EvalDecoder(self, features, states, 1, steps, start_id, return_alphas)
+        lib, st, cls = d.lib, L.stream(), self.classifier
+        B, P, C, E, H, V = d.dims
+        ids = torch.full((B, steps), int(start_id), dtype=torch.int64, device=features.device)
         wsb = lib.sat_vocab_argmax_ws_bytes(B, V)
-        ws = torch.empty(wsb // 4, device=dev)
-        amaps = torch.empty(steps, B, P, device=dev) if return_alphas else None       # step i's maps: the kernel's alpha output
-        for i in range(steps):
-            d.step(amaps[i].data_ptr() if return_alphas else None, start if i == 0 else None)
+        ws = torch.empty(wsb // 4, device=features.device)
+
+        def pick(i):
             col = ids[:, i]
-            L.check(lib.sat_vocab_argmax(L.ptr(d.Z), L.ptr(m.classifier.weight), L.ptr(m.classifier.bias), B, E, V, col.data_ptr(),
-                                         ids.stride(0), L.ptr(ws), wsb, st), "sat_vocab_argmax")
-            d.feed(col.data_ptr(), ids.stride(0), d.ctxb)
-        if return_alphas:
-            return ids, amaps.transpose(0, 1).contiguous()
-        return ids
+            L.check(lib.sat_vocab_argmax(L.ptr(d.Z), L.ptr(cls.weight), L.ptr(cls.bias), B, E, V, col.data_ptr(), ids.stride(0),
+                                         L.ptr(ws), wsb, st), "sat_vocab_argmax")
+            return col.data_ptr(), ids.stride(0), d.ctxb
+
+        d.run(pick)
+        return (ids, d.maps((B,))) if return_alphas else ids
 
     @torch.no_grad()
     def sample_stochastic(self, images, states=None, **kw):
@@ -625,55 +646,35 @@ class ShowAttendTellModel(nn.Module):
         steps = int(steps)
         if steps < 1:
             raise ValueError("steps must be >= 1")
-        m, dev = self, features.device
-        B, P, C = features.shape
-        E, H, V = m.embed_size, m.hidden_size, m.vocab_size
-        _check_states(states, B, H)
-        L.require_gpu(features, "features")
-        lib, st = L.load(), L.stream()
-        R = B * S
-        feats = features.contiguous()
-        if S > 1:
-            feats = feats.repeat_interleave(S, 0).contiguous()
-        f2 = feats.view(R * P, C)
-        ctx_enc = _context_encode(lib, m, f2)
-        if states is None:
-            h, c = torch.zeros(R, H, device=dev), torch.zeros(R, H, device=dev)
-        else:
-            h = states[0].to(dev).float().repeat_interleave(S, 0).contiguous().clone()
-            c = states[1].to(dev).float().repeat_interleave(S, 0).contiguous().clone()
+        d = _EvalDecoder(self, features, states, S, steps, start_id, return_alphas)
+        lib, st, dev, cls = d.lib, L.stream(), features.device, self.classifier
+        R, P, C, E, H, V = d.dims
         if seed is None:
             seed = draw_ss_seed()
-        d = _EvalDecoder(lib, m, f2, ctx_enc, h, c)
         ids = torch.full((R, steps), int(start_id), dtype=torch.int64, device=dev)
-        start = torch.full((R,), int(start_id), dtype=torch.int64, device=dev)
         ldl = L.pad4(V)
         logits = torch.zeros(steps if return_logits else 1, R, ldl, device=dev)
         logp = torch.empty(steps, R, device=dev) if return_logprobs else None
         kept = torch.empty(steps, R, dtype=torch.int32, device=dev) if return_logprobs else None
         wsb = lib.sat_sample_filtered_ws_bytes(R, V)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        amaps = torch.empty(steps, R, P, device=dev) if return_alphas else None
-        for i in range(steps):
-            d.step(amaps[i].data_ptr() if return_alphas else None, start if i == 0 else None)
-            lg = logits[i if return_logits else 0]
-            L.check(lib.sat_vocab_logits_fwd(L.ptr(d.Z), L.ptr(m.classifier.weight), L.ptr(m.classifier.bias), R, E, V, lg.data_ptr(),
-                                             ldl, st), "sat_vocab_logits_fwd")
-            col = ids[:, i]
+
+        def pick(i):
+            lg, col = logits[i if return_logits else 0], ids[:, i]
+            L.check(lib.sat_vocab_logits_fwd(L.ptr(d.Z), L.ptr(cls.weight), L.ptr(cls.bias), R, E, V, lg.data_ptr(), ldl, st),
+                    "sat_vocab_logits_fwd")
             L.check(lib.sat_sample_filtered(lg.data_ptr(), ldl, R, V, tau, top_k, top_p, seed, i, int(self.ss_rank), col.data_ptr(),
                                             ids.stride(0), logp[i].data_ptr() if return_logprobs else None,
                                             kept[i].data_ptr() if return_logprobs else None, L.ptr(ws), wsb, st), "sat_sample_filtered")
-            d.feed(col.data_ptr(), ids.stride(0), d.ctxb)
+            return col.data_ptr(), ids.stride(0), d.ctxb
+
+        d.run(pick)
         self.last_sample_seed = seed
-        shape = (B, S, steps) if S > 1 else (B, steps)
-        out = [ids.view(shape)]
-        if return_logprobs:
-            out.append(dict(logp=logp.t().contiguous().view(shape), kept=kept.t().contiguous().view(shape)))
-        if return_logits:
-            out.append(logits[:, :, :V])
-        if return_alphas:
-            out.append(amaps.transpose(0, 1).contiguous().view(shape + (P,)))
-        return out[0] if len(out) == 1 else tuple(out)
+        lead = (R // S, S) if S > 1 else (R,)
+        return stochastic_result(ids.view(lead + (steps,)),
+                                 dict(logp=logp.t().contiguous().view(lead + (steps,)),
+                                      kept=kept.t().contiguous().view(lead + (steps,))) if return_logprobs else None,
+                                 logits[:, :, :V] if return_logits else None, d.maps(lead) if return_alphas else None)
 
     @torch.no_grad()
     def sample_beam_features(self, features, beam_size=5, states=None, end_id=None, steps=20, start_id=1, return_all=False,
@@ -686,25 +687,14 @@ class ShowAttendTellModel(nn.Module):
         return_alphas: the attention maps follow as the last value -- [B,steps,P] of the best hypothesis, with return_all
         [B,K,steps,P] best-first.  Every step's maps are recorded per slot and `sat_beam_backtrack_rows` follows the parent chain:
         the map of a step belongs to the slot its survivor was expanded from."""
-        lib = L.load()
-        m, dev, st = self, features.device, L.stream()
-        B, P, C = features.shape
         K = int(beam_size)
         if K < 1 or K > 8:
             raise ValueError("beam_size must be in 1..8")
-        E, H, V = m.embed_size, m.hidden_size, m.vocab_size
-        _check_states(states, B, H)
-        R = B * K
-        feats = features.contiguous().repeat_interleave(K, 0).contiguous()           # [R, P, C]
-        f2 = feats.view(R * P, C)
-        ctx_enc = _context_encode(lib, m, f2)
-        if states is None:
-            h, c = torch.zeros(R, H, device=dev), torch.zeros(R, H, device=dev)
-        else:
-            h = states[0].to(dev).float().repeat_interleave(K, 0).contiguous()
-            c = states[1].to(dev).float().repeat_interleave(K, 0).contiguous()
+        d = _EvalDecoder(self, features, states, K, steps, start_id, return_alphas)
+        lib, st, dev, cls = d.lib, L.stream(), features.device, self.classifier
+        R, P, C, E, H, V = d.dims
+        B = R // K
         c2, ctx2 = torch.empty(R, H, device=dev), torch.empty(R, C, device=dev)
-        d = _EvalDecoder(lib, m, f2, ctx_enc, h, c)
         ldl = L.pad4(V)
         logits = torch.zeros(R, ldl, device=dev)
         scores = torch.full((B, K), float("-inf"), device=dev)
@@ -713,16 +703,15 @@ class ShowAttendTellModel(nn.Module):
         bws = torch.empty(lib.sat_beam_step_ws_bytes(B, K), dtype=torch.uint8, device=dev)
         parents = torch.empty(steps, R, dtype=torch.int32, device=dev)
         tokens = torch.empty(steps, R, dtype=torch.int64, device=dev)
-        start = torch.full((R,), int(start_id), dtype=torch.int64, device=dev)
-        amaps = torch.empty(steps, R, P, device=dev) if return_alphas else None
         eid = -1 if end_id is None else int(end_id)
-        for i in range(steps):
-            d.step(amaps[i].data_ptr() if return_alphas else None, start if i == 0 else None)
-            L.check(lib.sat_vocab_logits_fwd(L.ptr(d.Z), L.ptr(m.classifier.weight), L.ptr(m.classifier.bias), R, E, V, L.ptr(logits),
-                                             ldl, st), "sat_vocab_logits_fwd")
+
+        def pick(i):
+            nonlocal scores, scores2, c2
+            L.check(lib.sat_vocab_logits_fwd(L.ptr(d.Z), L.ptr(cls.weight), L.ptr(cls.bias), R, E, V, L.ptr(logits), ldl, st),
+                    "sat_vocab_logits_fwd")
             last = tokens[i - 1].data_ptr() if (i > 0 and eid >= 0) else None
-            L.check(lib.sat_beam_step(L.ptr(logits), ldl, L.ptr(scores), last, eid, B, K, V, parents[i].data_ptr(), tokens[i].data_ptr(),
-                                      L.ptr(scores2), L.ptr(bws), bws.numel(), st), "sat_beam_step")
+            L.check(lib.sat_beam_step(L.ptr(logits), ldl, L.ptr(scores), last, eid, B, K, V, parents[i].data_ptr(),
+                                      tokens[i].data_ptr(), L.ptr(scores2), L.ptr(bws), bws.numel(), st), "sat_beam_step")
             scores, scores2 = scores2, scores
             src_ctx = d.ctxb
             if K > 1:                                    # the survivors' state: h, c and THIS step's context follow their parent
@@ -731,12 +720,14 @@ class ShowAttendTellModel(nn.Module):
                 d.h, d.h2, d.c, c2 = d.h2, d.h, c2, d.c
                 L.check(lib.sat_beam_gather_rows(L.ptr(d.ctxb), parents[i].data_ptr(), B, K, C, L.ptr(ctx2), st), "sat_beam_gather_rows")
                 src_ctx = ctx2
-            d.feed(tokens[i].data_ptr(), 1, src_ctx)
+            return tokens[i].data_ptr(), 1, src_ctx
+
+        d.run(pick)
         ids = torch.empty(B, K, steps, dtype=torch.int64, device=dev)
         L.check(lib.sat_beam_backtrack(L.ptr(parents), L.ptr(tokens), steps, B, K, L.ptr(ids), st), "sat_beam_backtrack")
         if return_alphas:
             alphas = torch.empty(B, K, steps, P, device=dev)
-            L.check(lib.sat_beam_backtrack_rows(L.ptr(parents), L.ptr(amaps), steps, B, K, P, L.ptr(alphas), st), "sat_beam_backtrack_rows")
+            L.check(lib.sat_beam_backtrack_rows(L.ptr(parents), L.ptr(d.amaps), steps, B, K, P, L.ptr(alphas), st), "sat_beam_backtrack_rows")
             if return_all:
                 return ids, scores, alphas
             return ids[:, 0].contiguous(), alphas[:, 0].contiguous()

@@ -7,7 +7,7 @@
 //   beam_merge_kernel one wave per image: the K best of its K*K row candidates.
 // The union of per-row top-K lists contains the global top-K, and both kernels order candidates by (score desc, flat
 // index k*V+v asc), so the result is the exact top-K with a deterministic tie rule.
-#include "sat_internal.h"
+#include "sat_decode_state.h"
 #include <limits.h>
 
 namespace {
@@ -491,7 +491,6 @@ extern "C" int sat_beam_step(const float* logits, int64_t ldl, const float* scor
 //      5 launches per step (one LSTM layer) from C with no Python in between: LSTM step, exact-f32 vocab projection, per-row
 //      log-softmax + top-K, per-image merge (which also gathers the next step's embedding rows), ONE (h, c) re-ordering launch per
 //      layer.  Same kernels, same order, same arithmetic as the step-by-step entry points: bit-identical ids and scores. ----
-static int64_t al256(int64_t n) { return (n + 255) / 256 * 256; }
 constexpr int kBeamKSplitMax = 8;      // K-split slices of the wide LSTM step's gate GEMM (the workspace holds that many [R][4H] slabs)
 
 extern "C" int64_t sat_beam_decode_ws_bytes(int B, int K, int E, int H, int V, int num_layers, int steps) {
@@ -705,29 +704,17 @@ extern "C" int sat_greedy_decode(const float* features, const float* embed, cons
                                  const float* lin_w, const float* lin_b, int B, int E, int H, int V, int steps, float* h, float* c,
                                  float* h_tmp, float* x_tmp /*[B][E]*/, int64_t* ids, int64_t ids_stride, float* workspace,
                                  int64_t ws_bytes, sat_stream_t stream) {
-    if (!features || !embed || !lstm_w || !lin_w || !lin_b || !h || !c || !h_tmp || !x_tmp || !ids || !workspace) return SAT_ERR_ARG;
-    if (B <= 0 || E <= 0 || H <= 0 || V <= 0 || num_layers < 1 || num_layers > 8 || steps < 1 || ids_stride < steps) return SAT_ERR_ARG;
+    SAT_TRY(sat_decode_check(features, embed, lstm_w, num_layers, lin_w, lin_b, B, E, H, V, steps, h, c, h_tmp, x_tmp, ids, ids_stride));
+    if (!workspace) return SAT_ERR_ARG;
     if (ws_bytes < sat_vocab_argmax_ws_bytes(B, V)) return SAT_ERR_WORKSPACE;
-    float* hb[8][2];
-    for (int l = 0; l < num_layers; ++l) { hb[l][0] = h + (long)l * B * H; hb[l][1] = h_tmp + (long)l * B * H; }
-    int cur[8] = {0};
+    SatDecodeStack stack(lstm_w, num_layers, B, E, H, h, c, h_tmp, stream);
     const float* x = features;
     for (int i = 0; i < steps; ++i) {
-        const float* inp = x;
-        for (int l = 0; l < num_layers; ++l) {
-            SAT_TRY(sat_lstm_step(inp, hb[l][cur[l]], c + (long)l * B * H, lstm_w[4 * l], lstm_w[4 * l + 1], lstm_w[4 * l + 2],
-                                  lstm_w[4 * l + 3], B, l == 0 ? E : H, H, hb[l][1 - cur[l]], stream));
-            cur[l] = 1 - cur[l];
-            inp = hb[l][cur[l]];
-        }
-        SAT_TRY(sat_vocab_argmax(inp, lin_w, lin_b, B, H, V, ids + i, ids_stride, workspace, ws_bytes, stream));
+        const float* top;
+        SAT_TRY(stack.step(x, &top));
+        SAT_TRY(sat_vocab_argmax(top, lin_w, lin_b, B, H, V, ids + i, ids_stride, workspace, ws_bytes, stream));
         SAT_TRY(sat_embed_rows(embed, ids + i, ids_stride, B, E, V, x_tmp, stream));
         x = x_tmp;
     }
-    for (int l = 0; l < num_layers; ++l)
-        if (cur[l]) {                                          // an odd number of steps: the live hidden state sits in the scratch
-            hipError_t e = hipMemcpyAsync(hb[l][0], hb[l][1], (size_t)B * H * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-            if (e != hipSuccess) return (int)e;
-        }
-    return SAT_OK;
+    return stack.finish();
 }

@@ -43,6 +43,9 @@ int sat_outer_wgrad_launch(const float* dz, const float* x, int B, int E, int F,
 int sat_bn1d_bwd_launch(const float* dy, const float* xhat, const float* rstd, const float* gamma, int B, int E,
                         float* dz, float* dgamma, float* dbeta, float* db_fc, hipStream_t s);
 
+// n rounded up to 256: the pieces of a byte workspace start on 256-byte boundaries
+inline int64_t al256(int64_t n) { return (n + 255) / 256 * 256; }
+
 // fixed-point scale (2^22) of the integer-atomic BatchNorm statistics shared by the conv epilogue and its consumers
 #define SAT_STAT_SCALE 4194304.0
 

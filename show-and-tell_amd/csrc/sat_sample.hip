@@ -17,7 +17,7 @@
 //
 // No sort, no host read, no float accumulation whose order could vary: ids, kept and logp are functions of (row contents,
 // temperature, top_k, top_p, seed, rank, r, t) alone.
-#include "sat_internal.h"
+#include "sat_decode_state.h"
 #include <limits.h>
 #include <math.h>
 
@@ -413,8 +413,6 @@ int filtered_launch(const float* logits, int64_t ldl, int R, int V, float temper
     return SAT_OK;
 }
 
-int64_t al256(int64_t n) { return (n + 255) / 256 * 256; }
-
 }  // namespace
 
 extern "C" int64_t sat_sample_filtered_ws_bytes(int R, int V) { return (R < 1 || V < 1) ? 0 : kWsBytes; }
@@ -430,7 +428,7 @@ extern "C" int sat_sample_filtered(const float* logits, int64_t ldl, int R, int 
 
 // ---- `DecoderRNN.sample`'s loop (models.py:56-67) with a filtered draw where it takes the arg-max, as ONE call: steps x (LSTM step
 //      per layer, exact-f32 vocab projection stored, sat_sample_filtered with t = the step, embedding row of the drawn id), enqueued
-//      from C for the reason given at sat_greedy_decode.  State handling is sat_greedy_decode's. ----
+//      from C for the reason given at sat_greedy_decode.  State handling is sat_greedy_decode's (SatDecodeStack). ----
 extern "C" int64_t sat_sample_decode_ws_bytes(int B, int E, int H, int V, int num_layers) {
     if (B < 1 || E < 1 || H < 1 || V < 1 || num_layers < 1) return 0;
     return al256((int64_t)B * ((V + 3) / 4 * 4) * 4) + al256(sat_sample_filtered_ws_bytes(B, V));
@@ -441,11 +439,8 @@ extern "C" int sat_sample_decode(const float* features, const float* embed, cons
                                  int top_k, float top_p, uint64_t seed, int rank, float* h, float* c, float* h_tmp, float* x_tmp,
                                  int64_t* ids, int64_t ids_stride, float* logp, int32_t* kept, float* logits_out, int64_t ldl,
                                  void* workspace, int64_t ws_bytes, sat_stream_t stream) {
-    if (!features || !embed || !lstm_w || !lin_w || !lin_b || !h || !c || !h_tmp || !x_tmp || !ids || !workspace) return SAT_ERR_ARG;
-    if (B <= 0 || E <= 0 || H <= 0 || V <= 0 || num_layers < 1 || num_layers > 8 || steps < 1 || ids_stride < steps) return SAT_ERR_ARG;
-    if (logits_out && ldl < V) return SAT_ERR_ARG;
-    for (int i = 0; i < 4 * num_layers; ++i)
-        if (!lstm_w[i]) return SAT_ERR_ARG;
+    SAT_TRY(sat_decode_check(features, embed, lstm_w, num_layers, lin_w, lin_b, B, E, H, V, steps, h, c, h_tmp, x_tmp, ids, ids_stride));
+    if (!workspace || (logits_out && ldl < V)) return SAT_ERR_ARG;
     const int64_t lds = (V + 3) / 4 * 4, fws = al256((int64_t)B * lds * 4);
     SAT_TRY(filtered_check(features, V, B, V, temperature, top_k, top_p, 0, rank, ids, workspace, sat_sample_filtered_ws_bytes(B, V)));
     if (ws_bytes < sat_sample_decode_ws_bytes(B, E, H, V, num_layers)) return SAT_ERR_WORKSPACE;
@@ -455,30 +450,18 @@ extern "C" int sat_sample_decode(const float* features, const float* embed, cons
         hipError_t e = hipMemsetAsync(step_logits, 0, (size_t)fws, s);
         if (e != hipSuccess) return (int)e;
     }
-    float* hb[8][2];
-    for (int l = 0; l < num_layers; ++l) { hb[l][0] = h + (long)l * B * H; hb[l][1] = h_tmp + (long)l * B * H; }
-    int cur[8] = {0};
+    SatDecodeStack stack(lstm_w, num_layers, B, E, H, h, c, h_tmp, stream);
     const float* x = features;
     for (int i = 0; i < steps; ++i) {
-        const float* inp = x;
-        for (int l = 0; l < num_layers; ++l) {
-            SAT_TRY(sat_lstm_step(inp, hb[l][cur[l]], c + (long)l * B * H, lstm_w[4 * l], lstm_w[4 * l + 1], lstm_w[4 * l + 2],
-                                  lstm_w[4 * l + 3], B, l == 0 ? E : H, H, hb[l][1 - cur[l]], stream));
-            cur[l] = 1 - cur[l];
-            inp = hb[l][cur[l]];
-        }
+        const float* top;
+        SAT_TRY(stack.step(x, &top));
         float* lg = logits_out ? logits_out + (long)i * B * ldl : step_logits;
         const int64_t ld = logits_out ? ldl : lds;
-        SAT_TRY(sat_vocab_logits_fwd(inp, lin_w, lin_b, B, H, V, lg, ld, stream));
+        SAT_TRY(sat_vocab_logits_fwd(top, lin_w, lin_b, B, H, V, lg, ld, stream));
         SAT_TRY(filtered_launch(lg, ld, B, V, temperature, top_k, top_p, seed, i, rank, ids + i, ids_stride, logp ? logp + i : nullptr,
                                 steps, kept ? kept + i : nullptr, steps, s));
         SAT_TRY(sat_embed_rows(embed, ids + i, ids_stride, B, E, V, x_tmp, stream));
         x = x_tmp;
     }
-    for (int l = 0; l < num_layers; ++l)
-        if (cur[l]) {                                          // an odd number of steps: the live hidden state sits in the scratch
-            hipError_t e = hipMemcpyAsync(hb[l][0], hb[l][1], (size_t)B * H * 4, hipMemcpyDeviceToDevice, s);
-            if (e != hipSuccess) return (int)e;
-        }
-    return SAT_OK;
+    return stack.finish();
 }

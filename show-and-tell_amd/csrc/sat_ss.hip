@@ -99,6 +99,49 @@ int sample_step(const float* h, const float* lin_w, const float* lin_b, int M, i
                        s);
 }
 
+// The LSTM stack of the two training loops below on sat_lstm_fwd's tapes: per layer the tapes GA, CS, HS, HP and the cell state
+// (tapes[5l .. 5l+4]) and the weights (w_ih, w_hh, b_ih, b_hh) (lstm_w[4l .. 4l+3]).
+struct TapedStack {
+    float* const* tapes;
+    const float* const* lstm_w;
+    int num_layers, E, H;
+    hipStream_t s;
+
+    bool complete() const {
+        for (int l = 0; l < num_layers; ++l)
+            for (int k = 0; k < 5; ++k)
+                if (!tapes[5 * l + k] || !lstm_w[4 * l + (k & 3)]) return false;
+        return true;
+    }
+
+    // h_{-1} = c_{-1} = 0 for B rows
+    int zero(int B) const {
+        for (int l = 0; l < num_layers; ++l) {
+            hipError_t e = hipMemsetAsync(tapes[5 * l + 3], 0, (size_t)B * H * sizeof(float), s);
+            if (e == hipSuccess) e = hipMemsetAsync(tapes[5 * l + 4], 0, (size_t)B * H * sizeof(float), s);
+            if (e != hipSuccess) return (int)e;
+        }
+        return SAT_OK;
+    }
+
+    // one step of the n rows at packed offset `off`, input rows inp [n][E]; *top = the top layer's h_t (its HS rows).  Per layer,
+    // gates = h_{t-1} W_hh^T + x_t W_ih^T + b_ih + b_hh and the cell update in one launch; tapes GA (activated), CS, HS at the rows
+    // of step t and h_t into HP's rows of step t+1 (n_next of them), as sat_lstm_fwd's per-step form leaves them
+    int step(const float* inp, long off, int n, int n_next, const float** top) const {
+        int In = E;
+        for (int l = 0; l < num_layers; ++l) {
+            float* GA = tapes[5 * l], *CS = tapes[5 * l + 1], *HS = tapes[5 * l + 2], *HP = tapes[5 * l + 3], *cst = tapes[5 * l + 4];
+            SAT_TRY(sat_skinny_lstm(HP + off * H, lstm_w[4 * l + 1], inp, lstm_w[4 * l], In, lstm_w[4 * l + 2], lstm_w[4 * l + 3],
+                                    nullptr, 0, n, H, cst, GA + off * 4 * H, 4L * H, CS + off * H, HS + off * H,
+                                    n_next ? HP + (off + n) * H : nullptr, n_next, s));
+            inp = HS + off * H;
+            In = H;
+        }
+        *top = inp;
+        return SAT_OK;
+    }
+};
+
 }  // namespace
 
 extern "C" int64_t sat_ss_decoder_fwd_ws_bytes(int B, int V) { return (int64_t)B * sat_cdiv(V, 16) * 8; }
@@ -123,9 +166,9 @@ extern "C" int sat_ss_decoder_fwd(const float* features, const float* embed, con
     if (T < 1 || E < 4 || (E & 3) || H < 4 || (H & 3) || V < 1 || num_layers < 1 || num_layers > 8 || rank < 0) return SAT_ERR_ARG;
     if (T > 1 && (!captions || cap_stride < T - 1 || !used || used_stride < T - 1)) return SAT_ERR_ARG;
     if (logits && ldl < V) return SAT_ERR_ARG;
-    for (int l = 0; l < num_layers; ++l)
-        for (int k = 0; k < 5; ++k)
-            if (!tapes[5 * l + k] || !lstm_w[4 * l + (k & 3)]) return SAT_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const TapedStack stack{tapes, lstm_w, num_layers, E, H, s};
+    if (!stack.complete()) return SAT_ERR_ARG;
     const int B = batch_sizes[0];
     long N = 0;
     for (int t = 0; t < T; ++t) {
@@ -133,7 +176,6 @@ extern "C" int sat_ss_decoder_fwd(const float* features, const float* embed, con
         N += batch_sizes[t];
     }
     if (ws_bytes < sat_ss_decoder_fwd_ws_bytes(B, V)) return SAT_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
     // the teacher-forced inputs of every step (features, then embed[captions[b][t-1]]); draws overwrite rows step by step
     SAT_TRY(sat_embed_concat_fwd(features, embed, T > 1 ? captions : nullptr, cap_stride, prefix, T, (int)N, B, E, V, X, stream));
     if (T > 1) {
@@ -141,27 +183,13 @@ extern "C" int sat_ss_decoder_fwd(const float* features, const float* embed, con
                            T - 1, used, (long)used_stride);
         SAT_LAUNCH_CHECK();
     }
-    for (int l = 0; l < num_layers; ++l) {                      // h_{-1} = c_{-1} = 0
-        hipError_t e = hipMemsetAsync(tapes[5 * l + 3], 0, (size_t)B * H * sizeof(float), s);
-        if (e == hipSuccess) e = hipMemsetAsync(tapes[5 * l + 4], 0, (size_t)B * H * sizeof(float), s);
-        if (e != hipSuccess) return (int)e;
-    }
+    SAT_TRY(stack.zero(B));
     long off = 0;
     for (int t = 0; t < T; ++t) {
         const int n = batch_sizes[t];
         const int n_next = (t + 1 < T) ? batch_sizes[t + 1] : 0;
-        const float* inp = X + off * E;
-        int In = E;
-        for (int l = 0; l < num_layers; ++l) {
-            float* GA = tapes[5 * l], *CS = tapes[5 * l + 1], *HS = tapes[5 * l + 2], *HP = tapes[5 * l + 3], *cst = tapes[5 * l + 4];
-            // gates = h_{t-1} W_hh^T + x_t W_ih^T + b_ih + b_hh and the cell update in one launch; tapes GA (activated), CS, HS at
-            // the rows of step t and h_t into HP's rows of step t+1, as sat_lstm_fwd's per-step form leaves them
-            SAT_TRY(sat_skinny_lstm(HP + off * H, lstm_w[4 * l + 1], inp, lstm_w[4 * l], In, lstm_w[4 * l + 2], lstm_w[4 * l + 3],
-                                    nullptr, 0, n, H, cst, GA + off * 4 * H, 4L * H, CS + off * H, HS + off * H,
-                                    n_next ? HP + (off + n) * H : nullptr, n_next, s));
-            inp = HS + off * H;
-            In = H;
-        }
+        const float* inp;
+        SAT_TRY(stack.step(X + off * E, off, n, n_next, &inp));
         float* lg = logits ? logits + off * ldl : nullptr;
         if (t >= 1 && t + 1 < T) {
             // the input of step t+1 >= 2: a draw from this step's logits where mask(b, t+1) holds, the teacher's token elsewhere
@@ -191,30 +219,18 @@ extern "C" int sat_rollout_decoder_fwd(const float* features, const float* embed
     if (B < 1 || steps < 1 || E < 4 || (E & 3) || H < 4 || (H & 3) || V < 1 || num_layers < 1 || num_layers > 8 || rank < 0)
         return SAT_ERR_ARG;
     if (ldl < V || ids_stride < steps || (long)B * steps > 0x7fffffffL) return SAT_ERR_ARG;
-    for (int l = 0; l < num_layers; ++l)
-        for (int k = 0; k < 5; ++k)
-            if (!tapes[5 * l + k] || !lstm_w[4 * l + (k & 3)]) return SAT_ERR_ARG;
-    if (ws_bytes < sat_rollout_decoder_fwd_ws_bytes(B, V)) return SAT_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
+    const TapedStack stack{tapes, lstm_w, num_layers, E, H, s};
+    if (!stack.complete()) return SAT_ERR_ARG;
+    if (ws_bytes < sat_rollout_decoder_fwd_ws_bytes(B, V)) return SAT_ERR_WORKSPACE;
     hipError_t e = hipMemcpyAsync(X, features, (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, s);    // step 0's input
-    for (int l = 0; l < num_layers && e == hipSuccess; ++l) {                                                  // h_{-1} = c_{-1} = 0
-        e = hipMemsetAsync(tapes[5 * l + 3], 0, (size_t)B * H * sizeof(float), s);
-        if (e == hipSuccess) e = hipMemsetAsync(tapes[5 * l + 4], 0, (size_t)B * H * sizeof(float), s);
-    }
     if (e != hipSuccess) return (int)e;
+    SAT_TRY(stack.zero(B));
     for (int t = 0; t < steps; ++t) {
         const long off = (long)t * B;
         const bool more = t + 1 < steps;
-        const float* inp = X + off * E;
-        int In = E;
-        for (int l = 0; l < num_layers; ++l) {
-            float* GA = tapes[5 * l], *CS = tapes[5 * l + 1], *HS = tapes[5 * l + 2], *HP = tapes[5 * l + 3], *cst = tapes[5 * l + 4];
-            SAT_TRY(sat_skinny_lstm(HP + off * H, lstm_w[4 * l + 1], inp, lstm_w[4 * l], In, lstm_w[4 * l + 2], lstm_w[4 * l + 3],
-                                    nullptr, 0, B, H, cst, GA + off * 4 * H, 4L * H, CS + off * H, HS + off * H,
-                                    more ? HP + (off + B) * H : nullptr, more ? B : 0, s));
-            inp = HS + off * H;
-            In = H;
-        }
+        const float* inp;
+        SAT_TRY(stack.step(X + off * E, off, B, more ? B : 0, &inp));
         // ids[b][t] = s(b, t); its embedding row is step t+1's input (the last step's draw is a target only)
         SAT_TRY(sample_step(inp, lin_w, lin_b, B, B, H, V, logits + off * ldl, ldl, 1.0f, seed, t, rank, nullptr, 0, ids + t, ids_stride,
                             more ? embed : nullptr, E, more ? X + (off + B) * E : nullptr, E, workspace, s));

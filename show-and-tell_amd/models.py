@@ -471,6 +471,13 @@ def check_sample_args(temperature, top_k, top_p, num_samples, seed):
     return tau, top_k, p, num_samples, seed
 
 
+def stochastic_result(ids, logprobs, logits, alphas=None):
+    """What a `sample_stochastic` returns: ids, then -- in this order, each only where asked for (not None) -- the dict(logp, kept),
+    the logits and the attention maps; one value alone, else a tuple"""
+    out = [ids] + [x for x in (logprobs, logits, alphas) if x is not None]
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 def check_dropout_p(value, name):
     """A dropout probability as the float32 the kernel receives; a ValueError names the attribute `name` unless it is a finite
     number in [0, 1).  Host arithmetic only: runs before the library is loaded."""
@@ -636,14 +643,10 @@ class DecoderRNN(nn.Module):
         `states`: None (zeros), (h0, c0) each [num_layers, B, H], or eval.py:82-89's stacked [2, B, H] tensor
         (`_initial_states`); the result is squeezed like models.py:67 ([20] at batch 1)."""
         lib = L.load()
-        features = _f32c(features, "features")
-        dev = features.device
-        B = features.shape[0]
+        features, h, c, h_tmp, xe = self._decode_state(features, states, 1)
+        dev, B = features.device, features.shape[0]
         H, V, E = self.hidden_size, self.vocab_size, self.embed_size
         st = L.stream()
-        h0, c0 = self._initial_states(states, B, dev)
-        h, c = h0.clone().contiguous(), c0.clone().contiguous()         # [num_layers, B, H]: state in, state out
-        h_tmp, xe = torch.empty_like(h), torch.empty(B, E, device=dev)
         ids = torch.empty(B, 20, dtype=torch.int64, device=dev)
         wsb = lib.sat_vocab_argmax_ws_bytes(B, V)
         ws = torch.empty(max(wsb // 4, 4), device=dev)
@@ -672,40 +675,38 @@ class DecoderRNN(nn.Module):
         arg-max (`sample`, up to ties between logits: its projection is another kernel with another summation order)."""
         tau, top_k, top_p, S, seed = check_sample_args(temperature, top_k, top_p, num_samples, seed)
         lib = L.load()
-        features = _f32c(features, "features")
-        dev = features.device
-        B = features.shape[0]
+        features, h, c, h_tmp, xe = self._decode_state(features, states, S)
+        dev, R = features.device, features.shape[0]
         H, V, E, steps = self.hidden_size, self.vocab_size, self.embed_size, 20
-        h0, c0 = self._initial_states(states, B, dev)
-        if S > 1:
-            features = features.repeat_interleave(S, 0).contiguous()
-            h0, c0 = h0.repeat_interleave(S, 1), c0.repeat_interleave(S, 1)
-        R = B * S
         if seed is None:
             seed = draw_ss_seed()
-        h, c = h0.clone().contiguous(), c0.clone().contiguous()
-        h_tmp, xe = torch.empty_like(h), torch.empty(R, E, device=dev)
         ids = torch.empty(R, steps, dtype=torch.int64, device=dev)
         logp = torch.empty(R, steps, device=dev) if return_logprobs else None
         kept = torch.empty(R, steps, dtype=torch.int32, device=dev) if return_logprobs else None
         ldl = L.pad4(V)
         logits = torch.zeros(steps * R, ldl, device=dev) if return_logits else None
         wsb = lib.sat_sample_decode_ws_bytes(R, E, H, V, self.num_layers)
-        ws = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
-        off = (-ws.data_ptr()) % 256
+        ws, ws_ptr = L.workspace256(wsb, dev)
         L.check(lib.sat_sample_decode(L.ptr(features), L.ptr(self.embed.weight), self._lstm_ptrs(), self.num_layers,
                                       L.ptr(self.linear.weight), L.ptr(self.linear.bias), R, E, H, V, steps, tau, top_k, top_p, seed,
                                       int(self.ss_rank), L.ptr(h), L.ptr(c), L.ptr(h_tmp), L.ptr(xe), ids.data_ptr(), ids.stride(0),
-                                      L.ptr(logp), L.ptr(kept), L.ptr(logits), ldl, ws.data_ptr() + off, wsb, L.stream()),
-                "sat_sample_decode")
+                                      L.ptr(logp), L.ptr(kept), L.ptr(logits), ldl, ws_ptr, wsb, L.stream()), "sat_sample_decode")
         self.last_sample_seed = seed
-        shape = (B, S, steps) if S > 1 else (B, steps)
-        out = [ids.view(shape)]
-        if return_logprobs:
-            out.append(dict(logp=logp.view(shape), kept=kept.view(shape)))
-        if return_logits:
-            out.append(logits.view(steps, R, ldl)[:, :, :V])
-        return out[0] if len(out) == 1 else tuple(out)
+        shape = (R // S, S, steps) if S > 1 else (R, steps)
+        return stochastic_result(ids.view(shape), dict(logp=logp.view(shape), kept=kept.view(shape)) if return_logprobs else None,
+                                 logits.view(steps, R, ldl)[:, :, :V] if return_logits else None)
+
+    def _decode_state(self, features, states, rows):
+        """What `sample` / `sample_stochastic` hand the decode call for `rows` rows per image (row b * rows + r): the features f32
+        [R, E], the state h, c [num_layers, R, H] as PRIVATE contiguous copies of `states` (`_initial_states`; state in, state out:
+        the caller's tensors are never written), the scratch h_tmp of h's size and the embedding rows xe [R, E]"""
+        features = _f32c(features, "features")
+        h, c = self._initial_states(states, features.shape[0], features.device)
+        if rows > 1:
+            features = features.repeat_interleave(rows, 0).contiguous()
+            h, c = h.repeat_interleave(rows, 1), c.repeat_interleave(rows, 1)
+        h, c = h.clone().contiguous(), c.clone().contiguous()
+        return features, h, c, torch.empty_like(h), torch.empty(features.shape[0], self.embed_size, device=features.device)
 
     def _lstm_ptrs(self):
         """HOST array of the LSTM's device pointers, (w_ih, w_hh, b_ih, b_hh) per layer: the `lstm_w` argument of the decode calls"""
@@ -758,15 +759,14 @@ class DecoderRNN(nn.Module):
         st = L.stream()
         eid = -1 if end_id is None else int(end_id)
         wsb = lib.sat_beam_decode_ws_bytes(B, K, E, H, V, self.num_layers, steps)
-        ws = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
-        off = (-ws.data_ptr()) % 256
+        ws, ws_ptr = L.workspace256(wsb, dev)
         ids = torch.empty(B, K, steps, dtype=torch.int64, device=dev)
         scores = torch.empty(B, K, device=dev)
         # every step (LSTM step, exact-f32 vocab projection, per-row log-softmax + top-K, per-image merge that also gathers the next
         # input's embedding rows, one (h, c) re-ordering launch) is enqueued by ONE library call (sat_beam_decode)
         L.check(lib.sat_beam_decode(L.ptr(features), L.ptr(self.embed.weight), self._lstm_ptrs(), self.num_layers,
                                     L.ptr(self.linear.weight), L.ptr(self.linear.bias), B, K, E, H, V, int(steps), eid,
-                                    ids.data_ptr(), L.ptr(scores), ws.data_ptr() + off, wsb, st), "sat_beam_decode")
+                                    ids.data_ptr(), L.ptr(scores), ws_ptr, wsb, st), "sat_beam_decode")
         if return_all:
             return ids, scores
         return ids[:, 0].contiguous()

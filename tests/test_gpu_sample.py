@@ -332,16 +332,21 @@ def replay(logits, ids, logp, kept, tau, k, p, seed, rank):
     return n_band, n_close
 
 
-def step_by_step(dec, features, ids, states=None):
-    """the logits [20, R, V] of `sat_lstm_step` / `sat_vocab_logits_fwd` fed the ids returned"""
+def step_by_step(dec, features, ids, states=None, steps=20, pick=None):
+    """`steps` steps, one entry point at a time: (logits [steps, R, V], h, c) of `sat_lstm_step` / `sat_vocab_logits_fwd`.  pick
+    None: fed the ids given.  pick "argmax" (`sat_vocab_argmax`; no logits) or dict(tau, k, p, seed, rank) (`sat_sample_filtered`
+    with t = the step): the tokens are picked here, written to `ids` and fed through `sat_embed_rows`."""
     lib, st = L.load(), L.stream()
     R_, nl = features.shape[0], dec.num_layers
     h = torch.zeros(nl, R_, H5, device="cuda") if states is None else states[0].clone()
     c = torch.zeros(nl, R_, H5, device="cuda") if states is None else states[1].clone()
     ldl = pad4(V5)
-    out = torch.zeros(20, R_, ldl, device="cuda")
+    out = torch.zeros(steps, R_, ldl, device="cuda")
+    lin_w, lin_b = dec.linear.weight.data_ptr(), dec.linear.bias.data_ptr()
+    wsb = max(lib.sat_vocab_argmax_ws_bytes(R_, V5), lib.sat_sample_filtered_ws_bytes(R_, V5))
+    ws, ws_ptr = L.workspace256(wsb, "cuda")
     x = features.contiguous()
-    for t in range(20):
+    for t in range(steps):
         inp = x
         for l in range(nl):
             w_ih, w_hh, b_ih, b_hh = dec.lstm.layer(l)
@@ -350,10 +355,74 @@ def step_by_step(dec, features, ids, states=None):
                                       b_hh.data_ptr(), R_, inp.shape[1], H5, h2.data_ptr(), st), "sat_lstm_step")
             h[l].copy_(h2)
             inp = h2
-        L.check(lib.sat_vocab_logits_fwd(inp.data_ptr(), dec.linear.weight.data_ptr(), dec.linear.bias.data_ptr(), R_, H5, V5,
-                                         out[t].data_ptr(), ldl, st), "sat_vocab_logits_fwd")
-        x = dec.embed.weight[ids[:, t]].contiguous()
+        col = ids[:, t]
+        if pick == "argmax":
+            L.check(lib.sat_vocab_argmax(inp.data_ptr(), lin_w, lin_b, R_, H5, V5, col.data_ptr(), ids.stride(0), ws_ptr, wsb, st),
+                    "sat_vocab_argmax")
+        else:
+            L.check(lib.sat_vocab_logits_fwd(inp.data_ptr(), lin_w, lin_b, R_, H5, V5, out[t].data_ptr(), ldl, st), "sat_vocab_logits_fwd")
+        if pick is None:
+            x = dec.embed.weight[col].contiguous()
+            continue
+        if pick != "argmax":
+            L.check(lib.sat_sample_filtered(out[t].data_ptr(), ldl, R_, V5, pick["tau"], pick["k"], pick["p"], pick["seed"], t, pick["rank"],
+                                            col.data_ptr(), ids.stride(0), None, None, ws_ptr, wsb, st), "sat_sample_filtered")
+        x = torch.empty(R_, E5, device="cuda")
+        L.check(lib.sat_embed_rows(dec.embed.weight.data_ptr(), col.data_ptr(), ids.stride(0), R_, E5, V5, x.data_ptr(), st), "sat_embed_rows")
     return out[:, :, :V5], h, c
+
+
+@pytest.mark.parametrize("steps", [3, 4])
+@pytest.mark.parametrize("layers", [1, 2])
+def test_decode_calls_return_the_ids_and_the_state_of_their_single_steps(layers, steps):
+    """`sat_greedy_decode` and `sat_sample_decode` called directly, from a non-zero (h, c): ids and the final h and c are, bit for
+    bit, those of the same steps issued one entry point at a time.  An even step count ends with every layer's live h in the
+    caller's tensor, an odd one in the scratch: only then does the copy-back run.  (What h_tmp holds afterwards is not checked.)"""
+    lib, st, B = L.load(), L.stream(), 3
+    torch.manual_seed(100 * layers + steps)
+    dec = sat.DecoderRNN(E5, H5, V5, layers).cuda().eval()
+    dec.linear.weight.data.uniform_(-0.6, 0.6)
+    feats = torch.randn(B, E5).cuda()
+    h0, c0 = torch.randn(layers, B, H5).cuda() * 0.5, torch.randn(layers, B, H5).cuda() * 0.5
+    draw = dict(tau=0.8, k=20, p=0.9, seed=SEED, rank=RANK)
+    for pick in ("argmax", draw):
+        want_ids = torch.full((B, steps), -7, dtype=torch.int64, device="cuda")
+        _, want_h, want_c = step_by_step(dec, feats, want_ids, (h0, c0), steps, pick)
+        h, c, h_tmp, xe = h0.clone(), c0.clone(), torch.empty_like(h0), torch.empty(B, E5, device="cuda")
+        ids = torch.full((B, steps), -7, dtype=torch.int64, device="cuda")
+        common = (feats.data_ptr(), dec.embed.weight.data_ptr(), dec._lstm_ptrs(), layers, dec.linear.weight.data_ptr(),
+                  dec.linear.bias.data_ptr(), B, E5, H5, V5, steps)
+        state = (h.data_ptr(), c.data_ptr(), h_tmp.data_ptr(), xe.data_ptr(), ids.data_ptr(), ids.stride(0))
+        if pick == "argmax":
+            wsb = lib.sat_vocab_argmax_ws_bytes(B, V5)
+            ws, ws_ptr = L.workspace256(wsb, "cuda")
+            L.check(lib.sat_greedy_decode(*common, *state, ws_ptr, wsb, st), "sat_greedy_decode")
+        else:
+            wsb = lib.sat_sample_decode_ws_bytes(B, E5, H5, V5, layers)
+            ws, ws_ptr = L.workspace256(wsb, "cuda")
+            L.check(lib.sat_sample_decode(*common, draw["tau"], draw["k"], draw["p"], draw["seed"], draw["rank"], *state, None, None, None,
+                                          0, ws_ptr, wsb, st), "sat_sample_decode")
+        torch.cuda.synchronize()
+        assert (want_ids >= 0).all() and (want_ids < V5).all()
+        assert torch.equal(ids, want_ids), pick
+        assert torch.equal(h, want_h) and torch.equal(c, want_c), pick
+        assert not torch.equal(h, h0) and not torch.equal(c, c0)
+
+
+def test_decoder_rows_per_image_are_plain_repetition():
+    """num_samples = 2 is the num_samples = 1 decode of every feature row and state column repeated twice, under the same seed: the
+    kernels see the same rows and the same counters (row b * S + s)."""
+    torch.manual_seed(21)
+    layers, B = 2, 3
+    dec = sat.DecoderRNN(E5, H5, V5, layers).cuda().eval()
+    dec.linear.weight.data.uniform_(-0.6, 0.6)
+    feats = torch.randn(B, E5).cuda()
+    h0, c0 = torch.randn(layers, B, H5).cuda() * 0.5, torch.randn(layers, B, H5).cuda() * 0.5
+    ids = dec.sample_stochastic(feats, (h0, c0), num_samples=2, seed=31, top_k=20, top_p=0.9)
+    flat = dec.sample_stochastic(feats.repeat_interleave(2, 0), (h0.repeat_interleave(2, 1), c0.repeat_interleave(2, 1)),
+                                 num_samples=1, seed=31, top_k=20, top_p=0.9)
+    assert ids.shape == (B, 2, 20) and flat.shape == (2 * B, 20)
+    assert torch.equal(ids.view(2 * B, 20), flat)
 
 
 @pytest.mark.parametrize("layers,B,S", [(1, 1, 1), (1, 5, 3), (2, 5, 1), (2, 1, 3)])
@@ -454,6 +523,24 @@ def test_attend_sample_stochastic_features():
     ra = model.rollout(feats, feats.mean(1), 6)
     assert all(torch.equal(a, b) for a, b in zip(before, after))
     assert torch.equal(rb[0], ra[0]) and torch.equal(rb[1].detach(), ra[1].detach())
+
+
+def test_attend_rows_per_image_are_plain_repetition():
+    """`sample_stochastic_features` at the smallest legal dims (tests/test_gpu_attend.py's: E 4, C 8, H 12, P 5, V 11; B 3) from a
+    non-zero (h, c): num_samples = 2 is the num_samples = 1 decode of the features and states repeated twice per image under the
+    same seed, ids and attention maps bit for bit; the caller's h and c are not written."""
+    torch.manual_seed(179)
+    B, P, C, E, H, V = 3, 5, 8, 4, 12, 11
+    model = sat.ShowAttendTellModel(H, C, V, E, None, feature_size=(P, C), compute_dtype="f32", vgg_cfg=[C]).cuda().eval()
+    feats = torch.randn(B, P, C).cuda()
+    h, c = torch.randn(B, H).cuda(), torch.randn(B, H).cuda()
+    h_was, c_was = h.clone(), c.clone()
+    ids, alphas = model.sample_stochastic_features(feats, (h, c), num_samples=2, seed=31, top_k=20, top_p=0.9, return_alphas=True)
+    flat, flat_alphas = model.sample_stochastic_features(feats.repeat_interleave(2, 0), (h.repeat_interleave(2, 0), c.repeat_interleave(2, 0)),
+                                                         num_samples=1, seed=31, top_k=20, top_p=0.9, return_alphas=True)
+    assert ids.shape == (B, 2, 20) and alphas.shape == (B, 2, 20, P) and flat.shape == (2 * B, 20) and flat_alphas.shape == (2 * B, 20, P)
+    assert torch.equal(ids.view(2 * B, 20), flat) and torch.equal(alphas.view(2 * B, 20, P), flat_alphas)
+    assert torch.equal(h, h_was) and torch.equal(c, c_was)
 
 
 # ---- 7: argument errors of the two C entry points ----------------------------------------------------------------------------------

@@ -165,3 +165,25 @@ def test_c_entry_points_check_arguments_before_any_launch():
         assert call(**bad) == 1001, bad
     assert call(wsb=need - 1) == 1002
     assert call(V=32769, ldl=32769) == 1003
+
+
+def test_decode_entry_points_share_their_argument_check():
+    """`sat_greedy_decode` and `sat_sample_decode` refuse, before any HIP call: a null entry of lstm_w, num_layers outside 1..8,
+    steps < 1 and an ids row shorter than the steps"""
+    import ctypes as C
+    lib = L.load()
+    fake = C.c_void_p(4096)                     # never dereferenced: every check below fails first
+    B, E, H, V = 3, 8, 16, 100
+    full = [4096] * 36                          # room for the nine layers a bad num_layers asks for
+
+    def calls(lstm_w=full, num_layers=2, steps=4, ids_stride=4):
+        w = (C.c_void_p * len(lstm_w))(*lstm_w)
+        common = (fake, fake, w, num_layers, fake, fake, B, E, H, V, steps)
+        state = (fake, fake, fake, fake, fake, ids_stride)
+        return (lib.sat_greedy_decode(*common, *state, fake, 1 << 30, None),
+                lib.sat_sample_decode(*common, 1.0, 0, 1.0, 7, 0, *state, None, None, None, 0, fake, 1 << 30, None))
+
+    for hole in (0, 3, 5, 7):
+        assert calls(lstm_w=full[:hole] + [None] + full[hole + 1:]) == (1001, 1001), hole
+    for bad in (dict(num_layers=0), dict(num_layers=9), dict(steps=0), dict(steps=-1), dict(ids_stride=3)):
+        assert calls(**bad) == (1001, 1001), bad
