@@ -589,6 +589,64 @@ int sat_beam_decode(const float* features /*[B,E]*/, const float* embed /*[V,E]*
 int sat_greedy_decode(const float* features, const float* embed, const float* const* lstm_w /*[host]*/, int num_layers,
                       const float* lin_w, const float* lin_b, int B, int E, int H, int V, int steps, float* h, float* c, float* h_tmp,
                       float* x_tmp, int64_t* ids, int64_t ids_stride, float* workspace, int64_t ws_bytes, sat_stream_t stream);
+/* Constrained beam search (added within ABI 18): n-gram blocking, banned ids, a minimum length, and a length penalty on the final
+ * ranking.  Step i = 0..T-1.  The PREFIX of row (b, k) at step i is the i tokens y_0..y_{i-1} that hypothesis has emitted, recovered
+ * through the back-pointer records `parents` / `tokens` [T][B*K] that the beam loops keep (rows 0..i-1 valid at step i): slot
+ * s_{i-1} = k, y_t = tokens[t][b*K + s_t], s_{t-1} = parents[t][b*K + s_t].  Nothing else is carried from step to step: the
+ * entry points are stateless.
+ * For a LIVE, UNFINISHED row the banned set at step i is the union of
+ *   1. suppress_ids[0..n_suppress), at every step (ids outside [0, V) are ignored);
+ *   2. end_id, while i < min_length (needs end_id >= 0);
+ *   3. y_{i-1}, if block_repeat and i >= 1;
+ *   4. if no_repeat_ngram = n >= 1 and i >= n: every y_{j+n-1} with 0 <= j <= i-n and y[j..j+n-2] == y[i-n+1..i-1] (the rule of the
+ *      common NoRepeatNGram processors: with n = 1 every token already emitted; an n-gram that overlaps the tail counts).
+ * Scores are NOT renormalised: candidate (k, v) scores scores_in[b,k] + (logit[v] - lse) with lse over ALL V columns of the row,
+ * exactly as in sat_beam_step; a banned v is no candidate.  (Renormalising would raise a hypothesis's score because probability
+ * mass was banned from it; `scores` stays the sum of the model's token log-probabilities.)
+ * A FINISHED row (last token == end_id) is untouched by every constraint: its one continuation is end_id at unchanged score.  A
+ * DEAD row (-inf) has no candidate.  Everything else is sat_beam_step's contract: order (score desc, flat index k*V+v asc), -inf
+ * logits are no candidates, fewer than K candidates leave -inf / parent 0 / token 0 in the surplus slots, a live row needs one
+ * finite, unbanned logit (none: the row has no candidate, as if dead).
+ * LENGTH PENALTY (length_penalty = alpha; 0: off) is applied ONCE, after the last step, per image: L_k = the number of tokens in
+ * front of the first end_id plus 1 for it, T for a row without one (sat_kept_tokens' rule); norm_k = (double)score_k /
+ * pow((double)L_k, (double)alpha), rounded once to f32; the K hypotheses are re-ordered by (norm desc, previous rank asc); dead
+ * hypotheses stay last.  The search itself still selects by raw score: the fixed-width beam keeps finished hypotheses in their
+ * slots, so the final pool is the set a finished-heap implementation would rank.  A re-ranking, not a per-step normalisation.
+ * sat_beam_step_ex: sat_beam_step under `c`.  c == NULL or every step field off: the launches of sat_beam_step, bit-identical
+ *   outputs (so is a step at which `c` bans nothing).  parents / tokens may be NULL at i == 0 or without active constraints.
+ *   workspace: sat_beam_step_ex_ws_bytes (the prefix is walked from the records: no history in the workspace).
+ * sat_beam_rerank: ids [B][K][T], scores [B][K] -> ids_out, scores_out (raw, new order), norm_out (nullable), order_out (nullable;
+ *   [B][K]: the previous rank of the hypothesis now at r); ids_out != ids, scores_out != scores.  K <= 8, any T >= 1.
+ * sat_beam_decode_ex: sat_beam_decode's loop -- the same wide and narrow paths, the same projection -- with the constrained row
+ *   kernel at the steps that ban something and the rerank behind the backtrack when length_penalty > 0.  c == NULL or all fields
+ *   off: the launches of sat_beam_decode, bit-identical ids and scores.  norm_scores [B][K] and order [B][K] are nullable (without
+ *   a penalty: the scores and 0..K-1).  workspace: sat_beam_decode_ex_ws_bytes, 256-byte aligned.  With n-gram blocking the loop
+ *   keeps every slot's prefix in its workspace instead of walking the records at every step (same results; SAT_BEAM_HISTORY=0: walk).
+ * Errors, before anything is enqueued.  SAT_ERR_ARG: a NULL buffer, a negative field, block_repeat not 0 / 1, n_suppress > 256 or
+ *   > 0 with suppress_ids NULL, min_length > 0 with end_id < 0, a length_penalty that is negative or not finite, T < 1, i outside
+ *   [0, T), active constraints at i > 0 without records.  SAT_ERR_UNSUPPORTED: K > 8; with active step constraints T (steps) > 64
+ *   or V > 65536 (lane t of one wave keeps y_t; the ban bitmap is 8 KiB of LDS).  SAT_ERR_WORKSPACE as elsewhere. */
+typedef struct {
+    const int64_t* suppress_ids;   /* device, or NULL with n_suppress 0 */
+    int n_suppress;                /* 0..256 */
+    int min_length;                /* >= 0; > 0 needs end_id >= 0 */
+    int no_repeat_ngram;           /* 0 off, n >= 1 */
+    int block_repeat;              /* 0 / 1 */
+    float length_penalty;          /* finite, >= 0; 0 off; read by the rerank only */
+} sat_beam_constraints;
+int sat_beam_step_ex(const float* logits /*[B*K, ldl]*/, int64_t ldl, const float* scores_in /*[B*K]*/,
+                     const int64_t* last_tokens /*[B*K] or NULL*/, int64_t end_id, int B, int K, int V,
+                     const sat_beam_constraints* c /*[host], nullable*/, const int32_t* parents, const int64_t* tokens, int i, int T,
+                     int32_t* parent /*[B*K]*/, int64_t* token /*[B*K]*/, float* scores_out /*[B*K]*/,
+                     void* workspace, int64_t ws_bytes, sat_stream_t stream);
+int64_t sat_beam_step_ex_ws_bytes(int B, int K, int V, int T);
+int sat_beam_rerank(const int64_t* ids, const float* scores, int B, int K, int T, int64_t end_id, float length_penalty,
+                    int64_t* ids_out, float* scores_out, float* norm_out, int32_t* order_out, sat_stream_t stream);
+int64_t sat_beam_decode_ex_ws_bytes(int B, int K, int E, int H, int V, int num_layers, int steps);
+int sat_beam_decode_ex(const float* features /*[B,E]*/, const float* embed /*[V,E]*/, const float* const* lstm_w /*[host]*/, int num_layers,
+                       const float* lin_w /*[V,H]*/, const float* lin_b, int B, int K, int E, int H, int V, int steps, int64_t end_id,
+                       const sat_beam_constraints* c /*[host], nullable*/, int64_t* ids, float* scores, float* norm_scores,
+                       int32_t* order, void* workspace, int64_t ws_bytes, sat_stream_t stream);
 /* Scheduled sampling (the reference's DecoderRNN.ss_prob, models.py:38, and its schedule, train.py:109-113) in the training forward.
  * Random numbers: Philox4x32-10, key (seed & 0xffffffff, seed >> 32), u = ((x >> 8) + 0.5) * 2^-24.  The draw for row b of step t is
  * s(b, t) = first argmax_v (logit[b][v] + G(b, t, v)), G = -log(-log u) of counter (v >> 2, b, t, 2*rank), word v & 3 (Gumbel-max: an

@@ -49,6 +49,12 @@ class SatRefCorpus(C.Structure):
                 ("n_refs", C.c_int32), ("n_images", C.c_int32), ("max_ref_tokens", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SatBeamConstraints(C.Structure):
+    """mirror of `sat_beam_constraints` (include/sat_hip.h)"""
+    _fields_ = [("suppress_ids", _vp), ("n_suppress", C.c_int), ("min_length", C.c_int), ("no_repeat_ngram", C.c_int),
+                ("block_repeat", C.c_int), ("length_penalty", C.c_float)]
+
+
 class SatOp(C.Structure):
     """mirror of `struct sat_op` (include/sat_hip.h); no instance attributes besides the fields, so a misspelt field raises"""
     __slots__ = ()
@@ -175,6 +181,13 @@ SIGNATURES = {
     "sat_kept_tokens": (_i, [_vp, _i64, _i, _i, _i64, _vp, _vp]),
     "sat_beam_decode_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
     "sat_beam_decode": (_i, [_vp, _vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "sat_beam_step_ex": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _i, _i, C.POINTER(SatBeamConstraints), _vp, _vp, _i, _i, _vp, _vp, _vp, _vp,
+                              _i64, _vp]),
+    "sat_beam_step_ex_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "sat_beam_rerank": (_i, [_vp, _vp, _i, _i, _i, _i64, _f, _vp, _vp, _vp, _vp, _vp]),
+    "sat_beam_decode_ex_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
+    "sat_beam_decode_ex": (_i, [_vp, _vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, C.POINTER(SatBeamConstraints),
+                                _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sat_greedy_decode": (_i, [_vp, _vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "sat_ss_decoder_fwd_ws_bytes": (_i64, [_i, _i]),
     "sat_vocab_sample": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i64, _f, C.c_uint64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i, _vp,
@@ -221,7 +234,8 @@ ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_at
                     "sat_rollout_decoder_fwd_ws_bytes", "sat_rollout_decoder_fwd", "sat_scst_weights", "sat_ce_rows_weighted",
                     "sat_rollout_attend_fwd_ws_bytes", "sat_rollout_attend_fwd", "sat_bleu_comps", "sat_bleu_finalize",
                     "sat_rouge_l_score", "sat_sample_filtered_ws_bytes", "sat_sample_filtered", "sat_sample_decode_ws_bytes",
-                    "sat_sample_decode", "sat_dropout_f32")
+                    "sat_sample_decode", "sat_dropout_f32", "sat_beam_step_ex", "sat_beam_step_ex_ws_bytes", "sat_beam_rerank",
+                    "sat_beam_decode_ex_ws_bytes", "sat_beam_decode_ex")
 
 _lib = None
 

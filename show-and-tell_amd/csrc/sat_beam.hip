@@ -79,11 +79,34 @@ __device__ __forceinline__ void list_insert(float (&val)[KMAX], int (&idx)[KMAX]
 // 33 us per 320 rows).  Now: a thread keeps only its single best candidate; K rounds of block arg-best; the wave that owned the
 // winner strikes it out and finds its threads' next best -- the other waves skip that.  Exactly the same result: the K best
 // candidates of the row under (score desc, flat index asc).
-template <int NT>
-__global__ __launch_bounds__(NT) void beam_row_kernel(const float* __restrict__ logits, long ldl,
-                                                      const float* __restrict__ scores_in,
-                                                      const int64_t* __restrict__ last_tok, long end_id, int K, int V,
-                                                      float* __restrict__ cand_val, int* __restrict__ cand_idx) {
+//
+// CONSTRAINED (sat_beam_step_ex, include/sat_hip.h): the row's banned columns are struck from the candidates AFTER the log-sum-exp
+// over the whole row (scores are not renormalised).  The bans live in an LDS bitmap of V bits: every thread clears its words, one
+// barrier, then wave 0 alone gathers them -- the suppressed ids, end_id in front of min_length, and the row's own prefix, which it
+// recovers by walking the (parents, tokens) records from step i - 1 down (every lane walks the same chain, the loads are wave
+// broadcasts, both loads of a level in flight together; lane t keeps y_t in a register and the n-gram compare reads its neighbours
+// by ds_bpermute).  sat_beam_decode_ex, which owns a workspace, spares the walk under n-gram blocking: it keeps every slot's prefix
+// in two [B*K][64] planes, and a row reads ONE level of the chain plus its parent's prefix row and writes its own (BeamBan::hist_*).
+// The other waves meanwhile have their row loads in flight and wait in the first block reduction, whose barriers also publish the
+// bitmap.  A thread then tests ONE bitmap word per 16-byte chunk it holds: chunk q is bits 4q..4q+3 = a nibble of
+// word q >> 3, so 8 neighbouring lanes read one word (a broadcast) and a wave reads 8 consecutive words: no bank conflict.  The row
+// in registers is only ever indexed by unrolled constants.  Finished and dead rows leave before any of this.
+struct BeamBan {
+    const int64_t* suppress;     // device [n_suppress]
+    const int32_t* parents;      // records [T][B*K], rows < i valid
+    const int64_t* tokens;
+    int n_suppress, min_length, ngram, block_repeat, i;
+    const int* hist_in;          // sat_beam_decode_ex only: [B*K][kBanTMax], slot s's prefix as it stood BEFORE step i - 1's selection
+    int* hist_out;               //   ... and the prefixes of this step's rows (NULL: the prefix is walked from the records)
+};
+constexpr int kBanTMax = 64;     // steps a constrained decode may have (lane t of the walking wave keeps y_t)
+constexpr int kBanVMax = 65536;  // columns of the LDS ban bitmap (8 KiB)
+
+template <int NT, bool CONSTRAINED>
+__device__ __forceinline__ void beam_row_body(const float* __restrict__ logits, long ldl, const float* __restrict__ scores_in,
+                                              const int64_t* __restrict__ last_tok, long end_id, int K, int V,
+                                              float* __restrict__ cand_val, int* __restrict__ cand_idx, const BeamBan& ban,
+                                              unsigned* s_ban) {
     constexpr int NW = NT / 64, RCN = RC * 256 / NT;          // waves; 16-byte chunks of the row a thread keeps in registers
     __shared__ float sh[NW];
     __shared__ float s_rv[NW];
@@ -107,6 +130,53 @@ __global__ __launch_bounds__(NT) void beam_row_kernel(const float* __restrict__ 
     }
     const float* x = logits + (long)row * ldl;
     const int nq = V >> 2;                                   // whole 16-byte chunks (rows are 16-byte aligned: ldl % 4 == 0)
+    if constexpr (CONSTRAINED) {
+        for (int w = tid; w < (V + 31) >> 5; w += NT) s_ban[w] = 0u;
+        __syncthreads();
+        if (tid < 64) {                                      // wave 0 gathers the bans; the first block reduction publishes them
+            auto set = [&](long v) {
+                if (v >= 0 && v < V) atomicOr(&s_ban[v >> 5], 1u << (v & 31));
+            };
+            for (int j = tid; j < ban.n_suppress; j += 64) set((long)ban.suppress[j]);
+            if (tid == 0 && ban.i < ban.min_length) set(end_id);
+            const int i = ban.i, n = ban.ngram;
+            const bool grams = n >= 1 && i >= n;
+            const int depth = (grams || (ban.hist_out && i >= 1)) ? i : (ban.block_repeat && i >= 1 ? 1 : 0);
+            if (depth > 0) {
+                const long BK = gridDim.x, at0 = row - k;    // (b * K)
+                int cur = k, y = -1;                         // y: y_t in lane t
+                if (ban.hist_out) {
+                    // the decode loop keeps every slot's prefix: ONE level of the chain (this row's parent and last token), then the
+                    // parent's prefix as one coalesced row -- instead of i dependent levels
+                    const long at = (long)(i - 1) * BK + row;
+                    const int64_t tk = ban.tokens[at];
+                    const int pr = ban.parents[at];
+                    cur = pr < 0 ? 0 : (pr >= K ? K - 1 : pr);
+                    if (tid < i - 1) y = ban.hist_in[(at0 + cur) * kBanTMax + tid];
+                    if (tid == i - 1) y = (tk >= 0 && tk < V) ? (int)tk : -1;
+                    if (tid < i) ban.hist_out[(long)row * kBanTMax + tid] = y;
+                }
+                for (int t = i - 1; t >= i - depth && !ban.hist_out; --t) {
+                    const long at = (long)t * BK + at0 + cur;
+                    const int64_t tk = ban.tokens[at];
+                    const int pr = ban.parents[at];
+                    if (tid == t) y = (tk >= 0 && tk < V) ? (int)tk : -1;
+                    cur = pr < 0 ? 0 : (pr >= K ? K - 1 : pr);                  // memory safety only: the steps write 0..K-1
+                }
+                if (ban.block_repeat && tid == i - 1) set(y);
+                if (grams) {
+                    // lane j: the n-gram that starts at j, 0 <= j <= i - n, bans its last token when its first n - 1 equal the tail
+                    bool same = true;
+                    for (int m = 0; m + 1 < n; ++m) {        // (both reads by the whole wave: no short-circuit around a bpermute)
+                        const int mine = __shfl(y, (tid + m) & 63, 64), tail = __shfl(y, i - n + 1 + m, 64);
+                        same = same & (mine == tail);
+                    }
+                    const int lastv = __shfl(y, (tid + n - 1) & 63, 64);
+                    if (tid <= i - n && same) set(lastv);
+                }
+            }
+        }
+    }
     // (V < 4 has no whole chunk to clamp the out-of-row chunk indexes to -- nq - 1 would be the 16 bytes IN FRONT of the row: such
     // rows take the long-row path below)
     if ((ldl & 3) == 0 && nq >= 1 && nq <= RCN * NT) {
@@ -146,6 +216,16 @@ __global__ __launch_bounds__(NT) void beam_row_kernel(const float* __restrict__ 
 #pragma unroll
             for (int e = 0; e < 4; ++e) rc[c][e] = base + (rc[c][e] - lse);
         xt = base + (xt - lse);
+        if constexpr (CONSTRAINED) {                         // banned columns are no candidates (one bitmap word per chunk)
+#pragma unroll
+            for (int c = 0; c < RCN; ++c) {
+                const int q = tid + c * NT;
+                const unsigned nib = s_ban[q < nq ? q >> 3 : 0] >> (4 * (q & 7));
+#pragma unroll
+                for (int e = 0; e < 4; ++e) rc[c][e] = ((nib >> e) & 1u) ? -INFINITY : rc[c][e];
+            }
+            if (tail < V && ((s_ban[tail >> 5] >> (tail & 31)) & 1u)) xt = -INFINITY;
+        }
         // this thread's best TWO (elements in increasing index order: strict > keeps the lower index among equals in front)
         float v1 = -INFINITY, v2 = -INFINITY;
         int i1 = INT_MAX, i2 = INT_MAX;
@@ -235,6 +315,9 @@ __global__ __launch_bounds__(NT) void beam_row_kernel(const float* __restrict__ 
         s = block_reduce<NT>(s, false, sh);
         const float lse = m + logf(s);
         for (int i = tid; i < V; i += NT) {
+            if constexpr (CONSTRAINED) {
+                if ((s_ban[i >> 5] >> (i & 31)) & 1u) continue;
+            }
             const float cv = base + (x[i] - lse);
             if (cv > val[KMAX - 1]) list_insert(val, idx, cv, k * V + i);
         }
@@ -280,6 +363,23 @@ __global__ __launch_bounds__(NT) void beam_row_kernel(const float* __restrict__ 
             ci_out[r] = bi;
         }
     }
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void beam_row_kernel(const float* __restrict__ logits, long ldl,
+                                                      const float* __restrict__ scores_in,
+                                                      const int64_t* __restrict__ last_tok, long end_id, int K, int V,
+                                                      float* __restrict__ cand_val, int* __restrict__ cand_idx) {
+    beam_row_body<NT, false>(logits, ldl, scores_in, last_tok, end_id, K, V, cand_val, cand_idx, BeamBan{}, nullptr);
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void beam_row_ban_kernel(const float* __restrict__ logits, long ldl,
+                                                          const float* __restrict__ scores_in,
+                                                          const int64_t* __restrict__ last_tok, long end_id, int K, int V,
+                                                          float* __restrict__ cand_val, int* __restrict__ cand_idx, BeamBan ban) {
+    __shared__ unsigned s_ban[kBanVMax / 32];
+    beam_row_body<NT, true>(logits, ldl, scores_in, last_tok, end_id, K, V, cand_val, cand_idx, ban, s_ban);
 }
 
 // One workgroup of 256 threads per image: wave 0 merges (K rounds of a wave-wide arg-best over the image's K * K row candidates), then
@@ -452,6 +552,96 @@ __global__ __launch_bounds__(256) void kept_tokens_kernel(const int64_t* __restr
     kept[b] = n;
 }
 
+// Length-penalty re-ranking of a finished beam (sat_beam_rerank): one wave per image, lane k < K owns hypothesis k.  L_k as
+// kept_tokens_kernel counts it, plus 1 for the <end> (T without one); norm in f64, rounded once; rank = how many hypotheses come in
+// front under (norm desc, previous rank asc) -- a stable sort of K <= 8 keys by counting; then the wave copies the K id rows.
+__global__ __launch_bounds__(64) void beam_rerank_kernel(const int64_t* __restrict__ ids, const float* __restrict__ scores, int K, int T,
+                                                         int64_t end_id, float alpha, int64_t* __restrict__ ids_out,
+                                                         float* __restrict__ scores_out, float* __restrict__ norm_out,
+                                                         int32_t* __restrict__ order_out) {
+    __shared__ int s_order[KMAX];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    float sc = -INFINITY, norm = -INFINITY;
+    if (lane < K) {
+        const int64_t* row = ids + ((long)b * K + lane) * T;
+        int n = 0;
+        while (n < T && row[n] != end_id) ++n;
+        const int len = n < T ? n + 1 : T;
+        sc = scores[(long)b * K + lane];
+        norm = alpha > 0.0f ? (float)((double)sc / pow((double)len, (double)alpha)) : sc;
+    }
+    if (lane < K) s_order[lane] = lane;                      // (NaN scores can leave a rank unclaimed: memory safety only)
+    __syncthreads();
+    int rank = 0;
+    for (int j = 0; j < K; ++j) {
+        const float nj = __shfl(norm, j, 64);
+        rank += (nj > norm || (nj == norm && j < lane)) ? 1 : 0;
+    }
+    if (lane < K) {
+        rank = rank < K ? rank : K - 1;                      // (NaN scores: memory safety only)
+        s_order[rank] = lane;
+        const long at = (long)b * K + rank;
+        scores_out[at] = sc;
+        if (norm_out) norm_out[at] = norm;
+        if (order_out) order_out[at] = lane;
+    }
+    __syncthreads();
+    for (int r = 0; r < K; ++r) {
+        const int64_t* src = ids + ((long)b * K + s_order[r]) * T;
+        int64_t* dst = ids_out + ((long)b * K + r) * T;
+        for (int t = lane; t < T; t += 64) dst[t] = src[t];
+    }
+}
+
+// order[b, k] = k
+__global__ __launch_bounds__(256) void beam_iota_kernel(int32_t* __restrict__ order, int R, int K) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < R) order[t] = t % K;
+}
+
+// the checks every constrained entry point makes before anything is enqueued; *active: a step constraint is on
+int beam_constraints_check(const sat_beam_constraints* c, int64_t end_id, bool* active) {
+    *active = false;
+    if (!c) return SAT_OK;
+    if (c->n_suppress < 0 || c->min_length < 0 || c->no_repeat_ngram < 0 || (c->block_repeat != 0 && c->block_repeat != 1))
+        return SAT_ERR_ARG;
+    if (c->n_suppress > 256 || (c->n_suppress > 0 && !c->suppress_ids)) return SAT_ERR_ARG;
+    if (c->min_length > 0 && end_id < 0) return SAT_ERR_ARG;
+    if (!(c->length_penalty >= 0.0f) || c->length_penalty == INFINITY) return SAT_ERR_ARG;
+    *active = c->n_suppress > 0 || c->min_length > 0 || c->no_repeat_ngram > 0 || c->block_repeat != 0;
+    return SAT_OK;
+}
+
+// does step i of a decode under c ban anything?  (a step that does not runs the plain row kernel: the same bits)
+bool beam_step_bans(const sat_beam_constraints* c, int i) {
+    return c->n_suppress > 0 || i < c->min_length || (c->no_repeat_ngram >= 1 && i >= c->no_repeat_ngram) || (c->block_repeat && i >= 1);
+}
+
+// the row launch of one step: the constrained kernel where the step bans something, the plain one otherwise
+void beam_row_launch(hipStream_t s, const float* logits, long ldl, const float* scores_in, const int64_t* last, long end_id, int R, int K,
+                     int V, float* cand_val, int* cand_idx, const sat_beam_constraints* c, const int32_t* parents, const int64_t* tokens,
+                     int i, int* hist = nullptr) {
+    // (hist: two [R][kBanTMax] planes; with n-gram blocking the constrained kernel then runs from step 1 on, to keep them)
+    if (c && (beam_step_bans(c, i) || (hist && i >= 1))) {
+        BeamBan ban;
+        ban.suppress = c->suppress_ids;
+        ban.parents = parents;
+        ban.tokens = tokens;
+        ban.n_suppress = c->n_suppress;
+        ban.min_length = c->min_length;
+        ban.ngram = c->no_repeat_ngram;
+        ban.block_repeat = c->block_repeat;
+        ban.i = i;
+        ban.hist_in = hist ? hist + (long)((i + 1) & 1) * R * kBanTMax : nullptr;
+        ban.hist_out = hist ? hist + (long)(i & 1) * R * kBanTMax : nullptr;
+        hipLaunchKernelGGL(beam_row_ban_kernel<256>, dim3((unsigned)R), dim3(256), 0, s, logits, ldl, scores_in, last, end_id, K, V, cand_val,
+                           cand_idx, ban);
+    } else {
+        hipLaunchKernelGGL(beam_row_kernel<256>, dim3((unsigned)R), dim3(256), 0, s, logits, ldl, scores_in, last, end_id, K, V, cand_val,
+                           cand_idx);
+    }
+}
+
 }  // namespace
 
 extern "C" int sat_kept_tokens(const int64_t* ids, int64_t stride, int B, int T, int64_t end_id, int32_t* kept,
@@ -485,6 +675,48 @@ extern "C" int sat_beam_step(const float* logits, int64_t ldl, const float* scor
     return SAT_OK;
 }
 
+extern "C" int64_t sat_beam_step_ex_ws_bytes(int B, int K, int V, int T) {
+    if (B <= 0 || K <= 0 || V <= 0 || T <= 0) return 0;
+    return sat_beam_step_ws_bytes(B, K);                       // the prefix is walked from the records: no state in the workspace
+}
+
+extern "C" int sat_beam_step_ex(const float* logits, int64_t ldl, const float* scores_in, const int64_t* last_tokens,
+                                int64_t end_id, int B, int K, int V, const sat_beam_constraints* c, const int32_t* parents,
+                                const int64_t* tokens, int i, int T, int32_t* parent, int64_t* token, float* scores_out,
+                                void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    if (!logits || !scores_in || !parent || !token || !scores_out || !workspace) return SAT_ERR_ARG;
+    if (B <= 0 || K <= 0 || V <= 0 || ldl < V || T <= 0 || i < 0 || i >= T) return SAT_ERR_ARG;
+    bool active = false;
+    SAT_TRY(beam_constraints_check(c, end_id, &active));
+    if (active && i > 0 && (!parents || !tokens)) return SAT_ERR_ARG;
+    if (K > KMAX || (long)K * V > INT_MAX - 1) return SAT_ERR_UNSUPPORTED;
+    if (active && (T > kBanTMax || V > kBanVMax)) return SAT_ERR_UNSUPPORTED;
+    if (ws_bytes < sat_beam_step_ex_ws_bytes(B, K, V, T)) return SAT_ERR_WORKSPACE;
+    float* cand_val = (float*)workspace;                       // [B*K rows][K]
+    int* cand_idx = (int*)(cand_val + (long)B * K * K);
+    hipStream_t s = (hipStream_t)stream;
+    beam_row_launch(s, logits, (long)ldl, scores_in, last_tokens, (long)end_id, B * K, K, V, cand_val, cand_idx, active ? c : nullptr,
+                    parents, tokens, i);
+    SAT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, s, cand_val, cand_idx, K, V, parent, token, scores_out,
+                       (const float*)nullptr, 0, (float*)nullptr, 0L, (const float*)nullptr, (const float*)nullptr, 0, (float*)nullptr, 0L,
+                       (float*)nullptr);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
+extern "C" int sat_beam_rerank(const int64_t* ids, const float* scores, int B, int K, int T, int64_t end_id, float length_penalty,
+                               int64_t* ids_out, float* scores_out, float* norm_out, int32_t* order_out, sat_stream_t stream) {
+    if (!ids || !scores || !ids_out || !scores_out || ids == ids_out || scores == scores_out) return SAT_ERR_ARG;
+    if (B <= 0 || K <= 0 || T <= 0) return SAT_ERR_ARG;
+    if (!(length_penalty >= 0.0f) || length_penalty == INFINITY) return SAT_ERR_ARG;
+    if (K > KMAX) return SAT_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(beam_rerank_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, ids, scores, K, T, end_id, length_penalty, ids_out,
+                       scores_out, norm_out, order_out);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
 // ---- the whole beam decode of one batch as ONE call (eval.py:99's `model.sample` loop, models.py:56-67, widened to a beam; the
 //      reference's own sample_beam is a stub, model2.py:113-114).  Round 4 drove the 20 steps from Python: seven launches per step
 //      through ctypes, 2.44 ms per 20 steps of which the GPU was busy ~1.3 ms -- the loop was host-bound.  Here the host enqueues
@@ -504,14 +736,32 @@ extern "C" int64_t sat_beam_decode_ws_bytes(int B, int K, int E, int H, int V, i
            2 * al256(R * (int64_t)(E + H) * 4) + al256(4 * (int64_t)H * (E + H) * 4) + al256(kBeamKSplitMax * R * 4 * (int64_t)H * 4);
 }
 
-extern "C" int sat_beam_decode(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
-                               const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
-                               int64_t end_id, int64_t* ids, float* scores_out, void* workspace, int64_t ws_bytes,
-                               sat_stream_t stream) {
+// what sat_beam_decode_ex adds to the workspace: the ids in search order (the rerank writes the caller's), scores, norm, order,
+// and the two planes of the per-slot prefix history
+static int64_t beam_decode_ex_extra(int64_t R, int steps) { return al256(R * steps * 8) + 3 * al256(R * 4) + al256(2 * R * kBanTMax * 4); }
+
+extern "C" int64_t sat_beam_decode_ex_ws_bytes(int B, int K, int E, int H, int V, int num_layers, int steps) {
+    const int64_t base = sat_beam_decode_ws_bytes(B, K, E, H, V, num_layers, steps);
+    return base <= 0 ? 0 : base + beam_decode_ex_extra((int64_t)B * K, steps);
+}
+
+// ONE loop for sat_beam_decode (ex false, c NULL) and sat_beam_decode_ex: with constraints the row launch of a step that bans
+// something is the constrained kernel, and with a length penalty the rerank runs behind the backtrack; nothing else differs
+static int beam_decode_impl(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
+                            const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
+                            int64_t end_id, bool ex, const sat_beam_constraints* c, int64_t* ids, float* scores_out, float* norm_scores,
+                            int32_t* order, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
     if (!features || !embed || !lstm_w || !lin_w || !lin_b || !ids || !workspace) return SAT_ERR_ARG;
-    const int64_t need = sat_beam_decode_ws_bytes(B, K, E, H, V, num_layers, steps);
+    const int64_t need = ex ? sat_beam_decode_ex_ws_bytes(B, K, E, H, V, num_layers, steps)
+                            : sat_beam_decode_ws_bytes(B, K, E, H, V, num_layers, steps);
     if (need <= 0) return SAT_ERR_ARG;
+    bool active = false;
+    SAT_TRY(beam_constraints_check(c, end_id, &active));
     if ((E & 3) || (long)K * V > INT_MAX - 1) return SAT_ERR_UNSUPPORTED;
+    if (active && (steps > kBanTMax || V > kBanVMax)) return SAT_ERR_UNSUPPORTED;
+    const bool rerank = c && c->length_penalty > 0.0f;
+    const float c_length_penalty = c ? c->length_penalty : 0.0f;
+    if (!active) c = nullptr;
     if (ws_bytes < need || (((uintptr_t)workspace) & 255)) return SAT_ERR_WORKSPACE;
     for (int i = 0; i < 4 * num_layers; ++i)
         if (!lstm_w[i]) return SAT_ERR_ARG;
@@ -534,6 +784,19 @@ extern "C" int sat_beam_decode(const float* features, const float* embed, const 
     xh[1] = (float*)w; w += al256(R * (int64_t)(E + H) * 4);
     float* wcat = (float*)w; w += al256(4 * (int64_t)H * (E + H) * 4);
     float* gates = (float*)w; w += al256(kBeamKSplitMax * R * 4 * (int64_t)H * 4);
+    int64_t* ids_search = nullptr;
+    float *sc_ranked = nullptr, *norm_tmp = nullptr;
+    int32_t* order_tmp = nullptr;
+    int* hist = nullptr;
+    if (ex) {
+        ids_search = (int64_t*)w; w += al256(R * steps * 8);
+        sc_ranked = (float*)w; w += al256(R * 4);
+        norm_tmp = (float*)w; w += al256(R * 4);
+        order_tmp = (int32_t*)w; w += al256(R * 4);
+        hist = (int*)w; w += al256(2 * R * kBanTMax * 4);
+    }
+    static const bool hist_env = [] { const char* v = getenv("SAT_BEAM_HISTORY"); return !(v && v[0] == '0'); }();
+    if (!(c && c->no_repeat_ngram >= 1 && hist_env)) hist = nullptr;      // only n-gram blocking reads the whole prefix
     void* lin_split = w;                                       // [V128][H] x 3 bf16, fragment ordered (sat_gemm_f32x3_pack)
     hipError_t e = hipMemsetAsync(hc, 0, (size_t)(4 * (int64_t)num_layers * R * H * 4), s);      // h = c = 0
     if (e != hipSuccess) return (int)e;
@@ -622,8 +885,7 @@ extern "C" int sat_beam_decode(const float* features, const float* embed, const 
         int32_t* par = parents + (long)i * R;
         int64_t* tok = tokens + (long)i * R;
         const int64_t* last = (i > 0 && end_id >= 0) ? tok - R : (const int64_t*)nullptr;
-        hipLaunchKernelGGL(beam_row_kernel<256>, dim3((unsigned)R), dim3(256), 0, s, logits, (long)ldl, sc[si], last, (long)end_id, K, V,
-                           cand_val, cand_idx);
+        beam_row_launch(s, logits, (long)ldl, sc[si], last, (long)end_id, (int)R, K, V, cand_val, cand_idx, c, parents, tokens, i, hist);
         SAT_LAUNCH_CHECK();
         if (wide) {
             // ... the merge wave also moves (h, c) by parent: h straight into the next input row's h half (one launch fewer per step)
@@ -657,13 +919,45 @@ extern "C" int sat_beam_decode(const float* features, const float* embed, const 
         }
         x = xe;
     }
-    hipLaunchKernelGGL(beam_backtrack_kernel, dim3(sat_cdiv(R, 256)), dim3(256), 0, s, parents, tokens, steps, (int)R, K, ids);
+    hipLaunchKernelGGL(beam_backtrack_kernel, dim3(sat_cdiv(R, 256)), dim3(256), 0, s, parents, tokens, steps, (int)R, K,
+                       rerank ? ids_search : ids);
     SAT_LAUNCH_CHECK();
+    if (rerank) {                                              // (ex) the K hypotheses of an image re-ordered by score / L^alpha
+        hipLaunchKernelGGL(beam_rerank_kernel, dim3(B), dim3(64), 0, s, (const int64_t*)ids_search, (const float*)sc[si], K, steps, end_id,
+                           c_length_penalty, ids, scores_out ? scores_out : sc_ranked, norm_scores ? norm_scores : norm_tmp,
+                           order ? order : order_tmp);
+        SAT_LAUNCH_CHECK();
+        return SAT_OK;
+    }
     if (scores_out) {
         e = hipMemcpyAsync(scores_out, sc[si], (size_t)(R * 4), hipMemcpyDeviceToDevice, s);
         if (e != hipSuccess) return (int)e;
     }
+    if (norm_scores) {                                         // no penalty: the norm is the score, the order the identity
+        e = hipMemcpyAsync(norm_scores, sc[si], (size_t)(R * 4), hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return (int)e;
+    }
+    if (order) {
+        hipLaunchKernelGGL(beam_iota_kernel, dim3(sat_cdiv(R, 256)), dim3(256), 0, s, order, (int)R, K);
+        SAT_LAUNCH_CHECK();
+    }
     return SAT_OK;
+}
+
+extern "C" int sat_beam_decode(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
+                               const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
+                               int64_t end_id, int64_t* ids, float* scores_out, void* workspace, int64_t ws_bytes,
+                               sat_stream_t stream) {
+    return beam_decode_impl(features, embed, lstm_w, num_layers, lin_w, lin_b, B, K, E, H, V, steps, end_id, false, nullptr, ids,
+                            scores_out, nullptr, nullptr, workspace, ws_bytes, stream);
+}
+
+extern "C" int sat_beam_decode_ex(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
+                                  const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
+                                  int64_t end_id, const sat_beam_constraints* c, int64_t* ids, float* scores_out, float* norm_scores,
+                                  int32_t* order, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    return beam_decode_impl(features, embed, lstm_w, num_layers, lin_w, lin_b, B, K, E, H, V, steps, end_id, true, c, ids, scores_out,
+                            norm_scores, order, workspace, ws_bytes, stream);
 }
 
 extern "C" int sat_beam_gather_rows(const float* src, const int32_t* parent, int B, int K, int width, float* dst,

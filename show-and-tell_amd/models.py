@@ -471,6 +471,79 @@ def check_sample_args(temperature, top_k, top_p, num_samples, seed):
     return tau, top_k, p, num_samples, seed
 
 
+class BeamConstraints:
+    """The checked constraints of one `sample_beam` call (`check_beam_constraints`).  `active`: something differs from the defaults,
+    so the `_ex` entry points run; `struct(device)` is the `sat_beam_constraints` the library reads -- this object keeps the
+    `suppress_ids` device tensor it points to alive."""
+
+    def __init__(self, suppress_ids, min_length, no_repeat_ngram_size, block_repeat, length_penalty):
+        self.suppress_ids, self.min_length, self.no_repeat_ngram_size = suppress_ids, min_length, no_repeat_ngram_size
+        self.block_repeat, self.length_penalty = block_repeat, length_penalty
+        self.active = bool(suppress_ids or min_length or no_repeat_ngram_size or block_repeat or length_penalty > 0)
+        self._tensor = self._struct = None
+
+    def struct(self, device):
+        if self._struct is None or self._tensor is not None and self._tensor.device != torch.device(device):
+            self._tensor = torch.tensor(self.suppress_ids, dtype=torch.int64, device=device) if self.suppress_ids else None
+            self._struct = L.SatBeamConstraints(self._tensor.data_ptr() if self.suppress_ids else None, len(self.suppress_ids),
+                                                self.min_length, self.no_repeat_ngram_size, int(self.block_repeat), self.length_penalty)
+        return self._struct
+
+
+BEAM_MAX_SUPPRESS, BEAM_MAX_STEPS, BEAM_MAX_VOCAB = 256, 64, 65536         # include/sat_hip.h, sat_beam_step_ex
+_NO_CONSTRAINTS = BeamConstraints([], 0, 0, False, 0.0)
+
+
+def check_beam_constraints(suppress_ids=None, min_length=0, no_repeat_ngram_size=0, block_repeat=False, length_penalty=0.0,
+                           end_id=None, vocab_size=None, steps=None):
+    """The constraint arguments of the `sample_beam` methods as a `BeamConstraints`; a ValueError names the bad one -- everything
+    the library refuses, and an `end_id` among `suppress_ids` (no hypothesis could ever finish).  Host arithmetic only: runs
+    before the library is loaded."""
+    import math
+    if suppress_ids is None and block_repeat is False and type(min_length) is int and type(no_repeat_ngram_size) is int and \
+            type(length_penalty) in (int, float) and min_length == 0 and no_repeat_ngram_size == 0 and length_penalty == 0 and \
+            (end_id is None or type(end_id) is int):
+        return _NO_CONSTRAINTS                              # the defaults: nothing to check, nothing to build
+
+    def is_int(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+
+    if suppress_ids is None:
+        ids = []
+    else:
+        try:
+            ids = suppress_ids.tolist() if hasattr(suppress_ids, "tolist") else list(suppress_ids)
+        except TypeError:
+            raise ValueError("suppress_ids must be None or a sequence of token ids, got %r" % (suppress_ids,))
+    if any(not is_int(v) or v < 0 or (vocab_size is not None and v >= vocab_size) for v in ids):
+        raise ValueError("suppress_ids must be ints in [0, vocab_size), got %r" % (ids,))
+    if len(ids) > BEAM_MAX_SUPPRESS:
+        raise ValueError("at most %d suppress_ids, got %d" % (BEAM_MAX_SUPPRESS, len(ids)))
+    if end_id is not None and not is_int(end_id):
+        raise ValueError("end_id must be None or an int, got %r" % (end_id,))
+    eid = -1 if end_id is None else end_id
+    if eid >= 0 and eid in ids:
+        raise ValueError("end_id %d is among suppress_ids: no hypothesis could finish" % eid)
+    if not is_int(min_length) or min_length < 0:
+        raise ValueError("min_length must be an int >= 0, got %r" % (min_length,))
+    if min_length > 0 and eid < 0:
+        raise ValueError("min_length > 0 needs an end_id >= 0 (the token it holds back)")
+    if not is_int(no_repeat_ngram_size) or no_repeat_ngram_size < 0:
+        raise ValueError("no_repeat_ngram_size must be an int >= 0 (0: off), got %r" % (no_repeat_ngram_size,))
+    if not isinstance(block_repeat, (bool, int)) or block_repeat not in (0, 1):
+        raise ValueError("block_repeat must be a bool, got %r" % (block_repeat,))
+    alpha = _as_f32(length_penalty)
+    if isinstance(length_penalty, bool) or alpha is None or not math.isfinite(alpha) or alpha < 0:
+        raise ValueError("length_penalty must be a finite number >= 0 (as float32; 0: off), got %r" % (length_penalty,))
+    c = BeamConstraints(ids, min_length, no_repeat_ngram_size, bool(block_repeat), alpha)
+    if ids or min_length or no_repeat_ngram_size or block_repeat:
+        if steps is not None and steps > BEAM_MAX_STEPS:
+            raise ValueError("a constrained beam search runs at most %d steps, got %d" % (BEAM_MAX_STEPS, steps))
+        if vocab_size is not None and vocab_size > BEAM_MAX_VOCAB:
+            raise ValueError("a constrained beam search serves a vocabulary of at most %d, got %d" % (BEAM_MAX_VOCAB, vocab_size))
+    return c
+
+
 def stochastic_result(ids, logprobs, logits, alphas=None):
     """What a `sample_stochastic` returns: ids, then -- in this order, each only where asked for (not None) -- the dict(logp, kept),
     the logits and the attention maps; one value alone, else a tuple"""
@@ -541,6 +614,8 @@ class _RolloutFn(torch.autograd.Function):
 
 class DecoderRNN(nn.Module):
     """models.py:31-67."""
+
+    last_beam_norm_scores = last_beam_order = None     # set by a constrained `sample_beam` (None after a plain one)
 
     def __init__(self, embed_size, hidden_size, vocab_size, num_layers):
         super().__init__()
@@ -744,11 +819,20 @@ class DecoderRNN(nn.Module):
         return out[0], out[1]
 
     @torch.no_grad()
-    def sample_beam(self, features, beam_size=5, end_id=None, steps=20, return_all=False):
+    def sample_beam(self, features, beam_size=5, end_id=None, steps=20, return_all=False, *, suppress_ids=None, min_length=0,
+                    no_repeat_ngram_size=0, block_repeat=False, length_penalty=0.0):
         """Beam search over the same 20-step loop (`model2.py:113-114` is a stub in the reference).
         Returns the best hypothesis per image, i64 [B,steps]; with return_all also (ids [B,K,steps] best-first,
         scores [B,K] = sum of token log-probabilities).  beam_size=1, end_id=None is exactly `sample`.
-        end_id (eval.py's `<end>`, id 2): a finished hypothesis only repeats end_id at no cost."""
+        end_id (eval.py's `<end>`, id 2): a finished hypothesis only repeats end_id at no cost.
+        Constraints (include/sat_hip.h, sat_beam_step_ex; all off by default, and then the call is the one it always was):
+        suppress_ids are never emitted; end_id not in front of position min_length; no_repeat_ngram_size=n: no n-gram twice;
+        block_repeat: no token twice in a row; length_penalty=alpha re-orders the K results by score / length^alpha once the
+        search is over.  Scores are never renormalised: `scores` stays the raw sums, in the returned order; the normalised ones
+        are kept as `last_beam_norm_scores` [B,K] and the permutation as `last_beam_order` [B,K] (the search rank of the hypothesis
+        now at r) -- both None after an unconstrained call.  beam_size=1 with constraints is the constrained greedy decode."""
+        cons = check_beam_constraints(suppress_ids, min_length, no_repeat_ngram_size, block_repeat, length_penalty, end_id,
+                                      self.vocab_size, steps)
         lib = L.load()
         features = _f32c(features, "features")
         dev = features.device
@@ -758,15 +842,27 @@ class DecoderRNN(nn.Module):
         H, V, E = self.hidden_size, self.vocab_size, self.embed_size
         st = L.stream()
         eid = -1 if end_id is None else int(end_id)
-        wsb = lib.sat_beam_decode_ws_bytes(B, K, E, H, V, self.num_layers, steps)
-        ws, ws_ptr = L.workspace256(wsb, dev)
         ids = torch.empty(B, K, steps, dtype=torch.int64, device=dev)
         scores = torch.empty(B, K, device=dev)
+        if self.last_beam_order is not None:
+            self.last_beam_norm_scores = self.last_beam_order = None
         # every step (LSTM step, exact-f32 vocab projection, per-row log-softmax + top-K, per-image merge that also gathers the next
         # input's embedding rows, one (h, c) re-ordering launch) is enqueued by ONE library call (sat_beam_decode)
-        L.check(lib.sat_beam_decode(L.ptr(features), L.ptr(self.embed.weight), self._lstm_ptrs(), self.num_layers,
-                                    L.ptr(self.linear.weight), L.ptr(self.linear.bias), B, K, E, H, V, int(steps), eid,
-                                    ids.data_ptr(), L.ptr(scores), ws_ptr, wsb, st), "sat_beam_decode")
+        if cons.active:
+            wsb = lib.sat_beam_decode_ex_ws_bytes(B, K, E, H, V, self.num_layers, steps)
+            ws, ws_ptr = L.workspace256(wsb, dev)
+            norm, order = torch.empty(B, K, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev)
+            L.check(lib.sat_beam_decode_ex(L.ptr(features), L.ptr(self.embed.weight), self._lstm_ptrs(), self.num_layers,
+                                           L.ptr(self.linear.weight), L.ptr(self.linear.bias), B, K, E, H, V, int(steps), eid,
+                                           cons.struct(dev), ids.data_ptr(), L.ptr(scores), L.ptr(norm), L.ptr(order), ws_ptr, wsb, st),
+                    "sat_beam_decode_ex")
+            self.last_beam_norm_scores, self.last_beam_order = norm, order
+        else:
+            wsb = lib.sat_beam_decode_ws_bytes(B, K, E, H, V, self.num_layers, steps)
+            ws, ws_ptr = L.workspace256(wsb, dev)
+            L.check(lib.sat_beam_decode(L.ptr(features), L.ptr(self.embed.weight), self._lstm_ptrs(), self.num_layers,
+                                        L.ptr(self.linear.weight), L.ptr(self.linear.bias), B, K, E, H, V, int(steps), eid,
+                                        ids.data_ptr(), L.ptr(scores), ws_ptr, wsb, st), "sat_beam_decode")
         if return_all:
             return ids, scores
         return ids[:, 0].contiguous()
@@ -776,6 +872,8 @@ class ShowAndTell(nn.Module):
     """Encoder + decoder behind the reference trainer's single-module call contract (train.py:37,139;
     eval.py:93,99): `model(images, captions, lengths)` and `model.sample(images, state)`.
     state_dict keys: `encoder.*`, `decoder.*`."""
+
+    last_beam_norm_scores = last_beam_order = None     # set by a constrained `sample_beam` (None after a plain one)
 
     def __init__(self, embed_size, hidden_size, vocab_size, num_layers=1, arch=RESNET152, compute_dtype="bf16"):
         super().__init__()
@@ -818,8 +916,17 @@ class ShowAndTell(nn.Module):
         return self.decoder.sample(self.encoder(images), state)
 
     @torch.no_grad()
-    def sample_beam(self, images, beam_size=5, end_id=None, return_all=False):
-        return self.decoder.sample_beam(self.encoder(images), beam_size, end_id, return_all=return_all)
+    def sample_beam(self, images, beam_size=5, end_id=None, return_all=False, *, suppress_ids=None, min_length=0,
+                    no_repeat_ngram_size=0, block_repeat=False, length_penalty=0.0):
+        """`DecoderRNN.sample_beam` behind the encoder, its constraints included (checked before the encoder runs);
+        `last_beam_norm_scores` and `last_beam_order` are the decoder's."""
+        cons = dict(suppress_ids=suppress_ids, min_length=min_length, no_repeat_ngram_size=no_repeat_ngram_size,
+                    block_repeat=block_repeat, length_penalty=length_penalty)
+        check_beam_constraints(end_id=end_id, vocab_size=self.decoder.vocab_size, **cons)
+        ids = self.decoder.sample_beam(self.encoder(images), beam_size, end_id, return_all=return_all, **cons)
+        if self.decoder.last_beam_order is not None or self.last_beam_order is not None:
+            self.last_beam_norm_scores, self.last_beam_order = self.decoder.last_beam_norm_scores, self.decoder.last_beam_order
+        return ids
 
     @torch.no_grad()
     def sample_stochastic(self, images, state=None, **kw):
