@@ -647,6 +647,50 @@ int sat_beam_decode_ex(const float* features /*[B,E]*/, const float* embed /*[V,
                        const float* lin_w /*[V,H]*/, const float* lin_b, int B, int K, int E, int H, int V, int steps, int64_t end_id,
                        const sat_beam_constraints* c /*[host], nullable*/, int64_t* ids, float* scores, float* norm_scores,
                        int32_t* order, void* workspace, int64_t ws_bytes, sat_stream_t stream);
+/* Diverse beam search (added within ABI 18; Vijayakumar et al. 2016, arXiv:1610.02424: beam groups with a Hamming diversity penalty).
+ * K = beam width <= 8, G = num_groups, 1 <= G <= K, K % G == 0, Kg = K / G.  Slots g*Kg .. g*Kg + Kg - 1 are GROUP g, and a hypothesis
+ * never leaves its group: every parent of a slot of group g is a slot of group g.  lambda = diversity_penalty, finite, >= 0.
+ * START: slot g*Kg of every group is live at score 0, the other slots are dead (-inf).  G == 1 is the plain start.
+ * SELECTION at step i, per image, the groups in order g = 0 .. G-1.  The candidates of group g are the (k, v) with k in group g;
+ *   s(k, v) = scores_in[b,k] + (logit[v] - lse), the f32 expression of sat_beam_step / sat_beam_step_ex: lse over ALL V columns, a
+ *   banned column is no candidate, nothing is renormalised.  The selection KEY is key = s - lambda * n(v), n(v) = the number of slots
+ *   in groups h < g whose token chosen AT THIS SAME STEP is v and counts (below).  The key is formed in f32 as one rounded multiply
+ *   and one rounded subtract (no fused multiply-add); n == 0 leaves key = s bit for bit.  The Kg best keys win under (key desc, flat
+ *   index k*V+v asc) and become slots g*Kg + r, r = 0 .. Kg-1, best first.  scores_out is the RAW s of the winner, not the key.
+ * WHY RAW: `scores` stays the sum of the model's token log-probabilities, as under constraints.  This is eq. 5 of the paper: the
+ *   diversity term belongs to the current step's objective only.  Some other implementations fold the penalty into the carried
+ *   score; this one does not.
+ * A FINISHED row (last token == end_id) has its one continuation, end_id at unchanged score; it is not penalised and its token does
+ *   not count.  A DEAD row has no candidate.  A group with fewer than Kg candidates leaves score -inf, parent g*Kg, token 0 in its
+ *   surplus slots; these do not count.  WHAT COUNTS: every other chosen token, once per slot that chose it -- two slots of earlier
+ *   groups that both chose v give n(v) = 2, and a live row choosing end_id counts.  Tokens chosen within one group do not penalise
+ *   each other.
+ * The row pass is sat_beam_step_ex's, unchanged: every row's K best raw candidates are deep enough for an exact group selection
+ *   (at most K - Kg tokens are penalised, so Kg unpenalised candidates of a row beat everything behind its K-th; the lemma is
+ *   written out at beam_merge_groups_kernel).  Constraints compose: bans are per row and applied before the selection.
+ * G == 1: the launches of sat_beam_step_ex / sat_beam_decode_ex, bit-identical outputs; diversity_penalty is not read.
+ * sat_beam_step_groups: sat_beam_step_ex's arguments with num_groups and diversity_penalty behind T.  scores_in carries the start
+ *   above at i == 0 (the caller's).  With G > 1 and end_id >= 0, last_tokens is required at i > 0.  workspace:
+ *   sat_beam_step_groups_ws_bytes (= sat_beam_step_ex_ws_bytes).
+ * sat_beam_decode_groups: sat_beam_decode_ex's loop and arguments with the two behind `c`.  The search keeps its results in group
+ *   order; with G > 1 the result ALWAYS passes through the rerank: order (norm desc, search slot asc), norm = score / L^alpha or the
+ *   score itself at length_penalty 0 (c may be NULL); order[b][r] is the search slot of the hypothesis now at rank r, its group is
+ *   order / Kg.  workspace: sat_beam_decode_groups_ws_bytes (= sat_beam_decode_ex_ws_bytes), 256-byte aligned.
+ * Errors, before anything is enqueued, beside those of the _ex entry points.  SAT_ERR_ARG: G < 1, K % G != 0; with G > 1 a
+ *   diversity_penalty that is negative, NaN or infinite, and (step call) end_id >= 0 at i > 0 with last_tokens NULL.
+ *   SAT_ERR_UNSUPPORTED: K > 8. */
+int sat_beam_step_groups(const float* logits /*[B*K, ldl]*/, int64_t ldl, const float* scores_in /*[B*K]*/,
+                         const int64_t* last_tokens /*[B*K] or NULL*/, int64_t end_id, int B, int K, int V,
+                         const sat_beam_constraints* c /*[host], nullable*/, const int32_t* parents, const int64_t* tokens, int i, int T,
+                         int num_groups, float diversity_penalty, int32_t* parent /*[B*K]*/, int64_t* token /*[B*K]*/,
+                         float* scores_out /*[B*K]*/, void* workspace, int64_t ws_bytes, sat_stream_t stream);
+int64_t sat_beam_step_groups_ws_bytes(int B, int K, int V, int T);
+int64_t sat_beam_decode_groups_ws_bytes(int B, int K, int E, int H, int V, int num_layers, int steps);
+int sat_beam_decode_groups(const float* features /*[B,E]*/, const float* embed /*[V,E]*/, const float* const* lstm_w /*[host]*/,
+                           int num_layers, const float* lin_w /*[V,H]*/, const float* lin_b, int B, int K, int E, int H, int V, int steps,
+                           int64_t end_id, const sat_beam_constraints* c /*[host], nullable*/, int num_groups, float diversity_penalty,
+                           int64_t* ids, float* scores, float* norm_scores, int32_t* order, void* workspace, int64_t ws_bytes,
+                           sat_stream_t stream);
 /* Scheduled sampling (the reference's DecoderRNN.ss_prob, models.py:38, and its schedule, train.py:109-113) in the training forward.
  * Random numbers: Philox4x32-10, key (seed & 0xffffffff, seed >> 32), u = ((x >> 8) + 0.5) * 2^-24.  The draw for row b of step t is
  * s(b, t) = first argmax_v (logit[b][v] + G(b, t, v)), G = -log(-log u) of counter (v >> 2, b, t, 2*rank), word v & 3 (Gumbel-max: an

@@ -188,6 +188,12 @@ SIGNATURES = {
     "sat_beam_decode_ex_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
     "sat_beam_decode_ex": (_i, [_vp, _vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, C.POINTER(SatBeamConstraints),
                                 _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sat_beam_step_groups": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _i, _i, C.POINTER(SatBeamConstraints), _vp, _vp, _i, _i, _i, _f, _vp, _vp,
+                                  _vp, _vp, _i64, _vp]),
+    "sat_beam_step_groups_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "sat_beam_decode_groups_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
+    "sat_beam_decode_groups": (_i, [_vp, _vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, C.POINTER(SatBeamConstraints),
+                                    _i, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sat_greedy_decode": (_i, [_vp, _vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "sat_ss_decoder_fwd_ws_bytes": (_i64, [_i, _i]),
     "sat_vocab_sample": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i64, _f, C.c_uint64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i, _vp,
@@ -235,7 +241,8 @@ ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_at
                     "sat_rollout_attend_fwd_ws_bytes", "sat_rollout_attend_fwd", "sat_bleu_comps", "sat_bleu_finalize",
                     "sat_rouge_l_score", "sat_sample_filtered_ws_bytes", "sat_sample_filtered", "sat_sample_decode_ws_bytes",
                     "sat_sample_decode", "sat_dropout_f32", "sat_beam_step_ex", "sat_beam_step_ex_ws_bytes", "sat_beam_rerank",
-                    "sat_beam_decode_ex_ws_bytes", "sat_beam_decode_ex")
+                    "sat_beam_decode_ex_ws_bytes", "sat_beam_decode_ex", "sat_beam_step_groups", "sat_beam_step_groups_ws_bytes",
+                    "sat_beam_decode_groups_ws_bytes", "sat_beam_decode_groups")
 
 _lib = None
 

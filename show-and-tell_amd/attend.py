@@ -27,7 +27,7 @@ import torch.nn as nn
 from . import _lib as L
 from .attend_bwd import PARAM_ORDER, attend_backward
 from .decoder import dropout_rows
-from .models import check_beam_constraints, check_dropout_p, check_sample_args, draw_ss_seed, lookahead_stream, refuse_dropout_with, stochastic_result
+from .models import check_beam_constraints, check_beam_groups, check_dropout_p, check_sample_args, draw_ss_seed, lookahead_stream, refuse_dropout_with, stochastic_result
 from .pack import PackInfo
 from .scst import SelfCritical
 from .vgg import VGG16_FEATURES, VggFeatures, VggProgram, _VggFn  # noqa: F401  (VggFeatures is re-exported by the package)
@@ -344,6 +344,7 @@ class ShowAttendTellModel(nn.Module):
     """model2.py:9-111.  `compute_dtype` ('bf16' conv stack / 'f32' parity) and `vgg_cfg` are build extensions."""
 
     last_beam_norm_scores = last_beam_order = None     # set by a constrained `sample_beam` (None after a plain one)
+    last_beam_groups = None                            # set by a grouped `sample_beam`: [B,K] i32, the group of the hypothesis at r
 
     def __init__(self, hidden_size, context_size, vocab_size, embed_size, opt=None, feature_size=(196, 512),
                  compute_dtype="bf16", vgg_cfg=VGG16_FEATURES):
@@ -681,7 +682,7 @@ class ShowAttendTellModel(nn.Module):
     @torch.no_grad()
     def sample_beam_features(self, features, beam_size=5, states=None, end_id=None, steps=20, start_id=1, return_all=False,
                              return_alphas=False, *, suppress_ids=None, min_length=0, no_repeat_ngram_size=0, block_repeat=False,
-                             length_penalty=0.0):
+                             length_penalty=0.0, num_beam_groups=1, diversity_penalty=0.0):
         """Beam search over `sample`'s loop (model2.py:91-111; the reference's `sample_beam` is a stub, model2.py:113-114, so parity
         is pinned only at beam_size=1 == the greedy goldens).  Rows are (image b, hypothesis k) = b*K + k: the features and their
         attention encoding are replicated per hypothesis once (data movement), every step is `_EvalDecoder.step` on B*K rows,
@@ -692,9 +693,12 @@ class ShowAttendTellModel(nn.Module):
         the map of a step belongs to the slot its survivor was expanded from.
         Constraints as `DecoderRNN.sample_beam` documents them (all off by default: the calls are then the ones above): every step
         is `sat_beam_step_ex` over this loop's own (parents, tokens) records, and `sat_beam_rerank` re-orders ids, scores and maps
-        once the search is over; `last_beam_norm_scores` / `last_beam_order` [B,K] as there."""
+        once the search is over; `last_beam_norm_scores` / `last_beam_order` [B,K] as there.
+        Beam groups as `DecoderRNN.sample_beam` documents them: with num_beam_groups > 1 the first slot of every group starts live,
+        every step is `sat_beam_step_groups`, the rerank always runs (maps included) and `last_beam_groups` is set."""
         cons = check_beam_constraints(suppress_ids, min_length, no_repeat_ngram_size, block_repeat, length_penalty, end_id,
                                       self.vocab_size, steps)
+        G, lam = check_beam_groups(beam_size, num_beam_groups, diversity_penalty)
         K = int(beam_size)
         if K < 1 or K > 8:
             raise ValueError("beam_size must be in 1..8")
@@ -706,7 +710,7 @@ class ShowAttendTellModel(nn.Module):
         ldl = L.pad4(V)
         logits = torch.zeros(R, ldl, device=dev)
         scores = torch.full((B, K), float("-inf"), device=dev)
-        scores[:, 0] = 0.0
+        scores[:, ::K // G] = 0.0                        # the first slot of every group (one group: hypothesis 0)
         scores2 = torch.empty(B, K, device=dev)
         bws = torch.empty(lib.sat_beam_step_ws_bytes(B, K), dtype=torch.uint8, device=dev)
         parents = torch.empty(steps, R, dtype=torch.int32, device=dev)
@@ -714,14 +718,18 @@ class ShowAttendTellModel(nn.Module):
         eid = -1 if end_id is None else int(end_id)
         cstruct = cons.struct(dev) if cons.active else None
         if self.last_beam_order is not None:
-            self.last_beam_norm_scores = self.last_beam_order = None
+            self.last_beam_norm_scores = self.last_beam_order = self.last_beam_groups = None
 
         def pick(i):
             nonlocal scores, scores2, c2
             L.check(lib.sat_vocab_logits_fwd(L.ptr(d.Z), L.ptr(cls.weight), L.ptr(cls.bias), R, E, V, L.ptr(logits), ldl, st),
                     "sat_vocab_logits_fwd")
             last = tokens[i - 1].data_ptr() if (i > 0 and eid >= 0) else None
-            if cstruct is not None:
+            if G > 1:
+                L.check(lib.sat_beam_step_groups(L.ptr(logits), ldl, L.ptr(scores), last, eid, B, K, V, cstruct, L.ptr(parents),
+                                                 L.ptr(tokens), i, steps, G, lam, parents[i].data_ptr(), tokens[i].data_ptr(),
+                                                 L.ptr(scores2), L.ptr(bws), bws.numel(), st), "sat_beam_step_groups")
+            elif cstruct is not None:
                 L.check(lib.sat_beam_step_ex(L.ptr(logits), ldl, L.ptr(scores), last, eid, B, K, V, cstruct, L.ptr(parents), L.ptr(tokens),
                                              i, steps, parents[i].data_ptr(), tokens[i].data_ptr(), L.ptr(scores2), L.ptr(bws),
                                              bws.numel(), st), "sat_beam_step_ex")
@@ -742,17 +750,19 @@ class ShowAttendTellModel(nn.Module):
         ids = torch.empty(B, K, steps, dtype=torch.int64, device=dev)
         L.check(lib.sat_beam_backtrack(L.ptr(parents), L.ptr(tokens), steps, B, K, L.ptr(ids), st), "sat_beam_backtrack")
         order = None
-        if cstruct is not None:                          # the K results of an image by score / length^alpha (alpha 0: as they are)
+        if cstruct is not None or G > 1:                 # the K results of an image by score / length^alpha (alpha 0: by score)
             ids2, ranked = torch.empty_like(ids), torch.empty(B, K, device=dev)
             norm, order = torch.empty(B, K, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev)
             L.check(lib.sat_beam_rerank(L.ptr(ids), L.ptr(scores), B, K, steps, eid, cons.length_penalty, L.ptr(ids2), L.ptr(ranked),
                                         L.ptr(norm), L.ptr(order), st), "sat_beam_rerank")
             ids, scores = ids2, ranked
             self.last_beam_norm_scores, self.last_beam_order = norm, order
+            if G > 1:
+                self.last_beam_groups = order // (K // G)
         if return_alphas:
             alphas = torch.empty(B, K, steps, P, device=dev)
             L.check(lib.sat_beam_backtrack_rows(L.ptr(parents), L.ptr(d.amaps), steps, B, K, P, L.ptr(alphas), st), "sat_beam_backtrack_rows")
-            if order is not None and cons.length_penalty > 0:      # the maps follow their hypothesis
+            if order is not None and (cons.length_penalty > 0 or G > 1):      # the maps follow their hypothesis
                 ranked_maps = torch.empty_like(alphas)
                 L.check(lib.sat_beam_gather_rows(L.ptr(alphas), L.ptr(order), B, K, steps * P, L.ptr(ranked_maps), st),
                         "sat_beam_gather_rows")
@@ -766,11 +776,14 @@ class ShowAttendTellModel(nn.Module):
 
     @torch.no_grad()
     def sample_beam(self, images, beam_size=5, states=None, end_id=None, return_all=False, return_alphas=False, *, suppress_ids=None,
-                    min_length=0, no_repeat_ngram_size=0, block_repeat=False, length_penalty=0.0):
+                    min_length=0, no_repeat_ngram_size=0, block_repeat=False, length_penalty=0.0, num_beam_groups=1,
+                    diversity_penalty=0.0):
         """`sample_beam(images, ...)`: the method the reference leaves as a stub (model2.py:113-114); BASELINE configs[4] asks beam 5.
-        Constraints as `sample_beam_features` (checked before the encoder runs)."""
+        Constraints and beam groups as `sample_beam_features` (checked before the encoder runs)."""
         cons = dict(suppress_ids=suppress_ids, min_length=min_length, no_repeat_ngram_size=no_repeat_ngram_size,
                     block_repeat=block_repeat, length_penalty=length_penalty)
         check_beam_constraints(end_id=end_id, vocab_size=self.vocab_size, **cons)
+        if check_beam_groups(beam_size, num_beam_groups, diversity_penalty)[0] > 1:
+            cons.update(num_beam_groups=num_beam_groups, diversity_penalty=diversity_penalty)
         feats, _ = self._encode(images)
         return self.sample_beam_features(feats, beam_size, states, end_id, return_all=return_all, return_alphas=return_alphas, **cons)

@@ -5,6 +5,8 @@
 //   beam_row_kernel   one workgroup per (image, hypothesis) row, the row read ONCE into registers: log-sum-exp and the
 //                     row's K best continuations (thread-local sorted lists in registers, K rounds of block arg-best);
 //   beam_merge_kernel one wave per image: the K best of its K*K row candidates.
+//   (beam_merge_groups_kernel in its place for a diverse beam search: the K slots as groups that select in order, each under a
+//   penalty for the tokens the groups in front chose at this step)
 // The union of per-row top-K lists contains the global top-K, and both kernels order candidates by (score desc, flat
 // index k*V+v asc), so the result is the exact top-K with a deterministic tie rule.
 #include "sat_decode_state.h"
@@ -382,6 +384,33 @@ __global__ __launch_bounds__(NT) void beam_row_ban_kernel(const float* __restric
     beam_row_body<NT, true>(logits, ldl, scores_in, last_tok, end_id, K, V, cand_val, cand_idx, ban, s_ban);
 }
 
+// the second half of both merge kernels: behind ONE barrier all four waves move the rows of the next step -- the embedding row of the
+// chosen token and, in the wide decode path, the (h, c) rows of the hypothesis it extends -- every row by its own wave with all its
+// loads in flight at once
+__device__ __forceinline__ void beam_move_rows(const int* s_par, const int* s_tok, int b, int K, int lane, int wave,
+                                               const float* __restrict__ embed, int E, float* __restrict__ x_next, long ldx,
+                                               const float* __restrict__ h_src, const float* __restrict__ c_src, int H,
+                                               float* __restrict__ h_dst, long ldh, float* __restrict__ c_dst) {
+    if (!embed && !h_src) return;                          // (uniform)
+    __syncthreads();
+    for (int r = wave; r < K; r += 4) {
+        const int par = s_par[r], tok = s_tok[r];
+        const long to = (long)(b * K + r);
+        if (embed) {                                       // the next step's input row: embed(token) (models.py:64)
+            const float* src = embed + (long)tok * E;
+            for (int e = lane * 4; e < E; e += 256) *(f32x4*)(x_next + to * ldx + e) = *(const f32x4*)(src + e);
+        }
+        if (h_src) {                                       // ... and the LSTM state of the hypothesis it extends
+            const long from = (long)(b * K + par) * H;
+            for (int e = lane * 4; e < H; e += 256) {
+                const f32x4 hv = *(const f32x4*)(h_src + from + e), cv = *(const f32x4*)(c_src + from + e);
+                *(f32x4*)(h_dst + to * ldh + e) = hv;
+                *(f32x4*)(c_dst + to * H + e) = cv;
+            }
+        }
+    }
+}
+
 // One workgroup of 256 threads per image: wave 0 merges (K rounds of a wave-wide arg-best over the image's K * K row candidates), then
 // -- one barrier -- all four waves move the rows of the next step: embedding row of the chosen token and, in the wide decode path, the
 // (h, c) rows of the hypothesis it extends, every row by its own wave with all its loads in flight at once (the copies used to sit
@@ -420,35 +449,95 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict
             }
         }
     }
-    if (!embed && !h_src) return;                          // (uniform)
-    __syncthreads();
-    for (int r = wave; r < K; r += 4) {
-        const int par = s_par[r], tok = s_tok[r];
-        const long to = (long)(b * K + r);
-        if (embed) {                                       // the next step's input row: embed(token) (models.py:64)
-            const float* src = embed + (long)tok * E;
-            for (int e = lane * 4; e < E; e += 256) *(f32x4*)(x_next + to * ldx + e) = *(const f32x4*)(src + e);
+    beam_move_rows(s_par, s_tok, b, K, lane, wave, embed, E, x_next, ldx, h_src, c_src, H, h_dst, ldh, c_dst);
+}
+
+// the selection key of a candidate that n slots of the groups in front chose at this step: ONE rounded multiply and ONE rounded
+// subtract (no contraction into an fma: a plain f32 restatement rounds the same way)
+__device__ __forceinline__ float beam_penalised_key(float s, float lambda, int n) {
+#pragma clang fp contract(off)
+    const float p = lambda * (float)n;
+    return s - p;
+}
+
+// DIVERSE beam search (sat_beam_step_groups, include/sat_hip.h): beam_merge_kernel with the K slots of an image as G = K / Kg groups
+// that select IN ORDER, each under the key s - lambda * n(v), n(v) = how many slots of the groups in front chose token v at this same
+// step (finished rows' end_id and surplus slots do not count; a finished row's candidate is not penalised).  The carried score is the
+// raw s.  Wave 0 holds the image's K * K row candidates, one per lane, as the plain merge does; lane j < K also keeps the token slot j
+// chose (-1: it does not count), so n(v) is at most K compares against readlanes of wave-uniform slots.  Group g's keys are formed
+// once, before its rounds -- the tokens of a group are published to the lanes' compares only by the next group's key pass, so they do
+// not penalise each other -- then Kg rounds of wave_argbest: K rounds over the step, as many as the plain merge runs.
+//
+// LEMMA: group g's Kg winners under the key all lie within the raw top-K lists of group g's rows, which is all the row kernels leave.
+// Take a candidate c outside its row's raw top K: at least K candidates of that row are ahead of it under (s desc, index asc).  At most
+// g * Kg <= K - Kg distinct tokens are penalised, so at least Kg of those ahead are unpenalised and keep key = s; key(c) <= s(c)
+// because lambda >= 0; so Kg candidates of its own row alone beat c under (key desc, index asc).
+__global__ __launch_bounds__(256) void beam_merge_groups_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_idx,
+                                                                int K, int V, int Kg, float lambda, const int64_t* __restrict__ last_tok,
+                                                                long end_id, int* __restrict__ parent, int64_t* __restrict__ token,
+                                                                float* __restrict__ scores_out, const float* __restrict__ embed, int E,
+                                                                float* __restrict__ x_next, long ldx, const float* __restrict__ h_src,
+                                                                const float* __restrict__ c_src, int H, float* __restrict__ h_dst, long ldh,
+                                                                float* __restrict__ c_dst) {
+    __shared__ int s_par[KMAX], s_tok[KMAX];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (wave == 0) {
+        float v = -INFINITY;
+        int ix = INT_MAX;
+        if (lane < K * K) {
+            v = cand_val[(long)b * K * K + lane];
+            ix = cand_idx[(long)b * K * K + lane];
         }
-        if (h_src) {                                       // ... and the LSTM state of the hypothesis it extends
-            const long from = (long)(b * K + par) * H;
-            for (int e = lane * 4; e < H; e += 256) {
-                const f32x4 hv = *(const f32x4*)(h_src + from + e), cv = *(const f32x4*)(c_src + from + e);
-                *(f32x4*)(h_dst + to * ldh + e) = hv;
-                *(f32x4*)(c_dst + to * H + e) = cv;
+        const bool has = ix != INT_MAX;                    // (the row kernels leave INT_MAX with every -inf)
+        const int slot = has ? ix / V : 0, tok = has ? ix - slot * V : -2, group = has ? slot / Kg : -1;
+        const bool finished = has && last_tok != nullptr && end_id >= 0 && last_tok[b * K + slot] == end_id;
+        int chosen = -1;                                   // lane j < K: the token slot j chose at this step, if it counts
+        for (int g = 0; g * Kg < K; ++g) {
+            int n = 0;
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) n += (__builtin_amdgcn_readlane(chosen, j) == tok) ? 1 : 0;      // (tok >= 0 or -2; -1 matches none)
+            const bool mine = group == g;
+            float key = mine ? ((n > 0 && !finished) ? beam_penalised_key(v, lambda, n) : v) : -INFINITY;
+            int kix = mine ? ix : INT_MAX;
+            for (int r = 0; r < Kg; ++r) {
+                float bv = key;
+                int bi = kix;
+                wave_argbest(bv, bi);                      // (bv, bi) are the same in every lane after the reduction
+                const bool ok = bi != INT_MAX;
+                const bool won = ok && kix == bi;          // at most one lane: candidate indexes are unique
+                const unsigned long long who = __ballot(won);
+                const int src = ok ? __ffsll((long long)who) - 1 : 0;
+                const float raw = __shfl(v, src, 64);      // the carried score is the raw s of the winner, not its key
+                const bool counts = ok && __ballot(won && !finished) != 0ull;
+                if (won) {                                 // the winner leaves the pool
+                    key = -INFINITY;
+                    kix = INT_MAX;
+                }
+                const int to = g * Kg + r;
+                const int par = ok ? bi / V : g * Kg, tk = ok ? bi % V : 0;
+                if (lane == to) chosen = counts ? tk : -1;
+                if (lane == 0) {
+                    parent[b * K + to] = par;
+                    token[b * K + to] = tk;
+                    scores_out[b * K + to] = ok ? raw : -INFINITY;
+                    s_par[to] = par;
+                    s_tok[to] = tk;
+                }
             }
         }
     }
+    beam_move_rows(s_par, s_tok, b, K, lane, wave, embed, E, x_next, ldx, h_src, c_src, H, h_dst, ldh, c_dst);
 }
 
-// x0 row (b, k) = features[b]; scores: hypothesis 0 of every image live at 0, the others dead
+// x0 row (b, k) = features[b]; scores: the first slot of every group of Kg live at 0, the others dead (Kg == K: hypothesis 0 alone)
 __global__ __launch_bounds__(256) void beam_init_kernel(const float* __restrict__ features, int K, int E, long total,
-                                                        float* __restrict__ x0, long ldx, float* __restrict__ scores, int R) {
+                                                        float* __restrict__ x0, long ldx, float* __restrict__ scores, int R, int Kg) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long row = i / E;
         x0[row * ldx + (i - row * E)] = features[(row / K) * E + (i - row * E)];
     }
     const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t < R) scores[t] = (t % K) == 0 ? 0.0f : -INFINITY;
+    if (t < R) scores[t] = ((t % K) % Kg) == 0 ? 0.0f : -INFINITY;
 }
 
 // the (h, c) rows of one layer re-ordered by parent in ONE launch: dst row (b, k) = src row (b, parent[b, k])
@@ -642,6 +731,18 @@ void beam_row_launch(hipStream_t s, const float* logits, long ldl, const float* 
     }
 }
 
+// the merge launch of one step: the grouped kernel for groups of Kg < K slots, the plain one otherwise
+void beam_merge_launch(hipStream_t s, int B, const float* cand_val, const int* cand_idx, int K, int V, int Kg, float lambda,
+                       const int64_t* last, long end_id, int32_t* parent, int64_t* token, float* scores_out, const float* embed, int E,
+                       float* x_next, long ldx, const float* h_src, const float* c_src, int H, float* h_dst, long ldh, float* c_dst) {
+    if (Kg < K)
+        hipLaunchKernelGGL(beam_merge_groups_kernel, dim3(B), dim3(256), 0, s, cand_val, cand_idx, K, V, Kg, lambda, last, end_id, parent,
+                           token, scores_out, embed, E, x_next, ldx, h_src, c_src, H, h_dst, ldh, c_dst);
+    else
+        hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, s, cand_val, cand_idx, K, V, parent, token, scores_out, embed, E, x_next,
+                           ldx, h_src, c_src, H, h_dst, ldh, c_dst);
+}
+
 }  // namespace
 
 extern "C" int sat_kept_tokens(const int64_t* ids, int64_t stride, int B, int T, int64_t end_id, int32_t* kept,
@@ -705,6 +806,44 @@ extern "C" int sat_beam_step_ex(const float* logits, int64_t ldl, const float* s
     return SAT_OK;
 }
 
+// the checks of the two grouped entry points, before anything is enqueued (G == 1: lambda is not read)
+static int beam_groups_check(int K, int G, float lambda) {
+    if (G < 1 || K <= 0 || K % G != 0) return SAT_ERR_ARG;
+    if (G > 1 && (!(lambda >= 0.0f) || lambda == INFINITY)) return SAT_ERR_ARG;
+    return SAT_OK;
+}
+
+extern "C" int64_t sat_beam_step_groups_ws_bytes(int B, int K, int V, int T) { return sat_beam_step_ex_ws_bytes(B, K, V, T); }
+
+extern "C" int sat_beam_step_groups(const float* logits, int64_t ldl, const float* scores_in, const int64_t* last_tokens,
+                                    int64_t end_id, int B, int K, int V, const sat_beam_constraints* c, const int32_t* parents,
+                                    const int64_t* tokens, int i, int T, int num_groups, float diversity_penalty, int32_t* parent,
+                                    int64_t* token, float* scores_out, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    if (!logits || !scores_in || !parent || !token || !scores_out || !workspace) return SAT_ERR_ARG;
+    if (B <= 0 || K <= 0 || V <= 0 || ldl < V || T <= 0 || i < 0 || i >= T) return SAT_ERR_ARG;
+    SAT_TRY(beam_groups_check(K, num_groups, diversity_penalty));
+    if (num_groups == 1)                                       // the launches of sat_beam_step_ex
+        return sat_beam_step_ex(logits, ldl, scores_in, last_tokens, end_id, B, K, V, c, parents, tokens, i, T, parent, token, scores_out,
+                                workspace, ws_bytes, stream);
+    if (end_id >= 0 && i > 0 && !last_tokens) return SAT_ERR_ARG;      // which rows are finished decides what is penalised and counted
+    bool active = false;
+    SAT_TRY(beam_constraints_check(c, end_id, &active));
+    if (active && i > 0 && (!parents || !tokens)) return SAT_ERR_ARG;
+    if (K > KMAX || (long)K * V > INT_MAX - 1) return SAT_ERR_UNSUPPORTED;
+    if (active && (T > kBanTMax || V > kBanVMax)) return SAT_ERR_UNSUPPORTED;
+    if (ws_bytes < sat_beam_step_groups_ws_bytes(B, K, V, T)) return SAT_ERR_WORKSPACE;
+    float* cand_val = (float*)workspace;                       // [B*K rows][K]: deep enough for every group (the lemma at the kernel)
+    int* cand_idx = (int*)(cand_val + (long)B * K * K);
+    hipStream_t s = (hipStream_t)stream;
+    beam_row_launch(s, logits, (long)ldl, scores_in, last_tokens, (long)end_id, B * K, K, V, cand_val, cand_idx, active ? c : nullptr,
+                    parents, tokens, i);
+    SAT_LAUNCH_CHECK();
+    beam_merge_launch(s, B, cand_val, cand_idx, K, V, K / num_groups, diversity_penalty, last_tokens, (long)end_id, parent, token, scores_out,
+                      nullptr, 0, nullptr, 0L, nullptr, nullptr, 0, nullptr, 0L, nullptr);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
 extern "C" int sat_beam_rerank(const int64_t* ids, const float* scores, int B, int K, int T, int64_t end_id, float length_penalty,
                                int64_t* ids_out, float* scores_out, float* norm_out, int32_t* order_out, sat_stream_t stream) {
     if (!ids || !scores || !ids_out || !scores_out || ids == ids_out || scores == scores_out) return SAT_ERR_ARG;
@@ -745,13 +884,16 @@ extern "C" int64_t sat_beam_decode_ex_ws_bytes(int B, int K, int E, int H, int V
     return base <= 0 ? 0 : base + beam_decode_ex_extra((int64_t)B * K, steps);
 }
 
-// ONE loop for sat_beam_decode (ex false, c NULL) and sat_beam_decode_ex: with constraints the row launch of a step that bans
-// something is the constrained kernel, and with a length penalty the rerank runs behind the backtrack; nothing else differs
+// ONE loop for sat_beam_decode (ex false, c NULL), sat_beam_decode_ex and sat_beam_decode_groups: with constraints the row launch of a
+// step that bans something is the constrained kernel; with G > 1 groups the first slot of every group starts live and the merge
+// launch of every step is the grouped one; with a length penalty or with groups the rerank runs behind the backtrack; nothing else
+// differs
 static int beam_decode_impl(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
                             const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
-                            int64_t end_id, bool ex, const sat_beam_constraints* c, int64_t* ids, float* scores_out, float* norm_scores,
-                            int32_t* order, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+                            int64_t end_id, bool ex, const sat_beam_constraints* c, int G, float lambda, int64_t* ids, float* scores_out,
+                            float* norm_scores, int32_t* order, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
     if (!features || !embed || !lstm_w || !lin_w || !lin_b || !ids || !workspace) return SAT_ERR_ARG;
+    SAT_TRY(beam_groups_check(K, G, lambda));
     const int64_t need = ex ? sat_beam_decode_ex_ws_bytes(B, K, E, H, V, num_layers, steps)
                             : sat_beam_decode_ws_bytes(B, K, E, H, V, num_layers, steps);
     if (need <= 0) return SAT_ERR_ARG;
@@ -759,7 +901,8 @@ static int beam_decode_impl(const float* features, const float* embed, const flo
     SAT_TRY(beam_constraints_check(c, end_id, &active));
     if ((E & 3) || (long)K * V > INT_MAX - 1) return SAT_ERR_UNSUPPORTED;
     if (active && (steps > kBanTMax || V > kBanVMax)) return SAT_ERR_UNSUPPORTED;
-    const bool rerank = c && c->length_penalty > 0.0f;
+    const bool rerank = (c && c->length_penalty > 0.0f) || G > 1;      // (groups: the results leave in (norm desc, slot asc) order)
+    const int Kg = K / G;
     const float c_length_penalty = c ? c->length_penalty : 0.0f;
     if (!active) c = nullptr;
     if (ws_bytes < need || (((uintptr_t)workspace) & 255)) return SAT_ERR_WORKSPACE;
@@ -844,7 +987,7 @@ static int beam_decode_impl(const float* features, const float* embed, const flo
         if (grid > 2048) grid = 2048;
         if ((long)grid * 256 < R) grid = sat_cdiv(R, 256);
         hipLaunchKernelGGL(beam_init_kernel, dim3(grid), dim3(256), 0, s, features, K, E, total, wide ? xh[0] : x0, wide ? ldx : (long)E,
-                           sc[0], (int)R);
+                           sc[0], (int)R, Kg);
         SAT_LAUNCH_CHECK();
     }
     float* cand_val = (float*)cand;
@@ -889,9 +1032,9 @@ static int beam_decode_impl(const float* features, const float* embed, const flo
         SAT_LAUNCH_CHECK();
         if (wide) {
             // ... the merge wave also moves (h, c) by parent: h straight into the next input row's h half (one launch fewer per step)
-            hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, s, cand_val, cand_idx, K, V, par, tok, sc[1 - si], embed, E,
-                               xh[1 - xi], ldx, (const float*)(hc + (long)cur_h[0] * R * H), (const float*)(hc + (long)(2 + cur_c[0]) * R * H), H,
-                               xh[1 - xi] + E, ldx, hc + (long)(2 + 1 - cur_c[0]) * R * H);
+            beam_merge_launch(s, B, cand_val, cand_idx, K, V, Kg, lambda, last, (long)end_id, par, tok, sc[1 - si], embed, E, xh[1 - xi], ldx,
+                              hc + (long)cur_h[0] * R * H, hc + (long)(2 + cur_c[0]) * R * H, H, xh[1 - xi] + E, ldx,
+                              hc + (long)(2 + 1 - cur_c[0]) * R * H);
             SAT_LAUNCH_CHECK();
             si = 1 - si;
             cur_c[0] = 1 - cur_c[0];
@@ -899,8 +1042,8 @@ static int beam_decode_impl(const float* features, const float* embed, const flo
             x = xe;
             continue;
         }
-        hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, s, cand_val, cand_idx, K, V, par, tok, sc[1 - si], embed, E, xe, (long)E,
-                           (const float*)nullptr, (const float*)nullptr, 0, (float*)nullptr, 0L, (float*)nullptr);
+        beam_merge_launch(s, B, cand_val, cand_idx, K, V, Kg, lambda, last, (long)end_id, par, tok, sc[1 - si], embed, E, xe, (long)E, nullptr,
+                          nullptr, 0, nullptr, 0L, nullptr);
         SAT_LAUNCH_CHECK();
         si = 1 - si;
         if (K > 1) {
@@ -948,7 +1091,7 @@ extern "C" int sat_beam_decode(const float* features, const float* embed, const 
                                const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
                                int64_t end_id, int64_t* ids, float* scores_out, void* workspace, int64_t ws_bytes,
                                sat_stream_t stream) {
-    return beam_decode_impl(features, embed, lstm_w, num_layers, lin_w, lin_b, B, K, E, H, V, steps, end_id, false, nullptr, ids,
+    return beam_decode_impl(features, embed, lstm_w, num_layers, lin_w, lin_b, B, K, E, H, V, steps, end_id, false, nullptr, 1, 0.0f, ids,
                             scores_out, nullptr, nullptr, workspace, ws_bytes, stream);
 }
 
@@ -956,8 +1099,21 @@ extern "C" int sat_beam_decode_ex(const float* features, const float* embed, con
                                   const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
                                   int64_t end_id, const sat_beam_constraints* c, int64_t* ids, float* scores_out, float* norm_scores,
                                   int32_t* order, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
-    return beam_decode_impl(features, embed, lstm_w, num_layers, lin_w, lin_b, B, K, E, H, V, steps, end_id, true, c, ids, scores_out,
-                            norm_scores, order, workspace, ws_bytes, stream);
+    return beam_decode_impl(features, embed, lstm_w, num_layers, lin_w, lin_b, B, K, E, H, V, steps, end_id, true, c, 1, 0.0f, ids,
+                            scores_out, norm_scores, order, workspace, ws_bytes, stream);
+}
+
+extern "C" int64_t sat_beam_decode_groups_ws_bytes(int B, int K, int E, int H, int V, int num_layers, int steps) {
+    return sat_beam_decode_ex_ws_bytes(B, K, E, H, V, num_layers, steps);
+}
+
+extern "C" int sat_beam_decode_groups(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
+                                      const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
+                                      int64_t end_id, const sat_beam_constraints* c, int num_groups, float diversity_penalty,
+                                      int64_t* ids, float* scores_out, float* norm_scores, int32_t* order, void* workspace,
+                                      int64_t ws_bytes, sat_stream_t stream) {
+    return beam_decode_impl(features, embed, lstm_w, num_layers, lin_w, lin_b, B, K, E, H, V, steps, end_id, true, c, num_groups,
+                            diversity_penalty, ids, scores_out, norm_scores, order, workspace, ws_bytes, stream);
 }
 
 extern "C" int sat_beam_gather_rows(const float* src, const int32_t* parent, int B, int K, int width, float* dst,

@@ -66,18 +66,21 @@ def kept_tokens(ids, end_id):
 @torch.no_grad()
 def validation_step(model, images, captions, lengths, state=None, end_id=2, beam_size=1, scorer=None, image_index=None,
                     bleu=None, rouge=None, *, suppress_ids=None, min_length=0, no_repeat_ngram_size=0, block_repeat=False,
-                    length_penalty=0.0):
+                    length_penalty=0.0, num_beam_groups=1, diversity_penalty=0.0):
     """One iteration of the loop body eval.py:71-118 (the caller has put the model in eval mode, eval.py:65).
     Returns dict(loss f32[1], ids i64[B,20], kept i32[B]) -- all on the device, nothing synchronised.  With a `CiderScorer`
     and `image_index` (the corpus image of every row) the dict gains cider f64[1] and cider_scores f64[B] of `ids`; with a
     `BleuScorer` as `bleu`, bleu_scores f64[B,4] (and `bleu.update` has run on the rows: `bleu.compute()` after the last batch
     is the corpus Bleu_1..4); with a `RougeLScorer` as `rouge`, rouge_l f64[1] and rouge_l_scores f64[B].
     The keyword-only beam constraints (`sample_beam`'s; all off by default) go to the beam decode: with any of them on the
-    decode is `sample_beam` also at beam_size=1 -- the constrained greedy decode -- which starts from the zero state."""
-    from .models import check_beam_constraints
+    decode is `sample_beam` also at beam_size=1 -- the constrained greedy decode -- which starts from the zero state.
+    num_beam_groups / diversity_penalty (`sample_beam`'s diverse beam search; one group by default) go there too."""
+    from .models import check_beam_constraints, check_beam_groups
     cons = dict(suppress_ids=suppress_ids, min_length=min_length, no_repeat_ngram_size=no_repeat_ngram_size,
                 block_repeat=block_repeat, length_penalty=length_penalty)
     constraints = cons if check_beam_constraints(end_id=end_id, **cons).active else {}
+    if check_beam_groups(beam_size, num_beam_groups, diversity_penalty)[0] > 1:
+        constraints = dict(constraints, num_beam_groups=num_beam_groups, diversity_penalty=diversity_penalty)
     if bleu is None and rouge is None:
         if (scorer is None) != (image_index is None):
             raise ValueError("scorer and image_index go together")

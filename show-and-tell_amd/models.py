@@ -544,6 +544,25 @@ def check_beam_constraints(suppress_ids=None, min_length=0, no_repeat_ngram_size
     return c
 
 
+def check_beam_groups(beam_size, num_beam_groups=1, diversity_penalty=0.0):
+    """The group arguments of the `sample_beam` methods (include/sat_hip.h, sat_beam_step_groups) -> (G, penalty as float32); a
+    ValueError names the bad one.  Host arithmetic only: runs before the library is loaded."""
+    import math
+    if num_beam_groups == 1 and type(num_beam_groups) is int and type(diversity_penalty) in (int, float) and diversity_penalty == 0:
+        return 1, 0.0                                       # the defaults: nothing to check
+    G = num_beam_groups
+    if not isinstance(G, int) or isinstance(G, bool) or G < 1:
+        raise ValueError("num_beam_groups must be an int >= 1, got %r" % (G,))
+    if int(beam_size) % G != 0:
+        raise ValueError("beam_size %d is not divisible by num_beam_groups %d" % (int(beam_size), G))
+    lam = _as_f32(diversity_penalty)
+    if isinstance(diversity_penalty, bool) or lam is None or not math.isfinite(lam) or lam < 0:
+        raise ValueError("diversity_penalty must be a finite number >= 0 (as float32), got %r" % (diversity_penalty,))
+    if lam > 0 and G == 1:
+        raise ValueError("diversity_penalty %r needs num_beam_groups > 1: one group has nothing to differ from" % (diversity_penalty,))
+    return G, lam
+
+
 def stochastic_result(ids, logprobs, logits, alphas=None):
     """What a `sample_stochastic` returns: ids, then -- in this order, each only where asked for (not None) -- the dict(logp, kept),
     the logits and the attention maps; one value alone, else a tuple"""
@@ -616,6 +635,7 @@ class DecoderRNN(nn.Module):
     """models.py:31-67."""
 
     last_beam_norm_scores = last_beam_order = None     # set by a constrained `sample_beam` (None after a plain one)
+    last_beam_groups = None                            # set by a grouped `sample_beam`: [B,K] i32, the group of the hypothesis at r
 
     def __init__(self, embed_size, hidden_size, vocab_size, num_layers):
         super().__init__()
@@ -820,7 +840,7 @@ class DecoderRNN(nn.Module):
 
     @torch.no_grad()
     def sample_beam(self, features, beam_size=5, end_id=None, steps=20, return_all=False, *, suppress_ids=None, min_length=0,
-                    no_repeat_ngram_size=0, block_repeat=False, length_penalty=0.0):
+                    no_repeat_ngram_size=0, block_repeat=False, length_penalty=0.0, num_beam_groups=1, diversity_penalty=0.0):
         """Beam search over the same 20-step loop (`model2.py:113-114` is a stub in the reference).
         Returns the best hypothesis per image, i64 [B,steps]; with return_all also (ids [B,K,steps] best-first,
         scores [B,K] = sum of token log-probabilities).  beam_size=1, end_id=None is exactly `sample`.
@@ -830,9 +850,16 @@ class DecoderRNN(nn.Module):
         block_repeat: no token twice in a row; length_penalty=alpha re-orders the K results by score / length^alpha once the
         search is over.  Scores are never renormalised: `scores` stays the raw sums, in the returned order; the normalised ones
         are kept as `last_beam_norm_scores` [B,K] and the permutation as `last_beam_order` [B,K] (the search rank of the hypothesis
-        now at r) -- both None after an unconstrained call.  beam_size=1 with constraints is the constrained greedy decode."""
+        now at r) -- both None after an unconstrained call.  beam_size=1 with constraints is the constrained greedy decode.
+        Diverse beam search (sat_beam_decode_groups; arXiv:1610.02424): num_beam_groups=G splits the K slots into G groups of K / G
+        that search in order; a group's candidates lose diversity_penalty per slot of the groups in front that chose the same token
+        at the same step.  The penalty steers the selection only: `scores` stay the raw sums.  The K results come back ordered by
+        (normalised score, search slot) through the same rerank, with `last_beam_norm_scores` and `last_beam_order` set as for a
+        constrained call and `last_beam_groups` [B,K] i32 = last_beam_order // (K / G), the group of the hypothesis now at r (None
+        after an ungrouped call).  Constraints compose: bans are per row, applied before the selection."""
         cons = check_beam_constraints(suppress_ids, min_length, no_repeat_ngram_size, block_repeat, length_penalty, end_id,
                                       self.vocab_size, steps)
+        G, lam = check_beam_groups(beam_size, num_beam_groups, diversity_penalty)
         lib = L.load()
         features = _f32c(features, "features")
         dev = features.device
@@ -845,10 +872,19 @@ class DecoderRNN(nn.Module):
         ids = torch.empty(B, K, steps, dtype=torch.int64, device=dev)
         scores = torch.empty(B, K, device=dev)
         if self.last_beam_order is not None:
-            self.last_beam_norm_scores = self.last_beam_order = None
+            self.last_beam_norm_scores = self.last_beam_order = self.last_beam_groups = None
         # every step (LSTM step, exact-f32 vocab projection, per-row log-softmax + top-K, per-image merge that also gathers the next
         # input's embedding rows, one (h, c) re-ordering launch) is enqueued by ONE library call (sat_beam_decode)
-        if cons.active:
+        if G > 1:
+            wsb = lib.sat_beam_decode_groups_ws_bytes(B, K, E, H, V, self.num_layers, steps)
+            ws, ws_ptr = L.workspace256(wsb, dev)
+            norm, order = torch.empty(B, K, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev)
+            L.check(lib.sat_beam_decode_groups(L.ptr(features), L.ptr(self.embed.weight), self._lstm_ptrs(), self.num_layers,
+                                               L.ptr(self.linear.weight), L.ptr(self.linear.bias), B, K, E, H, V, int(steps), eid,
+                                               cons.struct(dev) if cons.active else None, G, lam, ids.data_ptr(), L.ptr(scores),
+                                               L.ptr(norm), L.ptr(order), ws_ptr, wsb, st), "sat_beam_decode_groups")
+            self.last_beam_norm_scores, self.last_beam_order, self.last_beam_groups = norm, order, order // (K // G)
+        elif cons.active:
             wsb = lib.sat_beam_decode_ex_ws_bytes(B, K, E, H, V, self.num_layers, steps)
             ws, ws_ptr = L.workspace256(wsb, dev)
             norm, order = torch.empty(B, K, device=dev), torch.empty(B, K, dtype=torch.int32, device=dev)
@@ -874,6 +910,7 @@ class ShowAndTell(nn.Module):
     state_dict keys: `encoder.*`, `decoder.*`."""
 
     last_beam_norm_scores = last_beam_order = None     # set by a constrained `sample_beam` (None after a plain one)
+    last_beam_groups = None                            # set by a grouped `sample_beam`: [B,K] i32, the group of the hypothesis at r
 
     def __init__(self, embed_size, hidden_size, vocab_size, num_layers=1, arch=RESNET152, compute_dtype="bf16"):
         super().__init__()
@@ -917,15 +954,18 @@ class ShowAndTell(nn.Module):
 
     @torch.no_grad()
     def sample_beam(self, images, beam_size=5, end_id=None, return_all=False, *, suppress_ids=None, min_length=0,
-                    no_repeat_ngram_size=0, block_repeat=False, length_penalty=0.0):
-        """`DecoderRNN.sample_beam` behind the encoder, its constraints included (checked before the encoder runs);
-        `last_beam_norm_scores` and `last_beam_order` are the decoder's."""
+                    no_repeat_ngram_size=0, block_repeat=False, length_penalty=0.0, num_beam_groups=1, diversity_penalty=0.0):
+        """`DecoderRNN.sample_beam` behind the encoder, its constraints and beam groups included (checked before the encoder runs);
+        `last_beam_norm_scores`, `last_beam_order` and `last_beam_groups` are the decoder's."""
         cons = dict(suppress_ids=suppress_ids, min_length=min_length, no_repeat_ngram_size=no_repeat_ngram_size,
                     block_repeat=block_repeat, length_penalty=length_penalty)
         check_beam_constraints(end_id=end_id, vocab_size=self.decoder.vocab_size, **cons)
+        if check_beam_groups(beam_size, num_beam_groups, diversity_penalty)[0] > 1:
+            cons.update(num_beam_groups=num_beam_groups, diversity_penalty=diversity_penalty)
         ids = self.decoder.sample_beam(self.encoder(images), beam_size, end_id, return_all=return_all, **cons)
         if self.decoder.last_beam_order is not None or self.last_beam_order is not None:
             self.last_beam_norm_scores, self.last_beam_order = self.decoder.last_beam_norm_scores, self.decoder.last_beam_order
+            self.last_beam_groups = self.decoder.last_beam_groups
         return ids
 
     @torch.no_grad()
