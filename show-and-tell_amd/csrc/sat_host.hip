@@ -182,7 +182,9 @@ extern "C" int sat_fc_bn1d_bwd(const float* dy, const float* pooled, const float
     if (!dy || !pooled || !xhat || !rstd || !gamma || !dw_fc || !db_fc || !dgamma || !dbeta || !workspace)
         return SAT_ERR_ARG;
     if (ws_bytes < (int64_t)B * E * (int64_t)sizeof(float)) return SAT_ERR_WORKSPACE;
-    if ((E & 3) || (F & 3)) return SAT_ERR_UNSUPPORTED;
+    // F % 4: outer_wgrad_kernel's 16-byte rows of pooled and dw_fc.  E % 4 is the GEMM path's need only (B > 1024): the forward
+    // takes any E, and so do bn1d_bwd_kernel and outer_wgrad_kernel, which read dz by the element
+    if ((F & 3) || (B > 1024 && (E & 3))) return SAT_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     float* dz = workspace;
     SAT_TRY(sat_bn1d_bwd_launch(dy, xhat, rstd, gamma, B, E, dz, dgamma, dbeta, db_fc, s));
