@@ -965,6 +965,31 @@ int sat_rollout_attend_fwd(const float* feats, const float* ctx_enc, const float
                            const float* const* w /*[host]*/, float* const* tapes /*[host]*/, int64_t* toks, float* logits, int64_t ldl,
                            int greedy, int64_t start_id, uint64_t seed, int rank, int64_t* ids, int64_t ids_stride, int64_t* fed,
                            int64_t fed_stride, float* workspace, int64_t ws_bytes, sat_stream_t stream);
+/* Label smoothing for the cross entropy (added within ABI 18): torch's F.cross_entropy(..., label_smoothing = smoothing).  For a row
+ * x[0..V) with target t (clamped into [0, V-1] as sat_ce_rows clamps it), m = max(x), s = sum exp(x - m), lse = m + log s:
+ *     row_nll[n]  = lse - x[t]
+ *     row_loss[n] = (1 - smoothing) * row_nll[n] + smoothing * (log s - mean(x - m))      (= (smoothing / V) * sum_v (lse - x[v]))
+ *     g[n][v]     = (softmax(x)[v] - (1 - smoothing) * [v == t] - smoothing / V) * inv_denom
+ *     loss_out[0] = inv_denom * sum_n row_loss[n],  nll_out[0] = inv_denom * sum_n row_nll[n]      (sat_ce_rows's fixed order)
+ * The smoothing term is formed from values centred on the row maximum.  Non-finite logits are outside the contract.
+ * sat_ce_rows_ls: one workgroup per row, one read of the logits and one write of the gradient (sat_ce_rows's register path for
+ *   V <= 12288 with 16-byte aligned bases and ldl % 4 == 0 -- and, with a gradient, ldg % 4 == 0 --, its strided path otherwise).
+ *   grad: f32 [N, ldg] (ldg >= V), or NULL for none; grad == logits with ldg == ldl is sat_ce_rows's in-place form, any other grad
+ *   must not overlap the logits, which are then left untouched.  Pad columns [V, ldg) are left alone.  row_nll, loss_out, nll_out may
+ *   be NULL (nll_out needs row_nll).  smoothing == 0: row_loss, loss_out and grad are bit for bit sat_ce_rows's.
+ *   SAT_ERR_ARG before any launch: NULL logits / targets / row_loss, smoothing outside [0, 1) or NaN, N < 1, V < 1, ldl < V,
+ *   ldg < V with a gradient, nll_out without row_nll.
+ * sat_vocab_ce_fwd_bf16_ls: sat_vocab_ce_fwd_bf16 (same workspace, size query and shape limits; logits written as f32 and not
+ *   modified) with the smoothed loss in row_loss / loss_out, the plain one in row_nll / nll_out (either may be NULL, nll_out needs
+ *   row_nll) and the smoothed gradient rounded once to bf16 where sat_vocab_ce_bwd_bf16 expects it, pad columns zero.
+ *   smoothing == 0: the same bits as sat_vocab_ce_fwd_bf16.  smoothing outside [0, 1) or NaN: SAT_ERR_ARG. */
+int sat_ce_rows_ls(const float* logits /*[N,ldl]*/, int64_t ldl, const int64_t* targets /*[N]*/, int N, int V, float inv_denom,
+                   float smoothing, float* grad /*[N,ldg], NULL, or == logits*/, int64_t ldg, float* row_loss /*[N]*/,
+                   float* row_nll /*[N] or NULL*/, float* loss_out /*[1] or NULL*/, float* nll_out /*[1] or NULL*/, sat_stream_t stream);
+int sat_vocab_ce_fwd_bf16_ls(const float* Hs /*[N,H]*/, const float* w /*[V,H]*/, const float* b /*[V]*/, const int64_t* targets /*[N]*/,
+                             int N, int H, int V, float inv_denom, float smoothing, float* logits /*[N,ldl]*/, int64_t ldl,
+                             float* row_loss /*[N]*/, float* row_nll /*[N] or NULL*/, float* loss_out /*[1] or NULL*/,
+                             float* nll_out /*[1] or NULL*/, void* workspace /*256-byte aligned*/, int64_t ws_bytes, sat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * clip_gradient (train.py:88-91) + optim.Adam step (train.py:56,146) over one flat buffer.

@@ -21,6 +21,7 @@ from .evaluate import kept_tokens, mean_cross_entropy, pack_validation_targets, 
 from .cider import CiderScorer, encode_references  # noqa: F401
 from .langstats import BleuScorer, MixedReward, RougeLScorer  # noqa: F401
 from .scst import SelfCritical, ce_rows_weighted, scst_loss, scst_weights  # noqa: F401
+from .criterion import CrossEntropy, cross_entropy  # noqa: F401
 from .optim import FusedClampAdam  # noqa: F401
 from .pack import PackInfo, pack_targets  # noqa: F401
 from .resnet import RESNET152, conv_flops  # noqa: F401

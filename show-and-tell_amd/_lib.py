@@ -215,6 +215,8 @@ SIGNATURES = {
                                      C.c_uint64, _i, _vp, _i64, _vp, _i64, _vp]),
     "sat_scst_weights": (_i, [_vp, _i64, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sat_ce_rows_weighted": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "sat_ce_rows_ls": (_i, [_vp, _i64, _vp, _i, _i, _f, _f, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "sat_vocab_ce_fwd_bf16_ls": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sat_rollout_attend_fwd_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
     "sat_rollout_attend_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _i64,
                                     _i, _i64, C.c_uint64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -243,7 +245,7 @@ ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_at
                     "sat_rouge_l_score", "sat_sample_filtered_ws_bytes", "sat_sample_filtered", "sat_sample_decode_ws_bytes",
                     "sat_sample_decode", "sat_dropout_f32", "sat_beam_step_ex", "sat_beam_step_ex_ws_bytes", "sat_beam_rerank",
                     "sat_beam_decode_ex_ws_bytes", "sat_beam_decode_ex", "sat_beam_step_groups", "sat_beam_step_groups_ws_bytes",
-                    "sat_beam_decode_groups_ws_bytes", "sat_beam_decode_groups")
+                    "sat_beam_decode_groups_ws_bytes", "sat_beam_decode_groups", "sat_ce_rows_ls", "sat_vocab_ce_fwd_bf16_ls")
 
 _lib = None
 

@@ -5,6 +5,7 @@
 //             pointwise step, BatchNorm1d forward/backward
 //   trainer : fused elementwise clamp + Adam over one flat buffer (train.py:88-91,146)
 #include "sat_bn_stats.h"
+#include "sat_ce_ls.h"
 #include <stdlib.h>
 
 namespace {
@@ -655,6 +656,74 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(float* __restrict__ logits
     }
 }
 
+// sat_ce_rows_ls: ce_rows_kernel<false>'s two paths with label smoothing (the row arithmetic is sat_ce_ls.h's, shared with the bf16
+// form), the row's plain NLL beside its smoothed loss, and the gradient written to `grad` (NULL: none; == logits with ldg == ldl: in
+// place -- every thread overwrites only elements it has read itself, so neither pointer is __restrict__).  Still one read and one
+// write of the row: the centred sum of the smoothing term is one more block reduction over the registers that hold it.
+__global__ __launch_bounds__(256) void ce_rows_ls_kernel(const float* logits, long ldl, const int64_t* __restrict__ targets, int V,
+                                                         float inv_denom, float eps, float* grad, long ldg,
+                                                         float* __restrict__ row_loss, float* __restrict__ row_nll) {
+    __shared__ float sh[4];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* x = logits + (long)row * ldl;
+    float* g = grad ? grad + (long)row * ldg : nullptr;
+    const CeLsCoef k = ce_ls_coef(eps, V);
+    auto reduce = [&](float v, bool is_max) { return block_reduce(v, is_max, sh); };
+    auto report = [&](float nll, float smooth) {
+        row_loss[row] = ce_ls_loss(k, nll, smooth);
+        if (row_nll) row_nll[row] = nll;
+    };
+    long tgt = targets[row];
+    tgt = tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt);
+    constexpr int RC = 12;                       // as ce_rows_kernel
+    const int nq = V >> 2;
+    if ((ldl & 3) == 0 && nq <= RC * 256 && (((uintptr_t)logits) & 15) == 0 && (!grad || ((ldg & 3) == 0 && (((uintptr_t)grad) & 15) == 0))) {
+        f32x4 rc[RC];
+#pragma unroll
+        for (int c = 0; c < RC; ++c)
+            if (tid + c * 256 < nq) rc[c] = *(const f32x4*)(x + 4 * (tid + c * 256));
+        const int tail = (nq << 2) + tid;
+        const float xt = tail < V ? x[tail] : -INFINITY;
+        const CeLsRow r = ce_ls_row_stats<RC>(rc, nq, xt, tail < V, V, reduce);
+        const int tq = (int)(tgt >> 2), te = (int)(tgt & 3);
+        // the thread that holds the target logit reports the row
+#pragma unroll
+        for (int c = 0; c < RC; ++c)
+            if (tid + c * 256 == tq && tq < nq) report(r.lse - rc[c][te], r.smooth);
+        if (tail == (int)tgt && tq >= nq) report(r.lse - xt, r.smooth);
+        if (g) {
+#pragma unroll
+            for (int c = 0; c < RC; ++c) {
+                const int q = tid + c * 256;
+                if (q < nq) {
+                    f32x4 o;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] = ce_ls_grad(k, rc[c][e], r.lse, (4 * q + e) == (int)tgt, inv_denom);
+                    *(f32x4*)(g + 4 * q) = o;
+                }
+            }
+            if (tail < V) g[tail] = ce_ls_grad(k, xt, r.lse, tail == (int)tgt, inv_denom);
+        }
+        return;
+    }
+    float m = -INFINITY;
+    for (int i = tid; i < V; i += 256) m = fmaxf(m, x[i]);
+    m = reduce(m, true);
+    float s = 0.0f, d = 0.0f;
+    for (int i = tid; i < V; i += 256) {
+        s += expf(x[i] - m);
+        d += x[i] - m;
+    }
+    s = reduce(s, false);
+    d = reduce(d, false);
+    const float logs = logf(s), lse = m + logs;
+    if (tid == 0) report(lse - x[tgt], logs - d / (float)V);
+    if (g) {
+        __syncthreads();   // x[tgt] read above before any overwrite (in place)
+        for (int i = tid; i < V; i += 256) g[i] = ce_ls_grad(k, x[i], lse, i == (int)tgt, inv_denom);
+    }
+}
+
 // out[0] = sum_n w[n] * v[n] in sum_scale_kernel's order; a term of weight 0 is exactly 0 whatever v[n] holds
 __global__ __launch_bounds__(256) void weighted_sum_kernel(const float* __restrict__ v, const float* __restrict__ w, int n, float* out) {
     __shared__ float sh[256];
@@ -705,7 +774,7 @@ __global__ __launch_bounds__(256) void scst_weights_kernel(const int64_t* __rest
     }
 }
 
-__global__ __launch_bounds__(256) void sum_scale_kernel(const float* __restrict__ v, int n, float scale, float* out) {
+__device__ __forceinline__ void sum_scale_block(const float* __restrict__ v, int n, float scale, float* out) {
     __shared__ float sh[256];
     float s = 0.0f;
     for (int i = threadIdx.x; i < n; i += 256) s += v[i];
@@ -716,6 +785,17 @@ __global__ __launch_bounds__(256) void sum_scale_kernel(const float* __restrict_
         __syncthreads();
     }
     if (threadIdx.x == 0) out[0] = sh[0] * scale;
+}
+
+__global__ __launch_bounds__(256) void sum_scale_kernel(const float* __restrict__ v, int n, float scale, float* out) {
+    sum_scale_block(v, n, scale, out);
+}
+
+// two such sums as one launch of two workgroups (sat_ce_rows_ls: the smoothed loss and the plain NLL), each in sum_scale_kernel's order
+__global__ __launch_bounds__(256) void sum_scale_pair_kernel(const float* __restrict__ v0, const float* __restrict__ v1, int n, float scale,
+                                                             float* out0, float* out1) {
+    if (blockIdx.x == 0) sum_scale_block(v0, n, scale, out0);
+    else sum_scale_block(v1, n, scale, out1);
 }
 
 // out[c] = sum_r x[r*ld + c]; block = 32 columns x 8 row groups, fixed order
@@ -1277,6 +1357,25 @@ extern "C" int sat_ce_rows(float* logits, int64_t ldl, const int64_t* targets, i
     SAT_LAUNCH_CHECK();
     if (loss_out) {
         hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(256), 0, s, row_loss, N, inv_denom, loss_out);
+        SAT_LAUNCH_CHECK();
+    }
+    return SAT_OK;
+}
+
+extern "C" int sat_ce_rows_ls(const float* logits, int64_t ldl, const int64_t* targets, int N, int V, float inv_denom, float smoothing,
+                              float* grad, int64_t ldg, float* row_loss, float* row_nll, float* loss_out, float* nll_out,
+                              sat_stream_t stream) {
+    if (!logits || !targets || !row_loss || N < 1 || V < 1 || ldl < V || (grad && ldg < V)) return SAT_ERR_ARG;
+    if (!(smoothing >= 0.0f && smoothing < 1.0f) || (nll_out && !row_nll)) return SAT_ERR_ARG;     // (a NaN fails the first)
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ce_rows_ls_kernel, dim3(N), dim3(256), 0, s, logits, (long)ldl, targets, V, inv_denom, smoothing, grad, (long)ldg,
+                       row_loss, row_nll);
+    SAT_LAUNCH_CHECK();
+    if (loss_out && nll_out) {
+        hipLaunchKernelGGL(sum_scale_pair_kernel, dim3(2), dim3(256), 0, s, row_loss, row_nll, N, inv_denom, loss_out, nll_out);
+        SAT_LAUNCH_CHECK();
+    } else if (loss_out || nll_out) {
+        hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(256), 0, s, loss_out ? row_loss : row_nll, N, inv_denom, loss_out ? loss_out : nll_out);
         SAT_LAUNCH_CHECK();
     }
     return SAT_OK;

@@ -13,6 +13,7 @@
 // a multiple of 64 with zeros, so the K loop has no tail); the f32 master weights, the CE arithmetic (exp / log in f32 from f32
 // logits), the bias gradient and every accumulation stay f32.  d loss / d logits is written ONCE, as bf16, by the CE kernel.
 #include "sat_internal.h"
+#include "sat_ce_ls.h"
 
 namespace {
 
@@ -353,12 +354,63 @@ __global__ __launch_bounds__(256) void ce_rows_bf16grad_kernel(const float* __re
     }
 }
 
-__global__ __launch_bounds__(256) void sum_scale_b_kernel(const float* __restrict__ v, int n, float scale, float* out) {
+// ce_rows_bf16grad_kernel with label smoothing and the row's plain NLL beside its smoothed loss: ce_rows_ls_kernel's register path
+// (sat_elementwise.hip) -- the row arithmetic of both is sat_ce_ls.h's -- with the gradient leaving once, as bf16, pad columns zero.
+__global__ __launch_bounds__(256) void ce_rows_ls_bf16grad_kernel(const float* __restrict__ logits, long ldl, const int64_t* __restrict__ targets,
+                                                                  int V, float inv_denom, float eps, float* __restrict__ row_loss,
+                                                                  float* __restrict__ row_nll, bf16_t* __restrict__ grad, long ldg) {
+    __shared__ float sh[4];
+    constexpr int RC = 12;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* x = logits + (long)row * ldl;
+    const int nq = V >> 2;
+    const CeLsCoef k = ce_ls_coef(eps, V);
+    f32x4 rc[RC];
+#pragma unroll
+    for (int c = 0; c < RC; ++c)
+        if (tid + c * 256 < nq) rc[c] = *(const f32x4*)(x + 4 * (tid + c * 256));
+    const CeLsRow r = ce_ls_row_stats<RC>(rc, nq, -INFINITY, false, V, [&](float v, bool is_max) { return blk_reduce(v, is_max, sh); });
+    long tgt = targets[row];
+    tgt = tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt);
+    const int tq = (int)(tgt >> 2), te = (int)(tgt & 3);
+    bf16_t* g = grad + (long)row * ldg;
+#pragma unroll
+    for (int c = 0; c < RC; ++c) {
+        const int q = tid + c * 256;
+        if (q < nq) {
+            if (q == tq) {
+                const float nll = r.lse - rc[c][te];
+                row_loss[row] = ce_ls_loss(k, nll, r.smooth);
+                if (row_nll) row_nll[row] = nll;
+            }
+            bf16x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = (bf16_t)ce_ls_grad(k, rc[c][e], r.lse, (4 * q + e) == (int)tgt, inv_denom);
+            *(bf16x4*)(g + 4 * q) = o;
+        } else if (4 * q < ldg) {                       // pad columns [V, ldg): zeros (the K axis of the dHs product)
+            bf16x4 o = {(bf16_t)0.0f, (bf16_t)0.0f, (bf16_t)0.0f, (bf16_t)0.0f};
+            *(bf16x4*)(g + 4 * q) = o;
+        }
+    }
+}
+
+__device__ __forceinline__ void sum_scale_b_block(const float* __restrict__ v, int n, float scale, float* out) {
     __shared__ float sh[4];
     float s = 0.0f;
     for (int i = threadIdx.x; i < n; i += 256) s += v[i];
     s = blk_reduce(s, false, sh);
     if (threadIdx.x == 0) out[0] = s * scale;
+}
+
+__global__ __launch_bounds__(256) void sum_scale_b_kernel(const float* __restrict__ v, int n, float scale, float* out) {
+    sum_scale_b_block(v, n, scale, out);
+}
+
+// two such sums as one launch of two workgroups (the smoothed loss and the plain NLL), each in sum_scale_b_kernel's order
+__global__ __launch_bounds__(256) void sum_scale_b_pair_kernel(const float* __restrict__ v0, const float* __restrict__ v1, int n, float scale,
+                                                               float* out0, float* out1) {
+    if (blockIdx.x == 0) sum_scale_b_block(v0, n, scale, out0);
+    else sum_scale_b_block(v1, n, scale, out1);
 }
 
 int pad64(int x) { return (x + 63) / 64 * 64; }
@@ -471,10 +523,12 @@ extern "C" int64_t sat_vocab_bf16_ws_bytes(int N, int H, int V) { return vocab_b
 
 // models.py:53 + train.py:143 in the bf16 throughput mode: logits (f32, from bf16 operands) + mean CE; d loss / d logits is
 // left in the workspace as bf16 for sat_vocab_ce_bwd_bf16, next to the bf16 operand copies both calls share.
-extern "C" int sat_vocab_ce_fwd_bf16(const float* Hs, const float* w, const float* b, const int64_t* targets, int N, int H, int V,
-                                     float inv_denom, float* logits, int64_t ldl, float* row_loss, float* loss_out, void* workspace,
-                                     int64_t ws_bytes, sat_stream_t stream) {
+// `ls`: the label-smoothed form (sat_vocab_ce_fwd_bf16_ls: smoothing, row_nll, nll_out); else sat_vocab_ce_fwd_bf16's own kernel
+static int vocab_ce_fwd_bf16(const float* Hs, const float* w, const float* b, const int64_t* targets, int N, int H, int V,
+                             float inv_denom, bool ls, float smoothing, float* logits, int64_t ldl, float* row_loss, float* row_nll,
+                             float* loss_out, float* nll_out, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
     if (!Hs || !w || !b || !targets || !logits || !row_loss || !workspace || ldl < V || (ldl % 4)) return SAT_ERR_ARG;
+    if (ls && (!(smoothing >= 0.0f && smoothing < 1.0f) || (nll_out && !row_nll))) return SAT_ERR_ARG;      // (a NaN fails the first)
     if (!vocab_bf16_ok(N, H, V)) return SAT_ERR_UNSUPPORTED;
     const VocabWs L = vocab_ws(N, H, V);
     if (ws_bytes < L.total) return SAT_ERR_WORKSPACE;
@@ -495,14 +549,38 @@ extern "C" int sat_vocab_ce_fwd_bf16(const float* Hs, const float* w, const floa
                        (long)L.Npad, (float*)nullptr);
     SAT_LAUNCH_CHECK();
     SAT_TRY(launch_gemm(hsb, H, wb, H, logits, (long)ldl, b, N, V, H, 1, 0, s));
-    hipLaunchKernelGGL(ce_rows_bf16grad_kernel, dim3(N), dim3(256), 0, s, logits, (long)ldl, targets, V, inv_denom, row_loss, gb,
-                       (long)L.Vpad);
+    if (ls)
+        hipLaunchKernelGGL(ce_rows_ls_bf16grad_kernel, dim3(N), dim3(256), 0, s, logits, (long)ldl, targets, V, inv_denom, smoothing,
+                           row_loss, row_nll, gb, (long)L.Vpad);
+    else
+        hipLaunchKernelGGL(ce_rows_bf16grad_kernel, dim3(N), dim3(256), 0, s, logits, (long)ldl, targets, V, inv_denom, row_loss, gb,
+                           (long)L.Vpad);
     SAT_LAUNCH_CHECK();
-    if (loss_out) {
-        hipLaunchKernelGGL(sum_scale_b_kernel, dim3(1), dim3(256), 0, s, row_loss, N, inv_denom, loss_out);
+    if (!ls) nll_out = nullptr;
+    if (loss_out && nll_out) {
+        hipLaunchKernelGGL(sum_scale_b_pair_kernel, dim3(2), dim3(256), 0, s, row_loss, row_nll, N, inv_denom, loss_out, nll_out);
+        SAT_LAUNCH_CHECK();
+    } else if (loss_out || nll_out) {
+        hipLaunchKernelGGL(sum_scale_b_kernel, dim3(1), dim3(256), 0, s, loss_out ? row_loss : row_nll, N, inv_denom,
+                           loss_out ? loss_out : nll_out);
         SAT_LAUNCH_CHECK();
     }
     return SAT_OK;
+}
+
+extern "C" int sat_vocab_ce_fwd_bf16(const float* Hs, const float* w, const float* b, const int64_t* targets, int N, int H, int V,
+                                     float inv_denom, float* logits, int64_t ldl, float* row_loss, float* loss_out, void* workspace,
+                                     int64_t ws_bytes, sat_stream_t stream) {
+    return vocab_ce_fwd_bf16(Hs, w, b, targets, N, H, V, inv_denom, false, 0.0f, logits, ldl, row_loss, nullptr, loss_out, nullptr, workspace,
+                             ws_bytes, stream);
+}
+
+// the same with label smoothing (sat_ce_ls.h) and the plain NLL beside the smoothed loss; sat_vocab_ce_bwd_bf16 is its backward too
+extern "C" int sat_vocab_ce_fwd_bf16_ls(const float* Hs, const float* w, const float* b, const int64_t* targets, int N, int H, int V,
+                                        float inv_denom, float smoothing, float* logits, int64_t ldl, float* row_loss, float* row_nll,
+                                        float* loss_out, float* nll_out, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    return vocab_ce_fwd_bf16(Hs, w, b, targets, N, H, V, inv_denom, true, smoothing, logits, ldl, row_loss, row_nll, loss_out, nll_out,
+                             workspace, ws_bytes, stream);
 }
 
 // train.py:144 for the vocab projection: dW[V,H], db[V], dHs[N,H] (all f32) from the workspace sat_vocab_ce_fwd_bf16 left

@@ -14,8 +14,10 @@ LSTM_NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
 
 # the bf16 throughput mode's projection + cross entropy (train.py:143) as one call, `sat_vocab_ce_fwd_bf16`: targets i64 [N],
 # inv_denom the loss scale, row_loss f32 [N], loss_out the 1-element loss slot, ws the uint8 workspace that keeps
-# d(loss)/d(logits) (bf16) for the backward's `sat_vocab_ce_bwd_bf16`
-VocabCE = collections.namedtuple("VocabCE", "targets inv_denom row_loss loss_out ws")
+# d(loss)/d(logits) (bf16) for the backward's `sat_vocab_ce_bwd_bf16`.  smoothing > 0: label smoothing, `sat_vocab_ce_fwd_bf16_ls`, with
+# the plain NLL of the rows in row_nll f32 [N] and their scaled sum in nll_out f32 [1]; with 0 those two are not touched
+VocabCE = collections.namedtuple("VocabCE", "targets inv_denom row_loss loss_out ws smoothing row_nll nll_out",
+                                 defaults=(0.0, None, None))
 
 
 def lstm_layers(params):
@@ -246,9 +248,15 @@ def decoder_forward(lib, features, params, captions, pi, ws=None, logits=None, c
     if ce is not None:
         # bf16 throughput mode: the projection on the bf16 matrix pipe (f32 accumulate, f32 logits), CE in f32 from them,
         # d(loss)/d(logits) left as bf16 in the workspace for decoder_backward
-        L.check(lib.sat_vocab_ce_fwd_bf16(L.ptr(tapes["X"][-1]), L.ptr(lin_w), L.ptr(lin_b), L.ptr(ce.targets), N, lin_w.shape[1], V,
-                                          float(ce.inv_denom), L.ptr(logits), logits.stride(0), L.ptr(ce.row_loss),
-                                          L.ptr(ce.loss_out), L.ptr(ce.ws), ce.ws.numel(), st), "sat_vocab_ce_fwd_bf16")
+        if ce.smoothing > 0:
+            L.check(lib.sat_vocab_ce_fwd_bf16_ls(L.ptr(tapes["X"][-1]), L.ptr(lin_w), L.ptr(lin_b), L.ptr(ce.targets), N, lin_w.shape[1],
+                                                 V, float(ce.inv_denom), float(ce.smoothing), L.ptr(logits), logits.stride(0),
+                                                 L.ptr(ce.row_loss), L.ptr(ce.row_nll), L.ptr(ce.loss_out), L.ptr(ce.nll_out),
+                                                 L.ptr(ce.ws), ce.ws.numel(), st), "sat_vocab_ce_fwd_bf16_ls")
+        else:
+            L.check(lib.sat_vocab_ce_fwd_bf16(L.ptr(tapes["X"][-1]), L.ptr(lin_w), L.ptr(lin_b), L.ptr(ce.targets), N, lin_w.shape[1], V,
+                                              float(ce.inv_denom), L.ptr(logits), logits.stride(0), L.ptr(ce.row_loss),
+                                              L.ptr(ce.loss_out), L.ptr(ce.ws), ce.ws.numel(), st), "sat_vocab_ce_fwd_bf16")
     return logits, tapes
 
 

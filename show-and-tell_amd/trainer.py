@@ -16,6 +16,7 @@ as each bucket's gradients become final and overlapped with the rest of the back
 import torch
 
 from . import _lib as L
+from .criterion import _check_smoothing
 from .decoder import LSTMWorkspaces, VocabCE, decoder_backward, decoder_forward, rollout_forward
 from .models import ShowAndTell, draw_ss_seed, fc_bn1d_backward, fc_bn1d_forward
 from .pack import PackInfo
@@ -90,9 +91,17 @@ class FlatParams:
 
 
 class TrainStep:
-    """One object = model + flat optimizer state; `step()` = one train.py:126-146 iteration on this GPU."""
+    """One object = model + flat optimizer state; `step()` = one train.py:126-146 iteration on this GPU.
+    label_smoothing (keyword, and a settable attribute; 0 <= value < 1): the teacher-forced step's criterion becomes
+    nn.CrossEntropyLoss(label_smoothing=) -- `sat_ce_rows_ls` in place on the step's logits in the f32 mode, `sat_vocab_ce_fwd_bf16_ls`
+    in the bf16 mode; with 0 both modes make exactly the calls they make without it.  Scheduled sampling and dropout compose: only
+    the CE call changes.  The loss slot then holds the SMOOTHED loss; `last_nll` (1-element device tensor) holds THIS RANK's
+    inv_denom * sum of the rows' plain NLL, for a perplexity -- it is not all-reduced: in a data-parallel step inv_denom is the
+    global token count, so the ranks' values add up to the global NLL.  With label_smoothing == 0 the loss is the NLL and `last_nll`
+    is the loss slot itself (which a data-parallel step does all-reduce).  `scst_step` and `validation_step` ignore the attribute:
+    SCST weights its own rows, validation reports the plain CE of eval.py:95."""
 
-    def __init__(self, model, lr=1e-3, grad_clip=0.1, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, model, lr=1e-3, grad_clip=0.1, betas=(0.9, 0.999), eps=1e-8, label_smoothing=0.0):
         if not isinstance(model, ShowAndTell):
             raise TypeError("TrainStep drives a ShowAndTell model")
         L.require_gpu(model.decoder.linear.weight, "model")
@@ -100,6 +109,8 @@ class TrainStep:
         self.model = model
         self.flat = FlatParams(model)
         self.lr, self.grad_clip, self.betas, self.eps = lr, grad_clip, betas, eps
+        self.label_smoothing = label_smoothing
+        self.last_nll = None
         self.step_count = 0
         self.buckets = self.flat.buckets
         self.flat_grad = self.flat.grads
@@ -114,6 +125,14 @@ class TrainStep:
         # the LSTM workspaces this engine owns for good (their status words are folded into the step's fault flag)
         self.lstm_ws = LSTMWorkspaces(self.flat.params.device, watch=False)
         self._lag_ring = StatusRing(8)       # data-parallel steps: reduced fault flags in flight (_watch_fixed_lag)
+
+    @property
+    def label_smoothing(self):
+        return self._label_smoothing
+
+    @label_smoothing.setter
+    def label_smoothing(self, value):
+        self._label_smoothing = _check_smoothing(value)
 
     # -- encoder look-ahead ---------------------------------------------------------------------------
     def prefetch_encoder(self, images):
@@ -187,12 +206,18 @@ class TrainStep:
         params = dict(dec.named_parameters())
         loss_slot = flat.grads[flat.loss_slot:flat.loss_slot + 1]
         ce = mixed_ws = None
+        smoothing = self._label_smoothing
+        if smoothing > 0 and "row_nll" not in bufs:
+            bufs["row_nll"], bufs["nll"] = torch.empty(N, device=dev), torch.empty(1, device=dev)
+        self.last_nll = bufs["nll"] if smoothing > 0 else loss_slot
         if self.decoder_gemm_dtype == "bf16":
             wsb = lib.sat_vocab_bf16_ws_bytes(N, dec.hidden_size, V)
             if wsb > 0:
                 if "vocab_bf16_ws" not in bufs:
                     bufs["vocab_bf16_ws"] = torch.empty(wsb, dtype=torch.uint8, device=dev)
                 ce = VocabCE(bufs["targets"], inv_denom, bufs["row_loss"], loss_slot, bufs["vocab_bf16_ws"])
+                if smoothing > 0:
+                    ce = ce._replace(smoothing=smoothing, row_nll=bufs["row_nll"], nll_out=bufs["nll"])
             # the LSTM layers' batched GEMMs on the bf16 matrix pipe too
             if "lstm_mixed_ws" not in bufs:
                 need = max(lib.sat_lstm_mixed_ws_bytes(N, E if l == 0 else dec.hidden_size, dec.hidden_size) for l in range(dec.num_layers))
@@ -212,7 +237,12 @@ class TrainStep:
         self.last_dropped_tape = tapes["X"][-1] if dropout is not None else None
         if ss is not None:
             dec.last_ss_inputs, dec.last_ss_seed = tapes["captions"], ss[1]
-        if ce is None:
+        if ce is None and smoothing > 0:
+            # ---- smoothed loss, plain NLL + d(loss)/d(logits) in place (nn.CrossEntropyLoss(label_smoothing=)) ----
+            L.check(lib.sat_ce_rows_ls(L.ptr(logits), logits.stride(0), L.ptr(bufs["targets"]), N, V, float(inv_denom), smoothing,
+                                       L.ptr(logits), logits.stride(0), L.ptr(bufs["row_loss"]), L.ptr(bufs["row_nll"]),
+                                       L.ptr(loss_slot), L.ptr(bufs["nll"]), st), "sat_ce_rows_ls")
+        elif ce is None:
             # ---- loss + d(loss)/d(logits) in place (train.py:143) ----
             L.check(lib.sat_ce_rows(L.ptr(logits), logits.stride(0), L.ptr(bufs["targets"]), N, V, float(inv_denom), 1,
                                     L.ptr(bufs["row_loss"]), L.ptr(loss_slot), st), "sat_ce_rows")
