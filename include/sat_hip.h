@@ -1010,6 +1010,38 @@ int sat_clamp_adam_step_guarded(float* p, float* g, float* m, float* v, int64_t 
  * training the flag rides the last bucket's all-reduce(sum) and EVERY rank skips the update of a step one rank lost. */
 int sat_step_fault_flag(const void* const* status_words, int n_words, float* sticky, float* slot, sat_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Global-norm clipping (torch.nn.utils.clip_grad_norm_) + decoupled weight decay (torch.optim.AdamW) over one flat buffer
+ * (sat_optim.hip).  No atomics; every sum in one fixed order, so the results are bitwise reproducible.
+ * sat_grad_sumsq: one read of g [n] (16-byte aligned).  Writes sat_grad_sumsq_partials(n) pairs {double sumsq, double nonfinite}
+ *   -- one per workgroup; the count depends on n only, at most 768 -- at pair index partial_offset of `partials` (16-byte aligned,
+ *   room for partial_capacity pairs), so several segments of a buffer fill one array.  sumsq: f64 sum of the f64 squares of the
+ *   elements, CLAMPED to [-clip, clip] first when clip > 0 (the gradient Adam will use); nonfinite: the count of RAW elements that
+ *   are Inf or NaN.  sat_grad_sumsq_ws_bytes(n): 16 bytes per pair.
+ *   SAT_ERR_ARG before any launch: NULL or misaligned g / partials, n < 1, NaN clip, partial_offset < 0, pairs beyond the capacity.
+ * sat_adamw_step: sat_clamp_adam_step_guarded with, per element: clamp (clip > 0), g *= coef, the scaled gradient written back,
+ *   p *= 1 - lr * weight_decay unless the element lies in an exempt range, then the same Adam arithmetic.
+ *   partials != NULL (n_partials pairs, all of them summed): total = sum of sumsq, norm = sqrt(total),
+ *   coef = min(max_norm / (norm + 1e-6), 1) -- clip_grad_norm_'s clip_coef_clamped; max_norm = +inf only measures.  When any
+ *   nonfinite count is non-zero or total is not finite the WHOLE update is dropped: p, g, m, v stay bit for bit what they were.
+ *   norm_out (2 doubles, may be NULL) receives {norm, sum of the nonfinite counts} either way (not when the skip word dropped the
+ *   step).  partials == NULL: no norm, coef = 1, no non-finite check, norm_out untouched.  coef == 1, weight_decay == 0: the
+ *   bits of sat_clamp_adam_step_guarded.
+ *   exempt: HOST array of n_exempt (<= 32) pairs [lo, hi) of element offsets, sorted and disjoint, every lo a multiple of 4 (the
+ *   slices of a flat buffer start on multiples of 4: a 16-byte chunk belongs to one parameter and is exempt as a whole when its
+ *   first element lies in a range -- what follows a slice up to the next multiple of 4 is padding; the n % 4 tail elements are
+ *   looked up one by one).
+ *   SAT_ERR_ARG before any launch: NULL or misaligned buffers, n < 1, step < 1, weight_decay < 0 or NaN, more than 32 ranges, an
+ *   unsorted, overlapping or empty range, a lo that is negative or no multiple of 4, and with partials: max_norm <= 0 or NaN,
+ *   n_partials < 1. */
+int sat_grad_sumsq_partials(int64_t n);
+int64_t sat_grad_sumsq_ws_bytes(int64_t n);
+int sat_grad_sumsq(const float* g, int64_t n, float clip, double* partials, int partial_offset, int partial_capacity,
+                   sat_stream_t stream);
+int sat_adamw_step(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float clip,
+                   int step, float weight_decay, const int64_t* exempt, int n_exempt, float max_norm, const double* partials,
+                   int n_partials, double* norm_out, const float* skip_if_nonzero, sat_stream_t stream);
+
 /* column sums: out[c] = sum_r x[r*ld + c]  (bias gradients) */
 int sat_colsum_f32(const float* x, int64_t ld, int rows, int cols, float* out, sat_stream_t stream);
 /* f32 -> bf16 / bf16 -> f32 casts (weight shadow copies) */

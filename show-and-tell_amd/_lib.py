@@ -229,6 +229,10 @@ SIGNATURES = {
     "sat_clamp_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp]),
     "sat_clamp_adam_step_guarded": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp, _vp]),
     "sat_step_fault_flag": (_i, [C.POINTER(_vp), _i, _vp, _vp, _vp]),
+    "sat_grad_sumsq_partials": (_i, [_i64]),
+    "sat_grad_sumsq_ws_bytes": (_i64, [_i64]),
+    "sat_grad_sumsq": (_i, [_vp, _i64, _f, _vp, _i, _i, _vp]),
+    "sat_adamw_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f, C.POINTER(_i64), _i, _f, _vp, _i, _vp, _vp, _vp]),
     "sat_colsum_f32": (_i, [_vp, _i64, _i, _i, _vp, _vp]),
     "sat_cast_f32_bf16": (_i, [_vp, _vp, _i64, _vp]),
     "sat_cast_bf16_f32": (_i, [_vp, _vp, _i64, _vp]),
@@ -245,7 +249,8 @@ ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_at
                     "sat_rouge_l_score", "sat_sample_filtered_ws_bytes", "sat_sample_filtered", "sat_sample_decode_ws_bytes",
                     "sat_sample_decode", "sat_dropout_f32", "sat_beam_step_ex", "sat_beam_step_ex_ws_bytes", "sat_beam_rerank",
                     "sat_beam_decode_ex_ws_bytes", "sat_beam_decode_ex", "sat_beam_step_groups", "sat_beam_step_groups_ws_bytes",
-                    "sat_beam_decode_groups_ws_bytes", "sat_beam_decode_groups", "sat_ce_rows_ls", "sat_vocab_ce_fwd_bf16_ls")
+                    "sat_beam_decode_groups_ws_bytes", "sat_beam_decode_groups", "sat_ce_rows_ls", "sat_vocab_ce_fwd_bf16_ls",
+                    "sat_grad_sumsq_partials", "sat_grad_sumsq_ws_bytes", "sat_grad_sumsq", "sat_adamw_step")
 
 _lib = None
 

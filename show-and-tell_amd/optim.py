@@ -6,34 +6,112 @@ writes, `step()` / `zero_grad()` / `state_dict()` / `load_state_dict()` keep the
 `torch.optim.Adam`'s layout.  The parameters are re-homed into one flat f32 buffer (so build it AFTER `model.cuda()`), with
 flat gradient / exp_avg / exp_avg_sq twins; `step()` is `sat_clamp_adam_step` over the whole buffer -- torch's single-tensor
 Adam arithmetic in its order, elementwise clamp first when `clip` is set (then drop the separate `clip_gradient` call).
-A torch Adam over the 12 Show-Attend-Tell parameters is ~10 multi-tensor launches + 19 clamp launches per step."""
+A torch Adam over the 12 Show-Attend-Tell parameters is ~10 multi-tensor launches + 19 clamp launches per step.
+
+`max_norm=`, `weight_decay=`, `no_decay=` (keywords) turn the step into `torch.nn.utils.clip_grad_norm_(params, max_norm)` +
+`torch.optim.AdamW(..., weight_decay=)` with `no_decay` (parameter tensors, matched by identity; `no_decay_params(module)` lists
+the 1-D ones) as the group of weight decay 0: one `sat_grad_sumsq` launch over the flat gradient (after the clamp, when `clip`
+is set too), then one `sat_adamw_step`.  Nothing is read back: `last_grad_norm` is a 2-element f64 DEVICE tensor {norm, number of
+Inf / NaN gradient elements} (None until a step with `max_norm` has run; `max_norm=float("inf")` measures without clipping).
+A step whose gradient holds an Inf or NaN is DROPPED on the device -- parameters, moments and gradient stay bit for bit what they
+were -- while `step_count` still advances (the bias correction of later steps sees one step more); `last_grad_norm[1] > 0` tells.
+With `max_norm=None` and `weight_decay=0` the step makes exactly the calls it makes without the keywords."""
+import ctypes
+import math
+
 import torch
 
 from . import _lib as L
 
+MAX_EXEMPT = 32         # sat_adamw_step's table of ranges that do not decay
+
+
+def no_decay_params(module):
+    """The parameters of `module` that AdamW recipes leave out of the weight decay: the 1-D ones (biases, BatchNorm weight / bias)."""
+    return [p for p in module.parameters() if p.requires_grad and p.dim() <= 1]
+
+
+def no_decay_names(module):
+    """`no_decay_params` by name (`TrainStep.no_decay` takes names)."""
+    return [n for n, p in module.named_parameters() if p.requires_grad and p.dim() <= 1]
+
+
+def check_weight_decay(value):
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not value >= 0 or math.isinf(value):
+        raise ValueError("weight_decay must be a finite number >= 0 (got %r)" % (value,))
+    return float(value)
+
+
+def group_weight_decay(group):
+    """the weight decay of a loaded param group; torch.optim.Adam's COUPLED (L2) decay is not what the kernel computes"""
+    wd = check_weight_decay(group.get("weight_decay", 0))
+    if wd > 0 and group.get("decoupled_weight_decay", True) is False:
+        raise ValueError("the optimizer state has a coupled (L2) weight_decay; only AdamW's decoupled decay is implemented")
+    return wd
+
+
+def check_max_norm(value, what="max_norm"):
+    """a number > 0; float("inf") measures the norm without clipping"""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not value > 0:
+        raise ValueError("%s must be a number > 0 (got %r)" % (what, value))
+    return float(value)
+
+
+def merge_ranges(ranges):
+    """[(lo, hi)] element ranges of flat slices (every lo a multiple of 4) sorted, with neighbours whose padded end meets the next
+    start merged; ValueError for more than sat_adamw_step's 32"""
+    out = []
+    for lo, hi in sorted(ranges):
+        if out and L.pad4(out[-1][1]) >= lo:
+            out[-1] = (out[-1][0], max(hi, out[-1][1]))
+        else:
+            out.append((lo, hi))
+    if len(out) > MAX_EXEMPT:
+        raise ValueError("no_decay makes %d separate ranges of the flat buffer, the kernel takes %d" % (len(out), MAX_EXEMPT))
+    return out
+
+
+def exempt_array(ranges, a=0, b=None):
+    """(ctypes int64 array or None, count): `ranges` cut to the segment [a, b) of the flat buffer, relative to a"""
+    cut = [(max(lo, a) - a, (hi if b is None else min(hi, b)) - a) for lo, hi in ranges if hi > a and (b is None or lo < b)]
+    if not cut:
+        return None, 0
+    return (ctypes.c_int64 * (2 * len(cut)))(*[x for r in cut for x in r]), len(cut)
+
 
 class FusedClampAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, clip=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, clip=None, *, max_norm=None, weight_decay=0.0, no_decay=()):
         params = [p for p in params if p.requires_grad]
         if not params:
             raise ValueError("no trainable parameters")
         if any(p.dtype != torch.float32 for p in params):
             raise TypeError("FusedClampAdam holds f32 parameters")
+        self.max_norm = None if max_norm is None else check_max_norm(max_norm)
+        self.weight_decay = check_weight_decay(weight_decay)
+        ids = {id(p): i for i, p in enumerate(params)}
+        exempt = []
+        for t in no_decay:
+            if id(t) not in ids:
+                raise ValueError("a no_decay entry is not one of the optimizer's parameters")
+            exempt.append(ids[id(t)])
+        self._slices, off = [], 0
+        for p in params:
+            self._slices.append((off, p.numel()))
+            off += L.pad4(p.numel())
+        self._exempt = merge_ranges([(self._slices[i][0], sum(self._slices[i])) for i in set(exempt)])
         L.require_gpu(params[0], "parameters")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps))
         self.clip = clip
         self.lib = L.load()
         dev = params[0].device
-        self._slices, off = [], 0
-        for p in params:
-            self._slices.append((off, p.numel()))
-            off += L.pad4(p.numel())
         self.n = off
         self.flat = torch.zeros(off, device=dev)
         self.flat_grad = torch.zeros(off, device=dev)
         self.exp_avg = torch.zeros(off, device=dev)
         self.exp_avg_sq = torch.zeros(off, device=dev)
         self.step_count = 0
+        self.last_grad_norm = None
+        self._partials = None
         self._params = params
         self._views = []
         for p, (o, n) in zip(params, self._slices):
@@ -73,15 +151,42 @@ class FusedClampAdam(torch.optim.Optimizer):
             start = o + L.pad4(n)
         if start < self.n:
             segs.append((start, self.n))
-        for a, b in segs:
-            L.check(self.lib.sat_clamp_adam_step(self.flat.data_ptr() + a * 4, self.flat_grad.data_ptr() + a * 4,
-                                                 self.exp_avg.data_ptr() + a * 4, self.exp_avg_sq.data_ptr() + a * 4, b - a,
-                                                 float(g["lr"]), g["betas"][0], g["betas"][1], float(g["eps"]), clip,
-                                                 self.step_count, L.stream()), "sat_clamp_adam_step")
+        if self.max_norm is None and self.weight_decay == 0:
+            for a, b in segs:
+                L.check(self.lib.sat_clamp_adam_step(self.flat.data_ptr() + a * 4, self.flat_grad.data_ptr() + a * 4,
+                                                     self.exp_avg.data_ptr() + a * 4, self.exp_avg_sq.data_ptr() + a * 4, b - a,
+                                                     float(g["lr"]), g["betas"][0], g["betas"][1], float(g["eps"]), clip,
+                                                     self.step_count, L.stream()), "sat_clamp_adam_step")
+        elif segs:
+            self._adamw_segments(segs, g, clip)
         # the kernel wrote the parameters through raw pointers: move their version counters as an in-place torch update
         # would, so that caches keyed on `_version` (kernel-layout weight copies of a conv stack) see the step
         torch.autograd.graph.increment_version(self._params)
         return loss
+
+    def _adamw_segments(self, segs, g, clip):
+        """the step with a global norm and / or weight decay: every present segment's sum of squares into ONE array of partial pairs
+        (so the norm covers every present gradient and nothing else), then one sat_adamw_step per segment reading all of them"""
+        lib, st = self.lib, L.stream()
+        partials, total, norm_out = None, 0, None
+        if self.max_norm is not None:
+            counts = [lib.sat_grad_sumsq_partials(b - a) for a, b in segs]
+            total = sum(counts)
+            if self._partials is None or self._partials.numel() < 2 * total:
+                self._partials = torch.empty(2 * total, dtype=torch.float64, device=self.flat.device)
+            if self.last_grad_norm is None:
+                self.last_grad_norm = torch.zeros(2, dtype=torch.float64, device=self.flat.device)
+            partials, norm_out, off = self._partials.data_ptr(), self.last_grad_norm.data_ptr(), 0
+            for (a, b), c in zip(segs, counts):
+                L.check(lib.sat_grad_sumsq(self.flat_grad.data_ptr() + a * 4, b - a, clip, partials, off, total, st), "sat_grad_sumsq")
+                off += c
+        for a, b in segs:
+            ex, nex = exempt_array(self._exempt, a, b) if self.weight_decay > 0 else (None, 0)
+            L.check(lib.sat_adamw_step(self.flat.data_ptr() + a * 4, self.flat_grad.data_ptr() + a * 4,
+                                       self.exp_avg.data_ptr() + a * 4, self.exp_avg_sq.data_ptr() + a * 4, b - a,
+                                       float(g["lr"]), g["betas"][0], g["betas"][1], float(g["eps"]), clip, self.step_count,
+                                       self.weight_decay, ex, nex, self.max_norm or 0.0, partials, total, norm_out, None, st),
+                    "sat_adamw_step")
 
     def state_dict(self):
         state = {}
@@ -91,10 +196,11 @@ class FusedClampAdam(torch.optim.Optimizer):
                             "exp_avg": self.exp_avg[o:o + n].view(p.shape).clone(),
                             "exp_avg_sq": self.exp_avg_sq[o:o + n].view(p.shape).clone()}
         g = self.param_groups[0]
-        group = {"lr": g["lr"], "betas": tuple(g["betas"]), "eps": g["eps"], "weight_decay": 0, "amsgrad": False, "maximize": False,
-                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
-                 "params": list(range(len(self._params)))}
-        return {"state": state, "param_groups": [group], "grad_clip": self.clip}
+        wd = self.weight_decay
+        group = {"lr": g["lr"], "betas": tuple(g["betas"]), "eps": g["eps"], "weight_decay": wd if wd > 0 else 0, "amsgrad": False,
+                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                 "decoupled_weight_decay": wd > 0, "params": list(range(len(self._params)))}
+        return {"state": state, "param_groups": [group], "grad_clip": self.clip, "max_grad_norm": self.max_norm}
 
     def load_state_dict(self, sd):
         group = sd["param_groups"][0]
@@ -102,6 +208,10 @@ class FusedClampAdam(torch.optim.Optimizer):
             raise ValueError("optimizer state has %d parameters, this optimizer %d" % (len(group["params"]), len(self._params)))
         g = self.param_groups[0]
         g["lr"], g["betas"], g["eps"] = float(group["lr"]), tuple(group["betas"]), float(group["eps"])
+        self.weight_decay = group_weight_decay(group)
+        if "max_grad_norm" in sd:
+            off = sd["max_grad_norm"] is None or sd["max_grad_norm"] == 0          # (0.0: TrainStep's "off")
+            self.max_norm = None if off else check_max_norm(sd["max_grad_norm"])
         self.exp_avg.zero_()
         self.exp_avg_sq.zero_()
         steps = set()

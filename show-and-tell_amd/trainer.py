@@ -19,6 +19,7 @@ from . import _lib as L
 from .criterion import _check_smoothing
 from .decoder import LSTMWorkspaces, VocabCE, decoder_backward, decoder_forward, rollout_forward
 from .models import ShowAndTell, draw_ss_seed, fc_bn1d_backward, fc_bn1d_forward
+from .optim import check_max_norm, check_weight_decay, exempt_array, group_weight_decay, merge_ranges
 from .pack import PackInfo
 from .scst import SelfCritical, ce_rows_weighted, scst_weights
 from .watch import ResidencyWatch, StatusRing
@@ -133,6 +134,61 @@ class TrainStep:
     @label_smoothing.setter
     def label_smoothing(self, value):
         self._label_smoothing = _check_smoothing(value)
+
+    # -- global-norm clipping and decoupled weight decay (attributes, not constructor arguments) ---------------------------------
+    # max_grad_norm: torch.nn.utils.clip_grad_norm_'s max_norm over the whole flat gradient (after the bucket all-reduces in a
+    #   data-parallel step, after the elementwise clamp when grad_clip is set); 0.0 = off, float("inf") = measure only.
+    # weight_decay: torch.optim.AdamW's (p *= 1 - lr * weight_decay in front of the Adam arithmetic); 0.0 = off.
+    # no_decay: NAMES from `flat.slices` that do not decay (`no_decay_names(model)`: biases, BatchNorm weight / bias); None decays
+    #   every parameter, which is what torch does with one param group.
+    # last_grad_norm: 2-element f64 DEVICE tensor {norm, number of Inf / NaN gradient elements} of the last step with max_grad_norm
+    #   set, None before.  A step with a non-finite gradient is dropped on the device with no host read, like a faulted one:
+    #   parameters, moments and gradient stay what they were.  step_count still advances -- the bias correction of the following
+    #   steps sees one step more -- and `last_grad_norm[1] > 0`, read whenever the loop likes, is how it finds out.
+    # With max_grad_norm and weight_decay both off `optimizer_step` makes exactly the call it makes without them.
+    _max_grad_norm, _weight_decay, _no_decay, _exempt = 0.0, 0.0, None, None
+    last_grad_norm = None
+
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        off = not isinstance(value, bool) and isinstance(value, (int, float)) and value == 0
+        self._max_grad_norm = 0.0 if off else check_max_norm(value, "max_grad_norm")
+
+    @property
+    def weight_decay(self):
+        return self._weight_decay
+
+    @weight_decay.setter
+    def weight_decay(self, value):
+        self._weight_decay = check_weight_decay(value)
+
+    @property
+    def no_decay(self):
+        return self._no_decay
+
+    @no_decay.setter
+    def no_decay(self, names):
+        if names is not None:
+            if isinstance(names, (str, bytes)) or not hasattr(names, "__iter__"):
+                raise ValueError("no_decay takes parameter NAMES (an iterable of str), or None")
+            names = tuple(names)
+            if not all(isinstance(n, str) for n in names):
+                raise ValueError("no_decay takes parameter NAMES (an iterable of str), or None")
+        # an engine made without __init__ has no flat buffer yet: the names are then checked by the first optimizer_step
+        exempt = self._ranges_of(names) if getattr(self, "flat", None) is not None else None
+        self._no_decay, self._exempt = names, exempt
+
+    def _ranges_of(self, names):
+        """the flat buffer's ranges of `names`, merged and checked against the kernel's table (ValueError)"""
+        slices = self.flat.slices
+        unknown = [n for n in names or () if n not in slices]
+        if unknown:
+            raise ValueError("no_decay: %s are not parameters of the flat buffer (%s)" % (unknown, sorted(slices)))
+        return merge_ranges([(slices[n][0], slices[n][0] + slices[n][1]) for n in set(names or ())])
 
     # -- encoder look-ahead ---------------------------------------------------------------------------
     def prefetch_encoder(self, images):
@@ -391,16 +447,38 @@ class TrainStep:
         before = self.step_count
         self.step_count += 1
         f = self.flat
-        L.check(self.lib.sat_clamp_adam_step_guarded(L.ptr(f.params), L.ptr(f.grads), L.ptr(f.m), L.ptr(f.v), f.n,
-                                                     float(self.lr if lr is None else lr), self.betas[0], self.betas[1],
-                                                     self.eps, float(self.grad_clip), self.step_count, L.ptr(self.fault_slot),
-                                                     L.stream()), "sat_clamp_adam_step_guarded")
+        if self._max_grad_norm == 0 and self._weight_decay == 0:
+            L.check(self.lib.sat_clamp_adam_step_guarded(L.ptr(f.params), L.ptr(f.grads), L.ptr(f.m), L.ptr(f.v), f.n,
+                                                         float(self.lr if lr is None else lr), self.betas[0], self.betas[1],
+                                                         self.eps, float(self.grad_clip), self.step_count, L.ptr(self.fault_slot),
+                                                         L.stream()), "sat_clamp_adam_step_guarded")
+        else:
+            self._adamw_step(float(self.lr if lr is None else lr))
         torch.autograd.graph.increment_version(self._params_list)     # written through raw pointers: bump `_version` like torch would
         if fixed_lag is not None:
             self._watch_fixed_lag(before, int(fixed_lag))
             return
         ResidencyWatch.get(f.params.device).submit(self.fault_slot.view(torch.int32), "a persistent LSTM recurrence of a training step",
                                                    lambda: self._on_fault(before), note=self.FAULT_NOTE)
+
+    def _adamw_step(self, lr):
+        """the update with a global norm and / or weight decay: the sum of squares over the n parameter gradients -- the loss and
+        fault slots behind them are no gradients and stay out --, then sat_adamw_step behind the same fault word; it drops the
+        update by itself when the gradient holds an Inf or NaN (see `last_grad_norm`)"""
+        f, lib, st = self.flat, self.lib, L.stream()
+        if self._exempt is None:
+            self._exempt = self._ranges_of(self._no_decay)
+        partials, count, norm_out = None, 0, None
+        if self._max_grad_norm > 0:
+            if getattr(self, "_norm_ws", None) is None:
+                self._norm_ws = torch.empty(lib.sat_grad_sumsq_ws_bytes(f.n) // 8, dtype=torch.float64, device=f.params.device)
+                self.last_grad_norm = torch.zeros(2, dtype=torch.float64, device=f.params.device)
+            partials, count, norm_out = L.ptr(self._norm_ws), lib.sat_grad_sumsq_partials(f.n), L.ptr(self.last_grad_norm)
+            L.check(lib.sat_grad_sumsq(L.ptr(f.grads), f.n, float(self.grad_clip), partials, 0, count, st), "sat_grad_sumsq")
+        ex, nex = exempt_array(self._exempt) if self._weight_decay > 0 else (None, 0)
+        L.check(lib.sat_adamw_step(L.ptr(f.params), L.ptr(f.grads), L.ptr(f.m), L.ptr(f.v), f.n, lr, self.betas[0], self.betas[1],
+                                   self.eps, float(self.grad_clip), self.step_count, self._weight_decay, ex, nex,
+                                   self._max_grad_norm, partials, count, norm_out, L.ptr(self.fault_slot), st), "sat_adamw_step")
 
     # -- optimizer checkpoint interchange (SURVEY 8f.4; the reference's load_optimizer is an empty stub, ------
     #    train.py:60-64, and only model.state_dict() is saved, train.py:191-193) ---------------------------
@@ -419,10 +497,12 @@ class TrainStep:
                 state[i] = {"step": torch.tensor(float(self.step_count)),
                             "exp_avg": f.m[o:o + n].view(shape).clone(),
                             "exp_avg_sq": f.v[o:o + n].view(shape).clone()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False,
+        wd = self._weight_decay
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": wd if wd > 0 else 0, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-                 "decoupled_weight_decay": False, "params": list(range(len(names)))}
-        return {"state": state, "param_groups": [group], "param_names": names, "grad_clip": self.grad_clip}
+                 "decoupled_weight_decay": wd > 0, "params": list(range(len(names)))}
+        return {"state": state, "param_groups": [group], "param_names": names, "grad_clip": self.grad_clip,
+                "max_grad_norm": self._max_grad_norm}
 
     def load_optimizer_state_dict(self, sd):
         f, trainable = self.flat, self._trainable()
@@ -431,6 +511,9 @@ class TrainStep:
             raise ValueError("optimizer state has %d parameters, model has %d trainable"
                              % (len(group["params"]), len(trainable)))
         self.lr, self.betas, self.eps = float(group["lr"]), tuple(group["betas"]), float(group["eps"])
+        self.weight_decay = group_weight_decay(group)
+        if "max_grad_norm" in sd:
+            self.max_grad_norm = 0.0 if sd["max_grad_norm"] is None else sd["max_grad_norm"]     # (None: FusedClampAdam's "off")
         steps = set()
         f.m.zero_()
         f.v.zero_()
