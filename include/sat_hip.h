@@ -691,6 +691,58 @@ int sat_beam_decode_groups(const float* features /*[B,E]*/, const float* embed /
                            int64_t end_id, const sat_beam_constraints* c /*[host], nullable*/, int num_groups, float diversity_penalty,
                            int64_t* ids, float* scores, float* norm_scores, int32_t* order, void* workspace, int64_t ws_bytes,
                            sat_stream_t stream);
+/* Ensemble decode (added within ABI 18): a beam search over the mixed distribution of M models (the ensembles of several checkpoints
+ * that Show-and-Tell and the self-critical paper report).  ONE kernel in front of the unchanged selection kernels.
+ * sat_ensemble_logprobs: logits is a HOST array of M device pointers, each an [R][ldl] f32 matrix of one model's logits; out [R][ldo]
+ *   receives one row of combined log-probabilities per input row.  lse_m = the log-sum-exp of model m's row over all V columns;
+ *   w_m = weights[m] / sum(weights), normalised on the host in double and rounded once to f32 (weights NULL: uniform, 1 / M).
+ *   mode 0 (probability mean, the usual captioning ensemble): out[v] = log(sum_m w_m * exp(x_m[v] - lse_m)), evaluated as
+ *     a_m = x_m[v] - lse_m + log w_m, out = max_m a_m + log(sum_m exp(a_m - max)).
+ *   mode 1 (log-probability mean, a product of experts): out[v] = sum_m w_m * (x_m[v] - lse_m), summed in model order; NOT
+ *     renormalised here -- the selection kernels subtract the row's lse anyway.
+ *   1 <= M <= 8; the pointers reach the kernel by value, there is no device-side pointer table.  A -inf column gives -inf in mode 0
+ *   only if every model has -inf there, in mode 1 if any model has (no NaN from 0 * inf).  A row that is all -inf in some model is
+ *   undefined (sat_beam_step's rule).  Columns V .. ldo-1 of out are not written.  Any ldl >= V and ldo >= V, odd ones included:
+ *   alignment only selects between the 16-byte path (ldl % 4 == 0, ldo % 4 == 0, every base 16-byte aligned) and the scalar path
+ *   and never changes a value.  out may not alias an input.  No allocation, no host sync: the call is capturable.
+ *   The result goes unchanged into sat_beam_step, sat_beam_step_ex, sat_beam_step_groups and sat_sample_filtered as their `logits`.
+ *   In mode 0 the lse those kernels subtract is 0 up to rounding.  The `scores` of an ensemble hypothesis are the sum of
+ *   log_softmax(out) as the step kernel forms it.
+ *   SAT_ERR_ARG before any launch: a NULL pointer; M outside 1..8; mode not 0 or 1; R or V <= 0; ldl < V or ldo < V; a weight that is
+ *   not finite or is <= 0; out equal to an input.
+ * sat_beam_decode_ensemble: sat_beam_decode_groups's loop for M DecoderRNN models in lock step.  models is a HOST array of M structs
+ *   of device pointers (lstm_w: a host array of 4 * num_layers device pointers, as above).  The models share V; they may differ in
+ *   E, H, num_layers and features (every model has its own encoder).  Per step and model: sat_lstm_step per layer on the R = B*K
+ *   rows and sat_vocab_logits_fwd (exact f32) into the model's own [R][pad4(V)] matrix; then the combine, the row launch and the
+ *   merge launch of sat_beam_decode_groups on the combined matrix (the plain, ban and group variants as there), and per model the
+ *   embedding rows of the chosen tokens and the (h, c) re-ordering by parent.  Backtrack, and the rerank under a length penalty or
+ *   with G > 1, as there.  K = 1 is the greedy ensemble decode.  A model with ONE layer takes sat_beam_decode's wide step from 128
+ *   rows on -- the gates as one split-K exact-f32 GEMM over [x | h], and for V % 4 == 0 the projection from a three-way bf16 split
+ *   (f32 accuracy, not the f32 pipe's bit pattern) -- and one launch then moves its embedding rows and (h, c).  The kernels that
+ *   run are a function of the shapes alone: the same inputs give the same bits in every process.
+ *   ids [B][K][steps], scores / norm_scores / order [B][K] (nullable) as sat_beam_decode_groups.  workspace:
+ *   sat_beam_decode_ensemble_ws_bytes (0 for arguments the call refuses), 256-byte aligned.
+ *   Errors, before anything is enqueued: those of sat_beam_decode_groups and of sat_ensemble_logprobs's (M, weights, mode);
+ *   SAT_ERR_ARG for a NULL field or a non-positive size in a model; SAT_ERR_UNSUPPORTED for a model with E % 4 != 0, H % 4 != 0 or
+ *   more than 8 layers. */
+typedef struct {
+    const float* features;         /* [B][E] */
+    const float* embed;            /* [V][E] */
+    const float* const* lstm_w;    /* HOST array of 4 * num_layers device pointers (w_ih, w_hh, b_ih, b_hh per layer) */
+    int num_layers;
+    const float* lin_w;            /* [V][H] */
+    const float* lin_b;            /* [V] */
+    int E;
+    int H;
+} sat_decoder_model;               /* host struct, device pointers */
+int sat_ensemble_logprobs(const float* const* logits /*[host] M device pointers, each [R][ldl]*/, int M, int64_t ldl,
+                          const float* weights /*[host] M, or NULL = uniform*/, int mode, int R, int V, float* out /*[R][ldo]*/,
+                          int64_t ldo, sat_stream_t stream);
+int64_t sat_beam_decode_ensemble_ws_bytes(const sat_decoder_model* models /*[host]*/, int M, int B, int K, int V, int steps);
+int sat_beam_decode_ensemble(const sat_decoder_model* models /*[host]*/, int M, const float* weights /*[host] M or NULL*/, int mode,
+                             int B, int K, int V, int steps, int64_t end_id, const sat_beam_constraints* c /*[host], nullable*/,
+                             int num_groups, float diversity_penalty, int64_t* ids, float* scores, float* norm_scores, int32_t* order,
+                             void* workspace, int64_t ws_bytes, sat_stream_t stream);
 /* Scheduled sampling (the reference's DecoderRNN.ss_prob, models.py:38, and its schedule, train.py:109-113) in the training forward.
  * Random numbers: Philox4x32-10, key (seed & 0xffffffff, seed >> 32), u = ((x >> 8) + 0.5) * 2^-24.  The draw for row b of step t is
  * s(b, t) = first argmax_v (logit[b][v] + G(b, t, v)), G = -log(-log u) of counter (v >> 2, b, t, 2*rank), word v & 3 (Gumbel-max: an

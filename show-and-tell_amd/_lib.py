@@ -56,6 +56,12 @@ class SatBeamConstraints(C.Structure):
                 ("block_repeat", C.c_int), ("length_penalty", C.c_float)]
 
 
+class SatDecoderModel(C.Structure):
+    """mirror of `sat_decoder_model` (include/sat_hip.h): one DecoderRNN of an ensemble, host struct of device pointers"""
+    _fields_ = [("features", _vp), ("embed", _vp), ("lstm_w", C.POINTER(_vp)), ("num_layers", C.c_int), ("lin_w", _vp), ("lin_b", _vp),
+                ("E", C.c_int), ("H", C.c_int)]
+
+
 class SatOp(C.Structure):
     """mirror of `struct sat_op` (include/sat_hip.h); no instance attributes besides the fields, so a misspelt field raises"""
     __slots__ = ()
@@ -195,6 +201,10 @@ SIGNATURES = {
     "sat_beam_decode_groups_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
     "sat_beam_decode_groups": (_i, [_vp, _vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, C.POINTER(SatBeamConstraints),
                                     _i, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sat_ensemble_logprobs": (_i, [C.POINTER(_vp), _i, _i64, C.POINTER(_f), _i, _i, _i, _vp, _i64, _vp]),
+    "sat_beam_decode_ensemble_ws_bytes": (_i64, [C.POINTER(SatDecoderModel), _i, _i, _i, _i, _i]),
+    "sat_beam_decode_ensemble": (_i, [C.POINTER(SatDecoderModel), _i, C.POINTER(_f), _i, _i, _i, _i, _i, _i64,
+                                      C.POINTER(SatBeamConstraints), _i, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sat_greedy_decode": (_i, [_vp, _vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "sat_ss_decoder_fwd_ws_bytes": (_i64, [_i, _i]),
     "sat_vocab_sample": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i64, _f, C.c_uint64, _i, _i, _vp, _i64, _vp, _i64, _vp, _i, _vp,
@@ -250,7 +260,8 @@ ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_at
                     "sat_sample_decode", "sat_dropout_f32", "sat_beam_step_ex", "sat_beam_step_ex_ws_bytes", "sat_beam_rerank",
                     "sat_beam_decode_ex_ws_bytes", "sat_beam_decode_ex", "sat_beam_step_groups", "sat_beam_step_groups_ws_bytes",
                     "sat_beam_decode_groups_ws_bytes", "sat_beam_decode_groups", "sat_ce_rows_ls", "sat_vocab_ce_fwd_bf16_ls",
-                    "sat_grad_sumsq_partials", "sat_grad_sumsq_ws_bytes", "sat_grad_sumsq", "sat_adamw_step")
+                    "sat_grad_sumsq_partials", "sat_grad_sumsq_ws_bytes", "sat_grad_sumsq", "sat_adamw_step",
+                    "sat_ensemble_logprobs", "sat_beam_decode_ensemble_ws_bytes", "sat_beam_decode_ensemble")
 
 _lib = None
 

@@ -1168,3 +1168,449 @@ extern "C" int sat_greedy_decode(const float* features, const float* embed, cons
     }
     return stack.finish();
 }
+
+// ---- ENSEMBLE decode (include/sat_hip.h, sat_ensemble_logprobs): M models' logits rows -> ONE row of combined log-probabilities,
+//      which the selection kernels above take as they take a model's logits.  One workgroup of 256 threads per row, two passes over
+//      the M rows (the second finds them in L2 / MALL: a row of 10 000 columns is 40 KB per model):
+//        pass 1  per model an ONLINE (max, sum) per thread -- one rescale per 16-byte chunk, not per element -- reduced over the wave
+//                by __shfl_xor and over the four waves through 2 * M * 4 floats of LDS: lse_m = max + log(sum);
+//        pass 2  out[v] from the M values of column v (mode 0: max_m a_m + log sum_m exp(a_m - max), a_m = x_m[v] - lse_m + log w_m;
+//                mode 1: sum_m w_m (x_m[v] - lse_m) in model order).
+//      exp as ONE fma and ONE v_exp_f32 (beam_row_body's form); the pointers and weights reach the kernel by value.  M is a template
+//      argument so that every per-model array is indexed by unrolled constants and lives in registers. ----
+namespace {
+
+constexpr int kEnsMax = 8;
+struct EnsArgs {
+    const float* x[kEnsMax];
+    float w[kEnsMax], logw[kEnsMax];
+};
+constexpr float kLog2e = 1.44269504088896340736f;
+
+// exp(x - m) for x <= m; m == -inf (nothing seen yet) counts as 0, so that exp(-inf - m) is 0 and never NaN
+__device__ __forceinline__ float ens_exp(float x, float m) {
+    const float mm = m == -INFINITY ? 0.0f : m;
+    return __builtin_amdgcn_exp2f(__builtin_fmaf(x, kLog2e, -mm * kLog2e));
+}
+// (m, s) <- (m, s) + (om, os): the sums rescaled to the larger maximum
+__device__ __forceinline__ void ens_join(float& m, float& s, float om, float os) {
+    const float nm = fmaxf(m, om);
+    s = s * ens_exp(m, nm) + os * ens_exp(om, nm);
+    m = nm;
+}
+template <bool VEC>
+__device__ __forceinline__ f32x4 ens_load4(const float* p) {
+    if constexpr (VEC) return *(const f32x4*)p;
+    else return (f32x4){p[0], p[1], p[2], p[3]};
+}
+
+template <int M, bool VEC>
+__global__ __launch_bounds__(256) void ensemble_logprobs_kernel(EnsArgs a, long ldl, int mode, int V, float* __restrict__ out, long ldo) {
+    __shared__ float s_m[4][M], s_s[4][M];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nq = V >> 2, tail = (nq << 2) + tid;           // whole 4-column chunks; V % 4 leftover columns, one per thread
+    const float* x[M];
+#pragma unroll
+    for (int j = 0; j < M; ++j) x[j] = a.x[j] + (long)row * ldl;
+    float m[M], s[M];
+#pragma unroll
+    for (int j = 0; j < M; ++j) { m[j] = -INFINITY; s[j] = 0.0f; }
+    for (int q = tid; q < nq; q += 256) {
+        f32x4 v[M];
+#pragma unroll
+        for (int j = 0; j < M; ++j) v[j] = ens_load4<VEC>(x[j] + 4 * q);      // M loads in flight
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            const float cm = fmaxf(fmaxf(v[j][0], v[j][1]), fmaxf(v[j][2], v[j][3]));
+            if (cm > m[j]) { s[j] *= ens_exp(m[j], cm); m[j] = cm; }
+            s[j] += (ens_exp(v[j][0], m[j]) + ens_exp(v[j][1], m[j])) + (ens_exp(v[j][2], m[j]) + ens_exp(v[j][3], m[j]));
+        }
+    }
+    if (tail < V) {
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            const float xv = x[j][tail];
+            if (xv > m[j]) { s[j] *= ens_exp(m[j], xv); m[j] = xv; }
+            s[j] += ens_exp(xv, m[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ens_join(m[j], s[j], __shfl_xor(m[j], o, 64), __shfl_xor(s[j], o, 64));
+        if (lane == 0) { s_m[wave][j] = m[j]; s_s[wave][j] = s[j]; }
+    }
+    __syncthreads();
+    float lse[M];
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        float bm = s_m[0][j], bs = s_s[0][j];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) ens_join(bm, bs, s_m[w][j], s_s[w][j]);      // wave order: fixed
+        lse[j] = bm + logf(bs);
+    }
+    auto combine = [&](const float (&xv)[M]) -> float {
+        if (mode == 0) {
+            float av[M], mx = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < M; ++j) { av[j] = (xv[j] - lse[j]) + a.logw[j]; mx = fmaxf(mx, av[j]); }
+            if (mx == -INFINITY) return -INFINITY;           // every model has -inf here
+            float sum = 0.0f;
+#pragma unroll
+            for (int j = 0; j < M; ++j) sum += __builtin_amdgcn_exp2f((av[j] - mx) * kLog2e);
+            return mx + logf(sum);
+        }
+        float acc = 0.0f;
+        bool dead = false;
+#pragma unroll
+        for (int j = 0; j < M; ++j) { dead |= xv[j] == -INFINITY; acc += a.w[j] * (xv[j] - lse[j]); }
+        return dead ? -INFINITY : acc;                       // (a weight that rounds to 0: no 0 * inf)
+    };
+    float* o = out + (long)row * ldo;
+    for (int q = tid; q < nq; q += 256) {
+        f32x4 v[M];
+#pragma unroll
+        for (int j = 0; j < M; ++j) v[j] = ens_load4<VEC>(x[j] + 4 * q);
+        f32x4 r;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float xv[M];
+#pragma unroll
+            for (int j = 0; j < M; ++j) xv[j] = v[j][e];
+            r[e] = combine(xv);
+        }
+        if constexpr (VEC) *(f32x4*)(o + 4 * q) = r;
+        else { o[4 * q] = r[0]; o[4 * q + 1] = r[1]; o[4 * q + 2] = r[2]; o[4 * q + 3] = r[3]; }
+    }
+    if (tail < V) {
+        float xv[M];
+#pragma unroll
+        for (int j = 0; j < M; ++j) xv[j] = x[j][tail];
+        o[tail] = combine(xv);
+    }
+}
+
+template <int M>
+void ensemble_launch_m(hipStream_t s, const EnsArgs& a, long ldl, int mode, int R, int V, float* out, long ldo, bool vec) {
+    if (vec) hipLaunchKernelGGL((ensemble_logprobs_kernel<M, true>), dim3((unsigned)R), dim3(256), 0, s, a, ldl, mode, V, out, ldo);
+    else hipLaunchKernelGGL((ensemble_logprobs_kernel<M, false>), dim3((unsigned)R), dim3(256), 0, s, a, ldl, mode, V, out, ldo);
+}
+
+// the checks of both ensemble entry points on (M, weights, mode), and the weights as the kernel takes them: normalised in double,
+// rounded once to f32 (w) and their logarithm likewise (logw); weights NULL: uniform
+int ensemble_weights(int M, const float* weights, int mode, EnsArgs* a) {
+    if (M < 1 || M > kEnsMax || (mode != 0 && mode != 1)) return SAT_ERR_ARG;
+    double sum = 0.0;
+    for (int j = 0; j < M; ++j) {
+        const float w = weights ? weights[j] : 1.0f;
+        if (!(w > 0.0f) || w == INFINITY) return SAT_ERR_ARG;
+        sum += (double)w;
+    }
+    for (int j = 0; j < kEnsMax; ++j) {
+        const double wn = j < M ? (double)(weights ? weights[j] : 1.0f) / sum : 0.0;
+        a->w[j] = (float)wn;
+        a->logw[j] = j < M ? (float)log(wn) : 0.0f;
+        a->x[j] = nullptr;
+    }
+    return SAT_OK;
+}
+
+// the launch; the 16-byte path where every row of every matrix is 16-byte aligned, the scalar path otherwise (same values up to
+// nothing: both paths do the same arithmetic in the same order)
+void ensemble_launch(hipStream_t s, const EnsArgs& a, int M, long ldl, int mode, int R, int V, float* out, long ldo) {
+    bool vec = !(ldl & 3) && !(ldo & 3) && !(((uintptr_t)out) & 15);
+    for (int j = 0; j < M; ++j) vec = vec && !(((uintptr_t)a.x[j]) & 15);
+    switch (M) {
+        case 1: ensemble_launch_m<1>(s, a, ldl, mode, R, V, out, ldo, vec); break;
+        case 2: ensemble_launch_m<2>(s, a, ldl, mode, R, V, out, ldo, vec); break;
+        case 3: ensemble_launch_m<3>(s, a, ldl, mode, R, V, out, ldo, vec); break;
+        case 4: ensemble_launch_m<4>(s, a, ldl, mode, R, V, out, ldo, vec); break;
+        case 5: ensemble_launch_m<5>(s, a, ldl, mode, R, V, out, ldo, vec); break;
+        case 6: ensemble_launch_m<6>(s, a, ldl, mode, R, V, out, ldo, vec); break;
+        case 7: ensemble_launch_m<7>(s, a, ldl, mode, R, V, out, ldo, vec); break;
+        default: ensemble_launch_m<8>(s, a, ldl, mode, R, V, out, ldo, vec); break;
+    }
+}
+
+}  // namespace
+
+extern "C" int sat_ensemble_logprobs(const float* const* logits, int M, int64_t ldl, const float* weights, int mode, int R, int V,
+                                     float* out, int64_t ldo, sat_stream_t stream) {
+    if (!logits || !out || R <= 0 || V <= 0 || ldl < V || ldo < V) return SAT_ERR_ARG;
+    EnsArgs a;
+    SAT_TRY(ensemble_weights(M, weights, mode, &a));
+    for (int j = 0; j < M; ++j) {
+        if (!logits[j] || logits[j] == out) return SAT_ERR_ARG;
+        a.x[j] = logits[j];
+    }
+    ensemble_launch((hipStream_t)stream, a, M, (long)ldl, mode, R, V, out, (long)ldo);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
+// ---- the beam decode of an ENSEMBLE of DecoderRNN models as ONE call: beam_decode_impl's loop with M decoder states in lock step.
+//      Per step and model: the LSTM stack step and the vocab projection into the model's own [R][pad4(V)] matrix (narrow: sat_lstm_step
+//      per layer and the exact-f32 projection; wide: see ensemble_wide); then ONE combine launch, the row launch and the merge launch
+//      on the combined matrix -- the plain, ban and group variants as beam_decode_impl chooses them -- and per model the embedding
+//      rows of the chosen tokens and the (h, c) re-ordering.  Which kernels run is a function of the shapes alone. ----
+static int ensemble_models_check(const sat_decoder_model* models, int M) {
+    if (!models || M < 1 || M > kEnsMax) return SAT_ERR_ARG;
+    bool unsupported = false;                                  // (an argument error anywhere comes in front of it)
+    for (int j = 0; j < M; ++j) {
+        const sat_decoder_model& d = models[j];
+        if (!d.features || !d.embed || !d.lstm_w || !d.lin_w || !d.lin_b || d.E <= 0 || d.H <= 0 || d.num_layers < 1) return SAT_ERR_ARG;
+        unsupported = unsupported || d.num_layers > 8 || (d.E & 3) || (d.H & 3);      // (sat_lstm_step's 16-byte rows)
+        for (int i = 0; i < 4 * (d.num_layers > 8 ? 8 : d.num_layers); ++i)
+            if (!d.lstm_w[i]) return SAT_ERR_ARG;
+    }
+    return unsupported ? SAT_ERR_UNSUPPORTED : SAT_OK;
+}
+
+// A member takes beam_decode_impl's WIDE step where that loop does -- one LSTM layer and >= 128 rows: the gates as ONE split-K
+// exact-f32 GEMM over [x | h] plus the pointwise launch, and the projection on the bf16 pipe from a three-way split where V % 4 == 0
+// (measured at 320 rows, E 256, H 512, V 10 000, 20 steps: 1.7 ms per member on the narrow path, ~1.0 on this one;
+// profiles/ensemble_bench.txt).  A function of the member's shape and the row count alone.
+static bool ensemble_wide(const sat_decoder_model& d, int64_t R) { return d.num_layers == 1 && R >= 128; }
+static bool ensemble_x3(const sat_decoder_model& d, int64_t R, int V) {
+    return ensemble_wide(d, R) && !(V & 3) && sat_gemm_f32x3_packed_bytes(V, d.H) > 0;
+}
+// the K-split of the wide gate GEMM: beam_decode_impl's rule (enough slices to fill the chip's ~512 workgroup slots)
+static int ensemble_ksplit(int64_t R, int H, long ldx) {
+    const long tiles = (long)sat_cdiv((int)R, 64) * sat_cdiv(4 * H, 64);
+    int ksplit = (int)(512 / (tiles > 0 ? tiles : 1));
+    const int nk = sat_cdiv((int)ldx, 32);
+    if (ksplit > nk / 4) ksplit = nk / 4;
+    if (ksplit > kBeamKSplitMax) ksplit = kBeamKSplitMax;
+    return ksplit < 1 ? 1 : ksplit;
+}
+
+// a model's own part of the workspace: (h, c) of every layer twice and its logits matrix; narrow: the step-0 input rows and the
+// embedding rows; wide: two [R][E + H] input rows, W_cat, the gate slabs and the split projection weights
+static int64_t ensemble_model_bytes(const sat_decoder_model& d, int64_t R, int64_t ldl, int V) {
+    int64_t n = al256(4 * (int64_t)d.num_layers * R * d.H * 4) + al256(R * ldl * 4);
+    if (!ensemble_wide(d, R)) return n + 2 * al256(R * d.E * 4);
+    n += 2 * al256(R * (int64_t)(d.E + d.H) * 4) + al256(4 * (int64_t)d.H * (d.E + d.H) * 4) + al256(kBeamKSplitMax * R * 4 * (int64_t)d.H * 4);
+    return n + (ensemble_x3(d, R, V) ? al256(sat_gemm_f32x3_packed_bytes(V, d.H)) : 0);
+}
+
+// what beam_merge_kernel's second half does for the model whose rows it moves, for ANY model of an ensemble: one workgroup per image
+// reads the step's (parent, token) records and moves the embedding rows of the chosen tokens and the (h, c) rows they extend
+__global__ __launch_bounds__(256) void ensemble_move_rows_kernel(const int* __restrict__ parent, const int64_t* __restrict__ token, int K,
+                                                                 const float* __restrict__ embed, int E, float* __restrict__ x_next, long ldx,
+                                                                 const float* __restrict__ h_src, const float* __restrict__ c_src, int H,
+                                                                 float* __restrict__ h_dst, long ldh, float* __restrict__ c_dst) {
+    __shared__ int s_par[KMAX], s_tok[KMAX];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x < K) {
+        s_par[threadIdx.x] = parent[b * K + threadIdx.x];
+        s_tok[threadIdx.x] = (int)token[b * K + threadIdx.x];
+    }
+    beam_move_rows(s_par, s_tok, b, K, lane, wave, embed, E, x_next, ldx, h_src, c_src, H, h_dst, ldh, c_dst);
+}
+
+extern "C" int64_t sat_beam_decode_ensemble_ws_bytes(const sat_decoder_model* models, int M, int B, int K, int V, int steps) {
+    if (ensemble_models_check(models, M) != SAT_OK) return 0;
+    if (B <= 0 || K <= 0 || K > KMAX || V <= 0 || steps < 1) return 0;
+    const int64_t R = (int64_t)B * K, ldl = (V + 3) / 4 * 4;
+    int64_t n = al256(R * ldl * 4) + 2 * al256(R * 4) + al256(sat_beam_step_ws_bytes(B, K)) + al256((int64_t)steps * R * 4) +
+                al256((int64_t)steps * R * 8) + beam_decode_ex_extra(R, steps);
+    for (int j = 0; j < M; ++j) n += ensemble_model_bytes(models[j], R, ldl, V);
+    return n;
+}
+
+extern "C" int sat_beam_decode_ensemble(const sat_decoder_model* models, int M, const float* weights, int mode, int B, int K, int V,
+                                        int steps, int64_t end_id, const sat_beam_constraints* c, int num_groups, float diversity_penalty,
+                                        int64_t* ids, float* scores_out, float* norm_scores, int32_t* order, void* workspace,
+                                        int64_t ws_bytes, sat_stream_t stream) {
+    if (!models || !ids || !workspace) return SAT_ERR_ARG;
+    EnsArgs ens;
+    SAT_TRY(ensemble_weights(M, weights, mode, &ens));
+    const int models_rc = ensemble_models_check(models, M);
+    if (models_rc == SAT_ERR_ARG) return models_rc;
+    SAT_TRY(beam_groups_check(K, num_groups, diversity_penalty));
+    if (B <= 0 || K > KMAX || V <= 0 || steps < 1) return SAT_ERR_ARG;
+    const int G = num_groups, Kg = K / G;
+    const float lambda = diversity_penalty;
+    bool active = false;
+    SAT_TRY(beam_constraints_check(c, end_id, &active));
+    if (models_rc != SAT_OK || (long)K * V > INT_MAX - 1) return SAT_ERR_UNSUPPORTED;
+    if (active && (steps > kBanTMax || V > kBanVMax)) return SAT_ERR_UNSUPPORTED;
+    const bool rerank = (c && c->length_penalty > 0.0f) || G > 1;
+    const float c_length_penalty = c ? c->length_penalty : 0.0f;
+    if (!active) c = nullptr;
+    const int64_t need = sat_beam_decode_ensemble_ws_bytes(models, M, B, K, V, steps);
+    if (need <= 0) return SAT_ERR_ARG;
+    if (ws_bytes < need || (((uintptr_t)workspace) & 255)) return SAT_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t R = (int64_t)B * K, ldl = (V + 3) / 4 * 4;
+    char* w = (char*)workspace;
+    float* comb = (float*)w; w += al256(R * ldl * 4);
+    float* sc[2];
+    sc[0] = (float*)w; w += al256(R * 4);
+    sc[1] = (float*)w; w += al256(R * 4);
+    float* cand_val = (float*)w; w += al256(sat_beam_step_ws_bytes(B, K));
+    int* cand_idx = (int*)(cand_val + (long)B * K * K);
+    int32_t* parents = (int32_t*)w; w += al256((int64_t)steps * R * 4);
+    int64_t* tokens = (int64_t*)w; w += al256((int64_t)steps * R * 8);
+    int64_t* ids_search = (int64_t*)w; w += al256(R * steps * 8);
+    float* sc_ranked = (float*)w; w += al256(R * 4);
+    float* norm_tmp = (float*)w; w += al256(R * 4);
+    int32_t* order_tmp = (int32_t*)w; w += al256(R * 4);
+    int* hist = (int*)w; w += al256(2 * R * kBanTMax * 4);
+    static const bool hist_env = [] { const char* v = getenv("SAT_BEAM_HISTORY"); return !(v && v[0] == '0'); }();
+    if (!(c && c->no_repeat_ngram >= 1 && hist_env)) hist = nullptr;
+    float *hc[kEnsMax], *logits[kEnsMax], *x0[kEnsMax] = {}, *xe[kEnsMax] = {};
+    float *xh[kEnsMax][2] = {}, *wcat[kEnsMax] = {}, *gates[kEnsMax] = {};      // the wide members' buffers
+    void* lin_split[kEnsMax] = {};
+    bool wide[kEnsMax] = {}, x3[kEnsMax] = {};
+    int ksplit[kEnsMax] = {}, xi[kEnsMax] = {};
+    for (int j = 0; j < M; ++j) {
+        const sat_decoder_model& d = models[j];
+        const int64_t ldx = d.E + d.H;
+        wide[j] = ensemble_wide(d, R);
+        x3[j] = ensemble_x3(d, R, V);
+        hc[j] = (float*)w; w += al256(4 * (int64_t)d.num_layers * R * d.H * 4);
+        logits[j] = (float*)w; w += al256(R * ldl * 4);
+        if (!wide[j]) {
+            x0[j] = (float*)w; w += al256(R * d.E * 4);
+            xe[j] = (float*)w; w += al256(R * d.E * 4);
+        } else {
+            xh[j][0] = (float*)w; w += al256(R * ldx * 4);
+            xh[j][1] = (float*)w; w += al256(R * ldx * 4);
+            wcat[j] = (float*)w; w += al256(4 * (int64_t)d.H * ldx * 4);
+            gates[j] = (float*)w; w += al256(kBeamKSplitMax * R * 4 * (int64_t)d.H * 4);
+            if (x3[j]) { lin_split[j] = w; w += al256(sat_gemm_f32x3_packed_bytes(V, d.H)); }
+            ksplit[j] = ensemble_ksplit(R, d.H, (long)ldx);
+        }
+        ens.x[j] = logits[j];
+    }
+    hipError_t e;
+    if (ldl > V) {                                             // pad columns: read by nobody, but keep them defined
+        e = hipMemsetAsync(comb, 0, (size_t)(R * ldl * 4), s);
+        if (e != hipSuccess) return (int)e;
+    }
+    for (int j = 0; j < M; ++j) {
+        const sat_decoder_model& d = models[j];
+        e = hipMemsetAsync(hc[j], 0, (size_t)(4 * (int64_t)d.num_layers * R * d.H * 4), s);       // h = c = 0
+        if (e != hipSuccess) return (int)e;
+        if (ldl > V) {
+            e = hipMemsetAsync(logits[j], 0, (size_t)(R * ldl * 4), s);
+            if (e != hipSuccess) return (int)e;
+        }
+        const long ldx = d.E + d.H;
+        if (wide[j]) {
+            if (x3[j]) SAT_TRY(sat_gemm_f32x3_pack(d.lin_w, V, d.H, lin_split[j], stream));
+            e = hipMemsetAsync(xh[j][0], 0, (size_t)(R * ldx * 4), s);                            // h_{-1} = 0
+            if (e != hipSuccess) return (int)e;
+            const long wtotal = 4L * d.H * ldx;
+            int wgrid = sat_cdiv(wtotal, 256);
+            if (wgrid > 2048) wgrid = 2048;
+            hipLaunchKernelGGL(beam_wcat_kernel, dim3(wgrid), dim3(256), 0, s, d.lstm_w[0], d.lstm_w[1], d.E, d.H, wtotal, wcat[j]);
+            SAT_LAUNCH_CHECK();
+        }
+        const long total = R * d.E;
+        int grid = sat_cdiv(total, 256);
+        if (grid > 2048) grid = 2048;
+        if ((long)grid * 256 < R) grid = sat_cdiv(R, 256);
+        hipLaunchKernelGGL(beam_init_kernel, dim3(grid), dim3(256), 0, s, d.features, K, d.E, total, wide[j] ? xh[j][0] : x0[j],
+                           wide[j] ? ldx : (long)d.E, sc[0], (int)R, Kg);
+        SAT_LAUNCH_CHECK();                                    // (every model writes the same start scores)
+    }
+    int cur_h[kEnsMax][8] = {}, cur_c[kEnsMax][8] = {};        // which of the two buffers holds a layer's live h / c
+    int si = 0;
+    for (int i = 0; i < steps; ++i) {
+        for (int j = 0; j < M; ++j) {
+            const sat_decoder_model& d = models[j];
+            const float* inp = i == 0 ? x0[j] : xe[j];
+            if (wide[j]) {
+                const long ldx = d.E + d.H;
+                float* cc = hc[j] + (long)(2 + cur_c[j][0]) * R * d.H;
+                float* h_new = hc[j];
+                SAT_TRY(sat_gemm_f32_splitk(0, 0, xh[j][xi[j]], ldx, wcat[j], ldx, gates[j], 4L * d.H, d.lstm_w[2], d.lstm_w[3], (int)R,
+                                            4 * d.H, (int)ldx, ksplit[j], R * 4L * d.H, stream));
+                const long total = R * d.H;
+                int grid = sat_cdiv(total, 256);
+                if (grid > 2048) grid = 2048;
+                hipLaunchKernelGGL(beam_lstm_point_kernel, dim3(grid), dim3(256), 0, s, gates[j], cc, h_new, d.H, total, ksplit[j],
+                                   R * 4L * d.H);
+                SAT_LAUNCH_CHECK();
+                if (x3[j]) SAT_TRY(sat_gemm_f32x3(h_new, d.H, lin_split[j], d.lin_b, logits[j], ldl, (int)R, V, d.H, stream));
+                else SAT_TRY(sat_vocab_logits_fwd(h_new, d.lin_w, d.lin_b, (int)R, d.H, V, logits[j], ldl, stream));
+                continue;
+            }
+            for (int l = 0; l < d.num_layers; ++l) {
+                float* base = hc[j] + (long)l * 4 * R * d.H;
+                float* h_in = base + (long)cur_h[j][l] * R * d.H;
+                float* h_out = base + (long)(1 - cur_h[j][l]) * R * d.H;
+                float* cc = base + (long)(2 + cur_c[j][l]) * R * d.H;
+                SAT_TRY(sat_lstm_step(inp, h_in, cc, d.lstm_w[4 * l], d.lstm_w[4 * l + 1], d.lstm_w[4 * l + 2], d.lstm_w[4 * l + 3], (int)R,
+                                      l == 0 ? d.E : d.H, d.H, h_out, stream));
+                cur_h[j][l] = 1 - cur_h[j][l];
+                inp = h_out;
+            }
+            SAT_TRY(sat_vocab_logits_fwd(inp, d.lin_w, d.lin_b, (int)R, d.H, V, logits[j], ldl, stream));
+        }
+        ensemble_launch(s, ens, M, (long)ldl, mode, (int)R, V, comb, (long)ldl);
+        SAT_LAUNCH_CHECK();
+        int32_t* par = parents + (long)i * R;
+        int64_t* tok = tokens + (long)i * R;
+        const int64_t* last = (i > 0 && end_id >= 0) ? tok - R : (const int64_t*)nullptr;
+        beam_row_launch(s, comb, (long)ldl, sc[si], last, (long)end_id, (int)R, K, V, cand_val, cand_idx, c, parents, tokens, i, hist);
+        SAT_LAUNCH_CHECK();
+        beam_merge_launch(s, B, cand_val, cand_idx, K, V, Kg, lambda, last, (long)end_id, par, tok, sc[1 - si], nullptr, 0, nullptr, 0L,
+                          nullptr, nullptr, 0, nullptr, 0L, nullptr);
+        SAT_LAUNCH_CHECK();
+        si = 1 - si;
+        if (i + 1 == steps) break;                             // nothing reads the state behind the last selection
+        for (int j = 0; j < M; ++j) {
+            const sat_decoder_model& d = models[j];
+            if (wide[j]) {                                     // embedding rows and (h, c) by parent in ONE launch, h into the next [x | h]
+                const long ldx = d.E + d.H;
+                float* xn = xh[j][1 - xi[j]];
+                hipLaunchKernelGGL(ensemble_move_rows_kernel, dim3(B), dim3(256), 0, s, (const int*)par, (const int64_t*)tok, K, d.embed, d.E,
+                                   xn, ldx, (const float*)hc[j], (const float*)(hc[j] + (long)(2 + cur_c[j][0]) * R * d.H), d.H, xn + d.E, ldx,
+                                   hc[j] + (long)(2 + 1 - cur_c[j][0]) * R * d.H);
+                SAT_LAUNCH_CHECK();
+                cur_c[j][0] = 1 - cur_c[j][0];
+                xi[j] = 1 - xi[j];
+                continue;
+            }
+            SAT_TRY(sat_embed_rows(d.embed, tok, 1, (int)R, d.E, V, xe[j], stream));
+            for (int l = 0; l < d.num_layers && K > 1; ++l) {
+                float* base = hc[j] + (long)l * 4 * R * d.H;
+                const long total = R * d.H;
+                int grid = sat_cdiv(2 * total, 256);
+                if (grid > 2048) grid = 2048;
+                hipLaunchKernelGGL(beam_gather2_kernel, dim3(grid), dim3(256), 0, s, base + (long)cur_h[j][l] * R * d.H,
+                                   base + (long)(2 + cur_c[j][l]) * R * d.H, par, K, d.H, total, base + (long)(1 - cur_h[j][l]) * R * d.H,
+                                   (long)d.H, base + (long)(2 + 1 - cur_c[j][l]) * R * d.H);
+                SAT_LAUNCH_CHECK();
+                cur_h[j][l] = 1 - cur_h[j][l];
+                cur_c[j][l] = 1 - cur_c[j][l];
+            }
+        }
+    }
+    hipLaunchKernelGGL(beam_backtrack_kernel, dim3(sat_cdiv(R, 256)), dim3(256), 0, s, parents, tokens, steps, (int)R, K,
+                       rerank ? ids_search : ids);
+    SAT_LAUNCH_CHECK();
+    if (rerank) {
+        hipLaunchKernelGGL(beam_rerank_kernel, dim3(B), dim3(64), 0, s, (const int64_t*)ids_search, (const float*)sc[si], K, steps, end_id,
+                           c_length_penalty, ids, scores_out ? scores_out : sc_ranked, norm_scores ? norm_scores : norm_tmp,
+                           order ? order : order_tmp);
+        SAT_LAUNCH_CHECK();
+        return SAT_OK;
+    }
+    if (scores_out) {
+        e = hipMemcpyAsync(scores_out, sc[si], (size_t)(R * 4), hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return (int)e;
+    }
+    if (norm_scores) {
+        e = hipMemcpyAsync(norm_scores, sc[si], (size_t)(R * 4), hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return (int)e;
+    }
+    if (order) {
+        hipLaunchKernelGGL(beam_iota_kernel, dim3(sat_cdiv(R, 256)), dim3(256), 0, s, order, (int)R, K);
+        SAT_LAUNCH_CHECK();
+    }
+    return SAT_OK;
+}
