@@ -906,6 +906,51 @@ int sat_cider_score(const sat_cider_corpus* corpus /*[host]*/, const int64_t* id
                     double* scores /*[B]*/, double* mean /*[1]*/, sat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Consensus (minimum-Bayes-risk) reranking of decoded candidates by pairwise CIDEr (added within ABI 18): every candidate of an
+ * image is scored against the OTHER candidates of the same image with the corpus's document frequencies, and the candidate the
+ * rest agree with most is picked -- the selection for images that have no reference captions.
+ *
+ * Image b has K candidates ids[b][i][0..T): candidate i of image b starts at ids + b * image_stride + i * cand_stride.
+ * Candidate i has L_i tokens: kept[b*K+i] clamped to [0, T], or with kept == NULL the position of its first end_id (T without
+ * one).  The corpus gives log_images = log(n_images) and df: exactly sat_cider_score's corpus, nothing new is built on the host
+ * (its reference captions and ref_norm are not read).
+ *
+ * For candidate i as hypothesis and candidate j != i as the single reference, with w_x(g) = tf_x(g) * (log_images -
+ * log(max(1, df[g]))):
+ *   val_ij[o] = sum over the DISTINCT order-o n-grams g of i, in order of first occurrence, of  min(w_i(g), w_j(g)) * w_j(g)
+ *               / (norm_i[o] * norm_j[o])   only when both are non-zero
+ *               * exp(-(len_i - len_j)^2 / (2 sigma^2)),        len_x = max(L_x - 1, 0)
+ *   pair[b][i][j] = (((val_ij[0] + val_ij[1]) + val_ij[2]) + val_ij[3]) / 4 * 10           pair[b][i][i] = +0.0 (not computed)
+ * Utility with weights == NULL (uniform):
+ *   tot[o] = sum over j != i, in slot order, of val_ij[o]
+ *   utility[b][i] = (((tot[0] + tot[1]) + tot[2]) + tot[3]) / 4 / (K - 1) * 10;   K == 1: utility 0.
+ * This is CiderScorer.compute_cider() of candidate i with the other K - 1 candidates as its reference set, operation for operation.
+ * Utility with weights (device f64 [B][K], finite and >= 0, not checked on the device):
+ *   tot[o] = sum over j != i, in slot order, of w_j * val_ij[o];   den = sum over j != i, in slot order, of w_j
+ *   utility = (((tot[0] + tot[1]) + tot[2]) + tot[3]) / 4 / den * 10, or 0 when den == 0.
+ * best[b] is the first slot of maximal utility (int64; a NaN utility is never picked over a number).
+ *
+ * Unlike sat_cider_score, an n-gram the corpus lacks (df = 0, weight tf * log_images) DOES match the same n-gram in another
+ * candidate: matches are by token comparison, never by node id.  An id outside [0, 2^31) is no token: it becomes -1 where its row
+ * is the hypothesis and -2 where it is the reference, so it never matches anything across rows, itself included; it still counts
+ * in L.  Every sum has the fixed order stated above: two calls give the same bits, and row b's results do not depend on B.
+ *
+ * Three launches: one wave per (image, candidate) leaves the candidate's norms and length in the workspace; one wave per (image,
+ * candidate) walks the other candidates of its image and writes pair and utility; one thread per image picks best.  No
+ * allocation, no host read, no workgroup waits for another.  workspace: sat_consensus_ws_bytes(B, K) bytes at an 8-byte aligned
+ * address (0 for non-positive sizes).
+ * SAT_ERR_ARG before anything is enqueued: a NULL pointer (kept, weights and pair excepted); B, K or T <= 0; cand_stride < T;
+ * image_stride < K * cand_stride when B > 1; sigma not finite or <= 0; a corpus that sat_cider_score refuses (ref_norm may be
+ * NULL); a workspace that is not 8-byte aligned.  SAT_ERR_UNSUPPORTED: T > 64, K > 64, B * K >= 2^31.  SAT_ERR_WORKSPACE:
+ * ws_bytes < sat_consensus_ws_bytes(B, K).
+ */
+int64_t sat_consensus_ws_bytes(int B, int K);
+int sat_consensus_rerank(const sat_cider_corpus* corpus /*[host]*/, const int64_t* ids, int64_t image_stride, int64_t cand_stride,
+                         int B, int K, int T, const int32_t* kept /*[B*K] or NULL*/, int64_t end_id, double sigma,
+                         const double* weights /*[B][K] or NULL*/, double* utility /*[B][K]*/, int64_t* best /*[B]*/,
+                         double* pair /*[B][K][K] or NULL*/, void* workspace, int64_t ws_bytes, sat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * BLEU-1..4 and ROUGE-L of decoded id rows against reference captions (added within ABI 18): the other plain-arithmetic metrics
  * of language_eval (eval.py:17-56).  Rows, `kept` / end_id, image_index and the flat corpus are those of sat_cider_score: ids is
  * [B] rows of T <= 64 int64, `stride` elements apart; row b has L tokens, L = kept[b] clamped to [0, T] or, with kept NULL, the

@@ -20,6 +20,7 @@ from .ensemble import Ensemble  # noqa: F401
 from .input import DevicePrefetcher, ImageTransform, collate_batch, collate_on_device  # noqa: F401
 from .evaluate import kept_tokens, mean_cross_entropy, pack_validation_targets, sentences, validation_step  # noqa: F401
 from .cider import CiderScorer, encode_references  # noqa: F401
+from .consensus import ConsensusReranker  # noqa: F401
 from .langstats import BleuScorer, MixedReward, RougeLScorer  # noqa: F401
 from .scst import SelfCritical, ce_rows_weighted, scst_loss, scst_weights  # noqa: F401
 from .criterion import CrossEntropy, cross_entropy  # noqa: F401

@@ -217,6 +217,9 @@ SIGNATURES = {
     "sat_cider_table_insert": (_i, [_vp, _i, _vp, _vp, _i64, _vp, _vp]),
     "sat_cider_ref_stats": (_i, [C.POINTER(SatCiderCorpus), _vp, _vp]),
     "sat_cider_score": (_i, [C.POINTER(SatCiderCorpus), _vp, _i64, _i, _i, _vp, _i64, _vp, C.c_double, _vp, _vp, _vp]),
+    "sat_consensus_ws_bytes": (_i64, [_i, _i]),
+    "sat_consensus_rerank": (_i, [C.POINTER(SatCiderCorpus), _vp, _i64, _i64, _i, _i, _i, _vp, _i64, C.c_double, _vp, _vp, _vp, _vp, _vp,
+                                  _i64, _vp]),
     "sat_bleu_comps": (_i, [C.POINTER(SatRefCorpus), _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sat_bleu_finalize": (_i, [_vp, _vp, _vp]),
     "sat_rouge_l_score": (_i, [C.POINTER(SatRefCorpus), _vp, _i64, _i, _i, _vp, _i64, _vp, C.c_double, _vp, _vp, _vp]),
@@ -261,7 +264,8 @@ ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_at
                     "sat_beam_decode_ex_ws_bytes", "sat_beam_decode_ex", "sat_beam_step_groups", "sat_beam_step_groups_ws_bytes",
                     "sat_beam_decode_groups_ws_bytes", "sat_beam_decode_groups", "sat_ce_rows_ls", "sat_vocab_ce_fwd_bf16_ls",
                     "sat_grad_sumsq_partials", "sat_grad_sumsq_ws_bytes", "sat_grad_sumsq", "sat_adamw_step",
-                    "sat_ensemble_logprobs", "sat_beam_decode_ensemble_ws_bytes", "sat_beam_decode_ensemble")
+                    "sat_ensemble_logprobs", "sat_beam_decode_ensemble_ws_bytes", "sat_beam_decode_ensemble",
+                    "sat_consensus_ws_bytes", "sat_consensus_rerank")
 
 _lib = None
 

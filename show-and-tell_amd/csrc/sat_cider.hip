@@ -316,3 +316,157 @@ extern "C" int sat_cider_score(const sat_cider_corpus* corpus, const int64_t* id
     SAT_LAUNCH_CHECK();
     return SAT_OK;
 }
+
+// Consensus reranking (sat_consensus_rerank in include/sat_hip.h): the candidates of one image scored against each other.  The
+// "references" of a row are the other rows of the decode output, so nothing of the corpus but the table and df is read, and an
+// n-gram the corpus lacks is matched like any other: by its tokens.
+namespace {
+constexpr int kMaxCand = 64;                 // candidates per image
+
+// candidate `row` of the grid into c.tok (hypothesis form: -1 for an id that is no token) and its length; then its statistics
+__device__ __forceinline__ int consensus_load_row(caption_lds<kMaxHyp>& c, int* len_lds, const int64_t* __restrict__ row, int slot, int T,
+                                                  const int32_t* __restrict__ kept, int64_t end_id, const cider_table& t,
+                                                  double log_images) {
+    const int lane = threadIdx.x;
+    const int64_t my = lane < T ? row[lane] : 0;
+    c.tok[lane] = lane < T && my >= 0 && my <= 0x7fffffffll ? (int)my : -1;
+    if (kept) {
+        if (lane == 0) *len_lds = clampi(kept[slot], 0, T);
+    } else {
+        const unsigned long long ends = __ballot(lane < T && my == end_id);
+        if (lane == 0) *len_lds = ends ? __ffsll(ends) - 1 : T;
+    }
+    __syncthreads();
+    const int L = *len_lds;
+    caption_stats(c, L, t, log_images);
+    return L;
+}
+
+// one wave per (image, candidate): norm[slot][4] and len[slot]
+__global__ __launch_bounds__(64) void consensus_stats_kernel(cider_table t, int n_images, const int64_t* __restrict__ ids,
+                                                             int64_t image_stride, int64_t cand_stride, int K, int T,
+                                                             const int32_t* __restrict__ kept, int64_t end_id, double* __restrict__ norm,
+                                                             int32_t* __restrict__ len) {
+    __shared__ caption_lds<kMaxHyp> cap;
+    __shared__ int cap_len;
+    const int slot = blockIdx.x, b = slot / K, i = slot - b * K, lane = threadIdx.x;
+    const int L = consensus_load_row(cap, &cap_len, ids + (int64_t)b * image_stride + (int64_t)i * cand_stride, slot, T, kept, end_id, t,
+                                     log((double)n_images));
+    if (lane < kOrders) norm[(int64_t)slot * kOrders + lane] = cap.norm[lane];
+    if (lane == 0) len[slot] = L;
+}
+
+// one wave per (image, candidate i): the other candidates j of the image as single references, in slot order
+__global__ __launch_bounds__(64) void consensus_pair_kernel(cider_table t, int n_images, const int64_t* __restrict__ ids,
+                                                            int64_t image_stride, int64_t cand_stride, int K, int T,
+                                                            const int32_t* __restrict__ kept, int64_t end_id,
+                                                            const double* __restrict__ norm, const int32_t* __restrict__ len,
+                                                            const double* __restrict__ weights, double inv_two_sigma2,
+                                                            double* __restrict__ utility, double* __restrict__ pair) {
+    __shared__ caption_lds<kMaxHyp> hyp;
+    __shared__ int rtok[kMaxHyp];
+    __shared__ int hyp_len;
+    __shared__ double total[kOrders], value[kOrders];
+    const int slot = blockIdx.x, b = slot / K, i = slot - b * K, lane = threadIdx.x;
+    const int64_t* image = ids + (int64_t)b * image_stride;
+    if (lane < kOrders) total[lane] = 0.0;
+    const int L = consensus_load_row(hyp, &hyp_len, image + (int64_t)i * cand_stride, slot, T, kept, end_id, t, log((double)n_images));
+    const int len_h = max(L - 1, 0);
+    const double* w = weights ? weights + (int64_t)b * K : nullptr;
+    double den = 0.0;
+    for (int j = 0; j < K; ++j) {
+        if (j == i) {
+            if (pair && lane == 0) pair[(int64_t)slot * K + j] = 0.0;
+            continue;
+        }
+        // reference form: -2 for an id that is no token, so it equals no hypothesis token (-1 included)
+        const int64_t other = lane < T ? image[(int64_t)j * cand_stride + lane] : -1;
+        rtok[lane] = other >= 0 && other <= 0x7fffffffll ? (int)other : -2;
+        const int Lr = clampi(len[b * K + j], 0, T);
+        const double wj = w ? w[j] : 1.0;
+        den += wj;
+        __syncthreads();
+        for (int item = lane; item < kOrders * kMaxHyp; item += 64) {
+            const int k = item / kMaxHyp, p = item - k * kMaxHyp;
+            double term = 0.0;
+            const int tf = hyp.tf[k][p];
+            if (tf > 0) {
+                int tfr = 0;
+                for (int q = 0; q + k < Lr; ++q) tfr += same_ngram(hyp.tok, p, rtok, q, k) ? 1 : 0;
+                const double vh = (double)tf * hyp.idf[k][p], vr = (double)tfr * hyp.idf[k][p];
+                term = fmin(vh, vr) * vr;
+            }
+            hyp.term[k][p] = term;
+        }
+        __syncthreads();
+        if (lane < kOrders) {
+            double val = 0.0;
+            for (int p = 0; p + lane < L; ++p) val += hyp.term[lane][p];
+            const double nh = hyp.norm[lane], nr = norm[(int64_t)(b * K + j) * kOrders + lane];
+            if (nh != 0.0 && nr != 0.0) val /= nh * nr;
+            const double delta = (double)(len_h - max(Lr - 1, 0));
+            val *= exp(-(delta * delta) * inv_two_sigma2);
+            value[lane] = val;
+            total[lane] += w ? wj * val : val;
+        }
+        __syncthreads();
+        if (pair && lane == 0) pair[(int64_t)slot * K + j] = (((value[0] + value[1]) + value[2]) + value[3]) / (double)kOrders * 10.0;
+    }
+    if (lane == 0) {
+        double s = (((total[0] + total[1]) + total[2]) + total[3]) / (double)kOrders;
+        if (w) s = den != 0.0 ? s / den * 10.0 : 0.0;
+        else s = K > 1 ? s / (double)(K - 1) * 10.0 : 0.0;
+        utility[slot] = s;
+    }
+}
+
+// one thread per image: the first slot of maximal utility
+__global__ __launch_bounds__(64) void consensus_best_kernel(const double* __restrict__ utility, int B, int K, int64_t* __restrict__ best) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const double* u = utility + (int64_t)b * K;
+    int arg = 0;
+    double top = u[0];
+    for (int i = 1; i < K; ++i) {
+        const double v = u[i];
+        if (v > top || (top != top && v == v)) {
+            top = v;
+            arg = i;
+        }
+    }
+    best[b] = arg;
+}
+}  // namespace
+
+extern "C" int64_t sat_consensus_ws_bytes(int B, int K) {
+    if (B <= 0 || K <= 0) return 0;
+    const int64_t rows = (int64_t)B * K;
+    return rows * kOrders * (int64_t)sizeof(double) + (rows * (int64_t)sizeof(int32_t) + 7) / 8 * 8;
+}
+
+extern "C" int sat_consensus_rerank(const sat_cider_corpus* corpus, const int64_t* ids, int64_t image_stride, int64_t cand_stride, int B,
+                                    int K, int T, const int32_t* kept, int64_t end_id, double sigma, const double* weights,
+                                    double* utility, int64_t* best, double* pair, void* workspace, int64_t ws_bytes,
+                                    sat_stream_t stream) {
+    SAT_TRY(corpus_check(corpus, false));
+    if (!ids || !utility || !best || !workspace || B <= 0 || K <= 0 || T <= 0 || cand_stride < T) return SAT_ERR_ARG;
+    if (B > 1 && image_stride < (int64_t)K * cand_stride) return SAT_ERR_ARG;
+    if (!(sigma > 0.0) || sigma - sigma != 0.0) return SAT_ERR_ARG;
+    if ((uintptr_t)workspace % 8 != 0) return SAT_ERR_ARG;
+    if (T > kMaxHyp || K > kMaxCand || (int64_t)B * K > 0x7fffffffll) return SAT_ERR_UNSUPPORTED;
+    if (ws_bytes < sat_consensus_ws_bytes(B, K)) return SAT_ERR_WORKSPACE;
+    const int rows = B * K;
+    double* norm = (double*)workspace;
+    int32_t* len = (int32_t*)(norm + (int64_t)rows * kOrders);
+    const cider_table t = corpus_dev(corpus).table;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(consensus_stats_kernel, dim3(rows), dim3(64), 0, s, t, corpus->n_images, ids, image_stride, cand_stride, K, T, kept,
+                       end_id, norm, len);
+    SAT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(consensus_pair_kernel, dim3(rows), dim3(64), 0, s, t, corpus->n_images, ids, image_stride, cand_stride, K, T, kept,
+                       end_id, norm, len, weights, 1.0 / (2.0 * sigma * sigma), utility, pair);
+    SAT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(consensus_best_kernel, dim3(sat_cdiv(B, 64)), dim3(64), 0, s, utility, B, K, best);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}

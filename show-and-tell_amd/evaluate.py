@@ -66,7 +66,7 @@ def kept_tokens(ids, end_id):
 @torch.no_grad()
 def validation_step(model, images, captions, lengths, state=None, end_id=2, beam_size=1, scorer=None, image_index=None,
                     bleu=None, rouge=None, *, suppress_ids=None, min_length=0, no_repeat_ngram_size=0, block_repeat=False,
-                    length_penalty=0.0, num_beam_groups=1, diversity_penalty=0.0):
+                    length_penalty=0.0, num_beam_groups=1, diversity_penalty=0.0, consensus=None):
     """One iteration of the loop body eval.py:71-118 (the caller has put the model in eval mode, eval.py:65).
     Returns dict(loss f32[1], ids i64[B,20], kept i32[B]) -- all on the device, nothing synchronised.  With a `CiderScorer`
     and `image_index` (the corpus image of every row) the dict gains cider f64[1] and cider_scores f64[B] of `ids`; with a
@@ -74,7 +74,11 @@ def validation_step(model, images, captions, lengths, state=None, end_id=2, beam
     is the corpus Bleu_1..4); with a `RougeLScorer` as `rouge`, rouge_l f64[1] and rouge_l_scores f64[B].
     The keyword-only beam constraints (`sample_beam`'s; all off by default) go to the beam decode: with any of them on the
     decode is `sample_beam` also at beam_size=1 -- the constrained greedy decode -- which starts from the zero state.
-    num_beam_groups / diversity_penalty (`sample_beam`'s diverse beam search; one group by default) go there too."""
+    num_beam_groups / diversity_penalty (`sample_beam`'s diverse beam search; one group by default) go there too.
+    consensus: a `ConsensusReranker` (consensus.py).  With one and beam_size > 1 the decoded `ids` are the consensus pick of the
+    beam_size hypotheses (equal weights; the reranker's end_id must be `end_id`) instead of the likelihood winner, and the dict
+    gains consensus_best i64[B] and consensus_utility f64[B,beam_size]; with beam_size == 1 there is nothing to pick from:
+    ValueError."""
     from .models import check_beam_constraints, check_beam_groups
     cons = dict(suppress_ids=suppress_ids, min_length=min_length, no_repeat_ngram_size=no_repeat_ngram_size,
                 block_repeat=block_repeat, length_penalty=length_penalty)
@@ -86,6 +90,11 @@ def validation_step(model, images, captions, lengths, state=None, end_id=2, beam
             raise ValueError("scorer and image_index go together")
     elif image_index is None:
         raise ValueError("bleu and rouge need image_index, the corpus image of every row")
+    if consensus is not None:
+        if beam_size <= 1:
+            raise ValueError("consensus reranking needs beam_size > 1: one hypothesis per image leaves nothing to pick from")
+        if consensus.end_id != end_id:
+            raise ValueError("the reranker ends rows at id %d, validation_step at %d" % (consensus.end_id, end_id))
     if model.training:
         raise RuntimeError("validation_step expects model.eval() (eval.py:65)")
     targets, _ = pack_validation_targets(captions, lengths)
@@ -96,12 +105,17 @@ def validation_step(model, images, captions, lengths, state=None, end_id=2, beam
     if beam_size > 1 or constraints:
         if constraints and state is not None:
             raise ValueError("the constrained decode is `sample_beam`, which takes no initial state")
-        ids = model.sample_beam(images, beam_size=beam_size, end_id=end_id, **constraints)
+        if consensus is not None:
+            ids = consensus.decode(model, images, beam_size=beam_size, **constraints)
+        else:
+            ids = model.sample_beam(images, beam_size=beam_size, end_id=end_id, **constraints)
     else:
         ids = model.sample(images, state)                               # eval.py:99
         if ids.dim() == 1:                                              # squeezed at batch 1 (models.py:67): one row
             ids = ids.view(1, -1)
     out = {"loss": loss, "ids": ids, "kept": kept_tokens(ids, end_id)}
+    if consensus is not None:
+        out["consensus_best"], out["consensus_utility"] = consensus.last_best, consensus.last_utility
     if scorer is not None:
         out["cider"], out["cider_scores"] = scorer.score(ids, image_index, end_id=end_id, kept=out["kept"])
     if bleu is not None:
