@@ -1036,6 +1036,34 @@ int sat_scst_weights(const int64_t* ids, int64_t stride, int B, int T, int64_t e
 int sat_ce_rows_weighted(float* logits /*[N,ldl]*/, int64_t ldl, const int64_t* ids, int64_t ids_stride, int B, int N, int V,
                          const float* w /*[N]*/, int write_grad, float* row_loss /*[N]*/, float* loss_out /*[1] or NULL*/,
                          sat_stream_t stream);
+/* Self-critical training with S sampled captions per image and a leave-one-out baseline (Luo 2020, arXiv:2003.09971; added within
+ * ABI 18).  Rows are image-major: R = B*S rows, row r = b*S + s is sample s of image b, packed logits row n = t*R + r (the rollouts
+ * run on R rows; nothing in them changes).
+ * sat_scst_weights_group: len[r] and M exactly as sat_scst_weights over the R rows (len[r] = min(kept[r] + 1, T); M = the integer
+ *   sum of all R lengths, or *denom when denom != NULL).
+ *   mode 0 (a baseline per image): advantage[r] = reward[r] - (baseline_img ? baseline_img[r / S] : 0.0); baseline_out[r] is that
+ *     baseline.  With S == 1 this is sat_scst_weights, bit for bit.
+ *   mode 1 (leave-one-out): advantage[r] = (sum over s' = 0..S-1, s' != s, ascending, starting from 0.0, of
+ *     (reward[r] - reward[b*S + s'])) / (S - 1).  The sum is of DIFFERENCES on purpose: S identical rewards give exactly +0.0,
+ *     which reward - mean(others) does not (0.1 + 0.1 + 0.1 = 0.30000000000000004).  baseline_out[r] = (sum over s' != s,
+ *     ascending, from 0.0, of reward[b*S + s']) / (S - 1), for logging only.
+ *   w[t*R + r] = (float)(advantage[r] / M) for t < len[r], +0.0f after.  All arithmetic is f64, rounded once, in a fixed order: the
+ *   bits are the same in every call and for every B.  Plain vector stores, no atomics; one launch of one workgroup whose threads
+ *   stride over the rows, so any R (and any B) is served.  reward f64 [B*S], baseline_img f64 [B] or NULL, denom f64 [1] or NULL:
+ *   device.  Outputs w f32 [T*B*S], len i32 [B*S], m_out f64 [1], advantage f64 [B*S], baseline_out f64 [B*S] or NULL.
+ *   SAT_ERR_ARG before anything is enqueued: a NULL required pointer; B, S or T < 1; mode outside {0, 1}; mode 1 with S < 2 or
+ *   with a non-NULL baseline_img; stride < T; B*S*T > INT_MAX.  SAT_ERR_UNSUPPORTED: S > 256.
+ * sat_group_sum_rows: out[b][j] = (((in[b*S][j] + in[b*S+1][j]) + in[b*S+2][j]) + ...) in f32, ascending s, j < W; S == 1 is a copy.
+ *   The backward of "one image's features feed S rows", here so that the autograd path and the fused step give the same bits.  A
+ *   16-byte path runs on the first W - W % 4 columns where both strides are multiples of 4 and both pointers 16-byte aligned; a
+ *   scalar path takes the other columns, or all of them.  SAT_ERR_ARG: NULL pointers, B, S or W < 1, ld_in < W, ld_out < W, or
+ *   `in` and `out` overlapping. */
+int sat_scst_weights_group(const int64_t* ids, int64_t stride, int B, int S, int T, int64_t end_id, const double* reward /*[B*S]*/,
+                           const double* baseline_img /*[B] or NULL*/, int mode, const double* denom /*[1] or NULL*/,
+                           float* w /*[T*B*S]*/, int32_t* len /*[B*S]*/, double* m_out /*[1]*/, double* advantage /*[B*S]*/,
+                           double* baseline_out /*[B*S] or NULL*/, sat_stream_t stream);
+int sat_group_sum_rows(const float* in /*[B*S][ld_in]*/, int64_t ld_in, int B, int S, int64_t W, float* out /*[B][ld_out]*/,
+                       int64_t ld_out, sat_stream_t stream);
 /* The rollout of the Show-Attend-Tell decoder (added within ABI 18): the training-form recurrence of model2.py:38-85 for all B rows
  * over all `steps` steps as ONE call, no host synchronisation -- sat_ss_attend_fwd's loop (the same five launches per step: weight_hh
  * projection from h_{t-1} with h_{-1} = h0, attention with its context written into X's context half, LSTMCell, output layer, vocab

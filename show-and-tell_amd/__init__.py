@@ -22,7 +22,7 @@ from .evaluate import kept_tokens, mean_cross_entropy, pack_validation_targets, 
 from .cider import CiderScorer, encode_references  # noqa: F401
 from .consensus import ConsensusReranker  # noqa: F401
 from .langstats import BleuScorer, MixedReward, RougeLScorer  # noqa: F401
-from .scst import SelfCritical, ce_rows_weighted, scst_loss, scst_weights  # noqa: F401
+from .scst import SelfCritical, ce_rows_weighted, group_sum_rows, scst_loss, scst_weights, scst_weights_group  # noqa: F401
 from .criterion import CrossEntropy, cross_entropy  # noqa: F401
 from .optim import FusedClampAdam, no_decay_names, no_decay_params  # noqa: F401
 from .pack import PackInfo, pack_targets  # noqa: F401

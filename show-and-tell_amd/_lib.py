@@ -228,6 +228,8 @@ SIGNATURES = {
                                      C.c_uint64, _i, _vp, _i64, _vp, _i64, _vp]),
     "sat_scst_weights": (_i, [_vp, _i64, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sat_ce_rows_weighted": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "sat_scst_weights_group": (_i, [_vp, _i64, _i, _i, _i, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sat_group_sum_rows": (_i, [_vp, _i64, _i, _i, _i64, _vp, _i64, _vp]),
     "sat_ce_rows_ls": (_i, [_vp, _i64, _vp, _i, _i, _f, _f, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sat_vocab_ce_fwd_bf16_ls": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sat_rollout_attend_fwd_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
@@ -265,7 +267,7 @@ ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_at
                     "sat_beam_decode_groups_ws_bytes", "sat_beam_decode_groups", "sat_ce_rows_ls", "sat_vocab_ce_fwd_bf16_ls",
                     "sat_grad_sumsq_partials", "sat_grad_sumsq_ws_bytes", "sat_grad_sumsq", "sat_adamw_step",
                     "sat_ensemble_logprobs", "sat_beam_decode_ensemble_ws_bytes", "sat_beam_decode_ensemble",
-                    "sat_consensus_ws_bytes", "sat_consensus_rerank")
+                    "sat_consensus_ws_bytes", "sat_consensus_rerank", "sat_scst_weights_group", "sat_group_sum_rows")
 
 _lib = None
 
@@ -363,10 +365,16 @@ _SKINNY_WS = {}
 _SKINNY_ROWS = int(os.environ.get("SAT_SKINNY_ROWS", "128"))   # per-step GEMMs with at most this many rows take the split-K kernel
 
 
+def gemm_splits_k(amode, bmode, lda, ldb, ldc, M, N, K, bias2=None):
+    """whether `gemm` hands this call to sat_skinny_gemm_f32.  Its K split depends on M, so a row of its result does too; a row
+    of sat_gemm_f32's does not (callers that encode a matrix once and repeat the result ask here)"""
+    return amode == 0 and M <= _SKINNY_ROWS and bias2 is None and ldc == N and K % 4 == 0 and lda % 4 == 0 and (bmode == 1 or ldb % 4 == 0)
+
+
 def gemm(lib, amode, bmode, A, lda, B, ldb, Cout, ldc, M, N, K, bias=None, bias2=None):
     """C[M,N] = op(A) op(B) + bias (+ bias2), f32; A, B, Cout: tensors or raw addresses.  A 64 x 64-tiled GEMM of a 64-row decode
     step runs on N/64 workgroups; those go to sat_skinny_gemm_f32, which splits K over waves and grid slices instead."""
-    if amode == 0 and M <= _SKINNY_ROWS and bias2 is None and ldc == N and K % 4 == 0 and lda % 4 == 0 and (bmode == 1 or ldb % 4 == 0):
+    if gemm_splits_k(amode, bmode, lda, ldb, ldc, M, N, K, bias2):
         import torch
         need = lib.sat_skinny_gemm_ws_bytes(M, N, K)
         dev = torch.cuda.current_device()

@@ -29,7 +29,7 @@ from .attend_bwd import PARAM_ORDER, attend_backward
 from .decoder import dropout_rows
 from .models import check_beam_constraints, check_beam_groups, check_dropout_p, check_sample_args, draw_ss_seed, lookahead_stream, refuse_dropout_with, stochastic_result
 from .pack import PackInfo
-from .scst import SelfCritical
+from .scst import SelfCritical, check_group, repeat_rows
 from .vgg import VGG16_FEATURES, VggFeatures, VggProgram, _VggFn  # noqa: F401  (VggFeatures is re-exported by the package)
 from .watch import IdGuard
 
@@ -72,6 +72,23 @@ def _context_encode(lib, m, f2):
     return ctx_enc
 
 
+def _context_encode_group(lib, m, src, S, f2):
+    """`_context_encode(f2)` for f2 = the features of `src` [B, P, C] with every image S times in a row, encoded ONCE per image
+    and the result repeated (data movement): the bits of encoding all R * P rows, for 1 / S of the GEMM.  A row of
+    `sat_gemm_f32`'s result does not depend on how many rows the call has: the row count only picks the workgroup tile (64 x 64,
+    128 x 64 or 128 x 128, `launch_f32_auto`), and every tile walks K in the same steps of 32 with the same 32x32x2 f32 MFMA in
+    the same order, so B * P rows and R * P rows may take different tiles and still agree bit for bit.  The split-K kernel's K
+    split does depend on the row count: where `L.gemm` would hand the R * P-row call to it (`L.gemm_splits_k`, the rule `L.gemm`
+    itself dispatches by), the repeated matrix is encoded as it stands."""
+    B, P, C = src.shape
+    if L.gemm_splits_k(0, 1, C, C, C, f2.shape[0], C, C):
+        return _context_encode(lib, m, f2)
+    enc = torch.empty(B * P, C, device=src.device)
+    L.check(lib.sat_gemm_f32(0, 1, L.ptr(src), C, L.ptr(m.image_att_w), C, L.ptr(enc), C, None, None, B * P, C, C, L.stream()),
+            "sat_gemm_f32")
+    return enc.view(B, P * C).repeat_interleave(S, 0).view(B * S * P, C)
+
+
 def _output_weight(lib, m):
     """Wz = [W_c2o | W_h2o] [E, C + H]: the output layer (model2.py:80-85) as one GEMM z = [ctx | h] Wz^T + b1 + b2, and the
     backward's dZin = dZ Wz"""
@@ -89,13 +106,14 @@ class _DecoderSetup:
     (model2.py:67-71, two GEMMs), the tapes `tp` named as in `_SS_TAPES` (HS = HSX[B:]), the token buffer toks [N] and Wz.
     with_wz=False leaves Wz to the caller: the teacher-forced loop builds it behind its steps."""
 
-    def __init__(self, lib, m, features, fmean, N, with_wz=True):
+    def __init__(self, lib, m, features, fmean, N, with_wz=True, group=None):
+        """group: None, or (src [B / S, P, C], S) when `features` is src with every image S times in a row (`rollout(num_samples=S)`)"""
         dev = features.device
         B, P, C = features.shape
         E, H = m.embed_size, m.hidden_size
         self.m, self.fmean = m, fmean
         self.f2 = features.view(B * P, C)
-        self.ctx_enc = _context_encode(lib, m, self.f2)
+        self.ctx_enc = _context_encode(lib, m, self.f2) if group is None else _context_encode_group(lib, m, *group, self.f2)
         self.HSX = torch.empty(B + N, H, device=dev)
         self.h0, self.c0 = self.HSX[:B], torch.empty(B, H, device=dev)
         L.gemm(lib, 0, 0, fmean, C, m.init_hidden.weight, C, self.h0, H, B, H, C, m.init_hidden.bias)
@@ -226,13 +244,14 @@ class _AttendRolloutFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, features, fmean, steps, greedy, start_id, seed, rank, out, *params):
-        """out: dict that receives "ids" [B, steps], "fed" [B, steps] (the tokens fed) and "alphas", the packed attention tape"""
+        """out: dict that receives "ids" [B, steps], "fed" [B, steps] (the tokens fed) and "alphas", the packed attention tape;
+        it may bring "group" = (src, S): `features` / `fmean` are then src's rows S times each (`_DecoderSetup`)"""
         lib, m, dev = L.load(), model, features.device
         B, P, C = features.shape
         E, H, V = m.embed_size, m.hidden_size, m.vocab_size
         pi = PackInfo.get([steps] * B, dev)
         N = pi.N
-        s = _DecoderSetup(lib, m, features, fmean, N)
+        s = _DecoderSetup(lib, m, features, fmean, N, group=out.pop("group", None))
         w, tapes = s.ssa_tables()
         ids = torch.empty(B, steps, dtype=torch.int64, device=dev)
         fed = torch.empty(B, steps, dtype=torch.int64, device=dev)
@@ -543,7 +562,7 @@ class ShowAttendTellModel(nn.Module):
             self.last_ss_inputs, self.last_ss_seed = ss["used"], ss["seed"]
         return out
 
-    def rollout(self, features, fmean, steps=20, greedy=False, start_id=1):
+    def rollout(self, features, fmean, steps=20, greedy=False, start_id=1, num_samples=1):
         """The decoder half of `forward` fed its OWN tokens (self-critical sequence training, Rennie et al. 2017): step 0 takes
         <start>, step t >= 1 the token of step t-1 -- a DRAW from softmax(logits of step t-1), or with `greedy` their arg-max.
         Returns (ids i64 [B, steps], logits f32 [steps * B, V]), logits row t * B + b those of step t of row b.  One
@@ -561,7 +580,17 @@ class ShowAttendTellModel(nn.Module):
         Either way `last_alphas` is the packed [steps * B, P] attention tape: `.view(steps, B, P)` is where the model looked for
         each word it emitted.  `ss_prob` and `alpha_c` do not act on a rollout, and `last_attention_penalty` is set to None:
         `sat_attention_coverage` counts every step a row is alive in, and here every row is alive behind its <end>, so the penalty
-        would pull the maps of steps the loss masks towards covering the image.  (A length-masked penalty is a separate change.)"""
+        would pull the maps of steps the loss masks towards covering the image.  (A length-masked penalty is a separate change.)
+
+        num_samples = S > 1 (sampled only; with greedy=True a ValueError, an arg-max decode has one answer): S captions per image.
+        features and fmean are repeated to R = B * S rows (row r = b * S + s) and the same call runs on R rows with draw row r: ids
+        [B, S, steps], logits [steps * R, V] with row t * R + r, `last_rollout_inputs` [R, steps] and `last_alphas` [steps * R, P]
+        -- bit for bit the rollout of the inputs repeated by hand.  The attention encoding of the features is computed once per
+        image and repeated (`_context_encode_group`); the repeated features and their encoding are S x [B, P, C] each while the
+        graph lives.  The R-row gradients of features and fmean come back summed per image (`sat_group_sum_rows`)."""
+        S = check_group(num_samples)[0]
+        if greedy and S > 1:
+            raise ValueError("rollout(greedy=True) is an arg-max decode, which has one answer per image: num_samples must be 1")
         if not self.training:
             raise RuntimeError("ShowAttendTellModel.rollout is a training forward (model.train()); eval mode decodes with sample()")
         self.dropout_plan(sampling=True, what="a rollout")
@@ -574,6 +603,9 @@ class ShowAttendTellModel(nn.Module):
             raise TypeError("features and fmean must be float32")
         features, fmean = features.contiguous(), fmean.contiguous()
         out = {}
+        if S > 1:
+            out["group"] = (features.detach(), S)
+            features, fmean = repeat_rows(features, S), repeat_rows(fmean, S)
         if greedy:
             with torch.no_grad():
                 logits = _AttendRolloutFn.apply(self, features, fmean, steps, True, int(start_id), 0, 0, out, *self._params())
@@ -583,16 +615,20 @@ class ShowAttendTellModel(nn.Module):
                                             *self._params())
             self.last_rollout_seed = seed
         self.last_rollout_inputs, self.last_alphas, self.last_attention_penalty = out["fed"], out["alphas"], None
-        return out["ids"], logits
+        ids = out["ids"]
+        return (ids if S == 1 else ids.view(-1, S, steps)), logits
 
-    def scst_forward(self, images, image_index, scorer, end_id=2, steps=20):
+    def scst_forward(self, images, image_index, scorer, end_id=2, steps=20, num_samples=1, baseline="greedy"):
         """The self-critical loss of one batch (`scst.SelfCritical.attend`) behind the conv stack: sampled rollout, arg-max rollout
         of the same policy as the baseline, CIDEr of both, weighted cross entropy.  image_index: the corpus image of every row, as
         for `CiderScorer.score`.  With `finetune(allow=True)` `loss.backward()` also reaches the conv stack.  The `SelfCritical`
-        object (its last_reward, last_baseline, last_ids, last_greedy_ids) is kept as `last_scst`."""
+        object (its last_reward, last_baseline, last_ids, last_greedy_ids) is kept as `last_scst`.  num_samples, baseline:
+        `SelfCritical`'s -- S sampled captions per image from ONE pass of the conv stack, baseline "greedy" or "sample_mean"
+        (leave-one-out: no arg-max rollout)."""
         self.dropout_plan(sampling=True, what="a rollout (scst_forward)")     # refuse before the conv stack runs
+        check_group(num_samples, baseline)
         feats, fmean = self._encode(images)
-        self.last_scst = SelfCritical(scorer, end_id)
+        self.last_scst = SelfCritical(scorer, end_id, num_samples=num_samples, baseline=baseline)
         return self.last_scst.attend(self, feats, fmean, image_index, steps)
 
     @torch.no_grad()

@@ -774,6 +774,91 @@ __global__ __launch_bounds__(256) void scst_weights_kernel(const int64_t* __rest
     }
 }
 
+// The same weights for S sampled captions per image (Luo 2020, arXiv:2003.09971), rows image-major: row r = b * S + s.  len and M as
+// above over all R = B * S rows.  mode 0: advantage[r] = reward[r] - baseline_img[r / S].  mode 1 (leave-one-out): advantage[r] =
+// (sum over s' != s, ascending, of (reward[r] - reward[b * S + s'])) / (S - 1) -- a sum of DIFFERENCES, so that S equal rewards give
+// exactly +0 -- and baseline_out[r] = (sum over s' != s of reward[b * S + s']) / (S - 1).  One workgroup whatever R is: every thread
+// owns the rows r = tid, tid + 256, ... in both passes, so nothing read was written by another thread but sh[].
+__global__ __launch_bounds__(256) void scst_weights_group_kernel(const int64_t* __restrict__ ids, long stride, int B, int S, int T,
+                                                                 int64_t end_id, const double* __restrict__ reward,
+                                                                 const double* __restrict__ baseline_img, int mode,
+                                                                 const double* __restrict__ denom, float* __restrict__ w,
+                                                                 int32_t* __restrict__ len, double* __restrict__ m_out,
+                                                                 double* __restrict__ advantage, double* __restrict__ baseline_out) {
+    __shared__ long long sh[256];
+    const int tid = threadIdx.x;
+    const long R = (long)B * S;
+    long long tot = 0;
+    for (long r = tid; r < R; r += 256) {
+        const int64_t* row = ids + r * stride;
+        int n = 0;
+        while (n < T && row[n] != end_id) ++n;
+        n = n + 1 < T ? n + 1 : T;
+        len[r] = n;
+        tot += n;
+    }
+    sh[tid] = tot;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (tid < k) sh[tid] += sh[tid + k];
+        __syncthreads();
+    }
+    const double M = denom ? *denom : (double)sh[0];
+    if (tid == 0) m_out[0] = M;
+    for (long r = tid; r < R; r += 256) {
+        const long b = r / S;
+        const int s = (int)(r - b * S);
+        const double rr = reward[r];
+        double adv, base;
+        if (mode == 0) {
+            base = baseline_img ? baseline_img[b] : 0.0;
+            adv = rr - base;
+        } else {
+            const double* g = reward + b * S;
+            double da = 0.0, sb = 0.0;
+            for (int o = 0; o < S; ++o) {
+                if (o == s) continue;
+                const double ro = g[o];
+                da += rr - ro;
+                sb += ro;
+            }
+            const double n1 = (double)(S - 1);
+            adv = da / n1;
+            base = sb / n1;
+        }
+        advantage[r] = adv;
+        if (baseline_out) baseline_out[r] = base;
+        const float wr = (float)(adv / M);
+        const int n = len[r];                   // the thread that wrote len[r] reads it back
+        for (int t = 0; t < T; ++t) w[(long)t * R + r] = t < n ? wr : 0.0f;
+    }
+}
+
+// out[b][j] = ((in[b*S][j] + in[b*S+1][j]) + in[b*S+2][j]) + ... (f32, ascending s): the backward of "one image's row feeds S rows".
+// An item is one 16-byte chunk of the first 4 * nv columns of an output row, or one of the W - 4 * nv columns behind them (VEC: nv =
+// W / 4 when strides and pointers are 16-byte granular, else 0: every column is a scalar item).
+template <bool VEC>
+__global__ __launch_bounds__(EW_BLOCK) void group_sum_rows_kernel(const float* __restrict__ in, long ld_in, int B, int S, long W, long nv,
+                                                                  float* __restrict__ out, long ld_out) {
+    const long per = nv + (W - 4 * nv);
+    const long total = (long)B * per;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long b = i / per, k = i - b * per;
+        const float* src = in + b * S * ld_in;
+        float* dst = out + b * ld_out;
+        if (VEC && k < nv) {
+            f32x4 acc = *(const f32x4*)(src + 4 * k);
+            for (int s = 1; s < S; ++s) acc += *(const f32x4*)(src + (long)s * ld_in + 4 * k);
+            *(f32x4*)(dst + 4 * k) = acc;
+        } else {
+            const long j = 4 * nv + (k - nv);
+            float acc = src[j];
+            for (int s = 1; s < S; ++s) acc += src[(long)s * ld_in + j];
+            dst[j] = acc;
+        }
+    }
+}
+
 __device__ __forceinline__ void sum_scale_block(const float* __restrict__ v, int n, float scale, float* out) {
     __shared__ float sh[256];
     float s = 0.0f;
@@ -1401,6 +1486,34 @@ extern "C" int sat_scst_weights(const int64_t* ids, int64_t stride, int B, int T
     if (!ids || !reward || !w || !len || !m_out || B < 1 || T < 1 || stride < T || (long)B * T > 0x7fffffffL) return SAT_ERR_ARG;
     hipLaunchKernelGGL(scst_weights_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ids, (long)stride, B, T, end_id, reward,
                        baseline, denom, w, len, m_out);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
+extern "C" int sat_scst_weights_group(const int64_t* ids, int64_t stride, int B, int S, int T, int64_t end_id, const double* reward,
+                                      const double* baseline_img, int mode, const double* denom, float* w, int32_t* len,
+                                      double* m_out, double* advantage, double* baseline_out, sat_stream_t stream) {
+    if (!ids || !reward || !w || !len || !m_out || !advantage || B < 1 || S < 1 || T < 1 || stride < T) return SAT_ERR_ARG;
+    if ((mode != 0 && mode != 1) || (mode == 1 && (S < 2 || baseline_img))) return SAT_ERR_ARG;
+    if ((int64_t)B * S > 0x7fffffffL || (int64_t)B * S * T > 0x7fffffffL) return SAT_ERR_ARG;
+    if (S > 256) return SAT_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(scst_weights_group_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ids, (long)stride, B, S, T, end_id,
+                       reward, baseline_img, mode, denom, w, len, m_out, advantage, baseline_out);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
+extern "C" int sat_group_sum_rows(const float* in, int64_t ld_in, int B, int S, int64_t W, float* out, int64_t ld_out,
+                                  sat_stream_t stream) {
+    if (!in || !out || B < 1 || S < 1 || W < 1 || ld_in < W || ld_out < W) return SAT_ERR_ARG;
+    const float* in_end = in + ((int64_t)B * S - 1) * ld_in + W;
+    const float* out_end = out + ((int64_t)B - 1) * ld_out + W;
+    if ((uintptr_t)in < (uintptr_t)out_end && (uintptr_t)out < (uintptr_t)in_end) return SAT_ERR_ARG;      // the two overlap
+    const bool vec = W >= 4 && !(ld_in & 3) && !(ld_out & 3) && !(((uintptr_t)in | (uintptr_t)out) & 15);
+    const long nv = vec ? (long)(W / 4) : 0;
+    const dim3 grid(ew_grid((long)B * (nv + (W - 4 * nv))));
+    if (vec) hipLaunchKernelGGL(group_sum_rows_kernel<true>, grid, dim3(EW_BLOCK), 0, (hipStream_t)stream, in, (long)ld_in, B, S, (long)W, nv, out, (long)ld_out);
+    else hipLaunchKernelGGL(group_sum_rows_kernel<false>, grid, dim3(EW_BLOCK), 0, (hipStream_t)stream, in, (long)ld_in, B, S, (long)W, nv, out, (long)ld_out);
     SAT_LAUNCH_CHECK();
     return SAT_OK;
 }

@@ -715,22 +715,29 @@ class DecoderRNN(nn.Module):
         self.last_dropout_seed = draw_ss_seed()
         return plan + (self.last_dropout_seed, int(self.ss_rank))
 
-    def rollout(self, features, steps=20):
+    def rollout(self, features, steps=20, num_samples=1):
         """`sample` with a DRAW from softmax(logits) where `sample` takes the arg-max, in training form (self-critical sequence
         training, Rennie et al. 2017): (ids i64 [B, steps], logits f32 [steps * B, V]), logits row t * B + b those of step t of row
         b.  The logits carry autograd: their backward is the teacher-forced backward on ids[:, :steps-1].  Training mode only.  The
         seed comes from torch's CPU generator (`draw_ss_seed`) and is kept as `last_rollout_seed`; the draws are `ss_rank`'s stream.
-        Rows keep running behind their <end>: `scst_loss` masks them."""
+        Rows keep running behind their <end>: `scst_loss` masks them.
+        num_samples = S > 1: S captions per image.  Every image's features are repeated to R = B * S rows (row r = b * S + s, as
+        in `sample_stochastic`) and the same call runs on R rows with draw row r: ids [B, S, steps], logits [steps * R, V] with row
+        t * R + r -- bit for bit the rollout of `features.repeat_interleave(S, 0)` from the same seed.  The R-row gradient of the features comes
+        back summed per image (`sat_group_sum_rows`)."""
+        from .scst import check_group, repeat_rows
+        S = check_group(num_samples)[0]
         if not self.training:
             raise RuntimeError("DecoderRNN.rollout is a training forward (decoder.train()); eval mode decodes with sample()")
         self.dropout_plan(sampling=True, what="a rollout")
-        features = _f32c(features, "features")
+        features = repeat_rows(_f32c(features, "features"), S)
         seed = draw_ss_seed()
         names, tensors = zip(*self.named_parameters())
         out = {}
         logits = _RolloutFn.apply(features, int(steps), seed, int(self.ss_rank), out, names, *tensors)
         self.last_rollout_seed = seed
-        return out["ids"], logits
+        ids = out["ids"]
+        return (ids if S == 1 else ids.view(-1, S, ids.shape[1])), logits
 
     @torch.no_grad()
     def sample(self, features, states=None):
@@ -938,13 +945,14 @@ class ShowAndTell(nn.Module):
     def forward(self, images, captions, lengths):
         return self.decoder(self.encoder(images), captions, lengths)
 
-    def scst_forward(self, images, image_index, scorer, end_id=2):
+    def scst_forward(self, images, image_index, scorer, end_id=2, num_samples=1, baseline="greedy"):
         """The self-critical loss of one batch (`scst.SelfCritical`) behind the encoder's forward, so that `loss.backward()` also
         trains fc / bn.  image_index: the corpus image of every row, as for `CiderScorer.score`.  The `SelfCritical` object (its
-        last_reward, last_baseline, last_ids) is kept as `last_scst`."""
+        last_reward, last_baseline, last_ids) is kept as `last_scst`.  num_samples, baseline: `SelfCritical`'s -- S captions per
+        image from ONE encoder pass, baseline "greedy" or "sample_mean" (leave-one-out; no greedy decode)."""
         from .scst import SelfCritical
         self.decoder.dropout_plan(sampling=True, what="a rollout (scst_forward)")            # before the encoder runs
-        self.last_scst = SelfCritical(scorer, end_id)
+        self.last_scst = SelfCritical(scorer, end_id, num_samples=num_samples, baseline=baseline)
         return self.last_scst(self.decoder, self.encoder(images), image_index)
 
     @torch.no_grad()

@@ -21,7 +21,7 @@ from .decoder import LSTMWorkspaces, VocabCE, decoder_backward, decoder_forward,
 from .models import ShowAndTell, draw_ss_seed, fc_bn1d_backward, fc_bn1d_forward
 from .optim import check_max_norm, check_weight_decay, exempt_array, group_weight_decay, merge_ranges
 from .pack import PackInfo
-from .scst import SelfCritical, ce_rows_weighted, scst_weights
+from .scst import SelfCritical, ce_rows_weighted, check_group, group_sum_rows, scst_weights, scst_weights_group
 from .watch import ResidencyWatch, StatusRing
 
 
@@ -311,20 +311,25 @@ class TrainStep:
             on_bucket_ready(2)   # encoder head + embedding gradients (and the loss slot) are final
         return loss_slot
 
-    def _step_bufs(self, B, N, dev):
-        """the buffers a step of B images and N packed rows owns (one set is kept: another (B, N) replaces it)"""
-        bufs = self._bufs.get((B, N))
+    def _step_bufs(self, B, N, dev, R=None):
+        """the buffers a step of B images, R decoder rows (None: B) and N packed rows owns (one set is kept: another (B, N, R)
+        replaces it).  R != B, S sampled captions per image: the set also holds the features repeated to R rows and their
+        gradient, feat_rows and d_feat_rows [R, E]"""
+        R = B if R is None else R
+        bufs = self._bufs.get((B, N, R))
         if bufs is None:
             self._bufs.clear()
             enc, dec = self.model.encoder, self.model.decoder
             E, V, F = dec.embed_size, dec.vocab_size, enc.resnet.feature_dim
             wsb = self.lib.sat_fc_bn1d_ws_bytes(B, F, E)
-            bufs = self._bufs[(B, N)] = dict(
+            bufs = self._bufs[(B, N, R)] = dict(
                 targets=torch.empty(N, dtype=torch.int64, device=dev), logits=L.logits_buffer(N, V, dev),
                 row_loss=torch.empty(N, device=dev), feats=torch.empty(B, E, device=dev),
                 xhat=torch.empty(B, E, device=dev), rstd=torch.empty(E, device=dev),
                 head_ws=torch.empty(max(wsb // 4, B * E), device=dev), d_feat=torch.empty(B, E, device=dev),
                 pooled=torch.empty(B, F, device=dev))
+            if R != B:
+                bufs["feat_rows"], bufs["d_feat_rows"] = torch.empty(R, E, device=dev), torch.empty(R, E, device=dev)
         return bufs
 
     def _head_forward(self, images, bufs, next_images):
@@ -357,14 +362,20 @@ class TrainStep:
         words, nw = self.lstm_ws.fault_words
         L.check(lib.sat_step_fault_flag(words, nw, L.ptr(self._fault_sticky), L.ptr(self.fault_slot), L.stream()), "sat_step_fault_flag")
 
-    def scst_forward_backward(self, images, image_index, scorer, end_id=2, steps=20, next_images=None):
+    def scst_forward_backward(self, images, image_index, scorer, end_id=2, steps=20, next_images=None, num_samples=1,
+                              baseline="greedy"):
         """`forward_backward` for the self-critical loss (`scst.SelfCritical`, Rennie et al. 2017): same look-ahead, cached [B, E]
         features accepted, gradients straight into the flat buffer, loss into the loss slot, fault flag.  The decoder part is the
         sampled rollout (`sat_rollout_decoder_fwd`), the greedy decode as baseline, CIDEr of both on the device, `sat_scst_weights`
         + `sat_ce_rows_weighted` in place on the step's logits, and the teacher-forced backward on the tokens drawn.  The decoder
         arithmetic of this step is EXACT F32 whatever `decoder_gemm_dtype` says: the draws are taken from exact-f32 logits and
         the backward runs on them (the bf16 decoder GEMMs are not wired into this step).  Rewards, baseline and ids of the step
-        are kept on `last_scst`."""
+        are kept on `last_scst`.
+        num_samples = S > 1, baseline "greedy" / "sample_mean": `SelfCritical`'s.  The head runs on the B images once; its [B, E]
+        features are repeated to R = B * S rows, the decoder buffers hold R rows and R * steps packed rows, the weights come from
+        `sat_scst_weights_group`, and the decoder's d_feat [R, E] is summed per image (`sat_group_sum_rows`) in front of the head's
+        backward.  With the defaults the calls are those made without the keywords."""
+        S, baseline = check_group(num_samples, baseline)             # host checks, before anything is launched
         lib, model, flat = self.lib, self.model, self.flat
         dec = model.decoder
         if not model.training:
@@ -372,21 +383,33 @@ class TrainStep:
         dec.dropout_plan(sampling=True, what="a rollout (scst_step)")
         dev = images.device
         B, steps = images.shape[0], int(steps)
-        bufs = self._step_bufs(B, B * steps, dev)
+        R = B * S
+        bufs = self._step_bufs(B, R * steps, dev, R)
         feats_in, pooled = self._head_forward(images, bufs, next_images)
         params = dict(dec.named_parameters())
         loss_slot = flat.grads[flat.loss_slot:flat.loss_slot + 1]
         seed = draw_ss_seed()
-        ids, logits, tapes, pi = rollout_forward(lib, feats_in, params, steps, seed, dec.ss_rank, self.lstm_ws, logits=bufs["logits"])
+        rows_in = feats_in
+        if S > 1:
+            rows_in = bufs["feat_rows"]                              # row b * S + s = the features of image b (data movement)
+            rows_in.view(B, S, -1).copy_(feats_in.unsqueeze(1).expand(B, S, -1))
+        ids, logits, tapes, pi = rollout_forward(lib, rows_in, params, steps, seed, dec.ss_rank, self.lstm_ws, logits=bufs["logits"])
         dec.last_rollout_seed = seed
-        sc = self.last_scst = SelfCritical(scorer, end_id)
-        sc.last_reward, sc.last_baseline, sc.last_greedy_ids = sc.rewards(dec, feats_in, ids, image_index)
-        sc.last_ids = ids
-        w, _, _ = scst_weights(ids, sc.last_reward, sc.last_baseline, end_id)
+        sc = self.last_scst = SelfCritical(scorer, end_id, num_samples=S, baseline=baseline)
+        if S == 1:
+            sc.last_reward, sc.last_baseline, sc.last_greedy_ids = sc.rewards(dec, feats_in, ids, image_index)
+            sc.last_ids = ids
+            w, _, _ = scst_weights(ids, sc.last_reward, sc.last_baseline, end_id)
+        else:
+            sc.last_ids = ids.view(B, S, steps)
+            sc.last_reward, base, sc.last_greedy_ids = sc.rewards(dec, feats_in, sc.last_ids, image_index)
+            w, _, _, sc._advantage, sc.last_baseline = scst_weights_group(sc.last_ids, sc.last_reward, base, end_id)
         ce_rows_weighted(logits[:, :dec.vocab_size], ids, w, write_grad=True, loss_out=loss_slot)
         g = {name: flat.grad("decoder." + name) for name in params}
-        g["features"] = bufs["d_feat"]
+        g["features"] = bufs["d_feat"] if S == 1 else bufs["d_feat_rows"]
         decoder_backward(lib, logits, tapes, params, pi, g, self.lstm_ws)
+        if S > 1:
+            group_sum_rows(bufs["d_feat_rows"], S, out=bufs["d_feat"])
         self._head_backward(bufs, pooled, feats_in)
         return loss_slot
 
@@ -540,10 +563,12 @@ class TrainStep:
         self.optimizer_step(lr)
         return loss
 
-    def scst_step(self, images, image_index, scorer, lr=None, next_images=None, end_id=2, steps=20):
+    def scst_step(self, images, image_index, scorer, lr=None, next_images=None, end_id=2, steps=20, num_samples=1,
+                  baseline="greedy"):
         """One whole self-critical iteration (`scst_forward_backward` + `optimizer_step`); returns the loss as a 1-element device
-        tensor (no host sync).  The decoder arithmetic of this step is exact f32 whatever `decoder_gemm_dtype` is."""
-        loss = self.scst_forward_backward(images, image_index, scorer, end_id, steps, next_images).clone()
+        tensor (no host sync).  The decoder arithmetic of this step is exact f32 whatever `decoder_gemm_dtype` is.  num_samples,
+        baseline: S sampled captions per image and the baseline they are judged against (`scst_forward_backward`)."""
+        loss = self.scst_forward_backward(images, image_index, scorer, end_id, steps, next_images, num_samples, baseline).clone()
         self.optimizer_step(lr)
         return loss
 
