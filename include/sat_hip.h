@@ -852,6 +852,52 @@ int sat_sample_decode(const float* features, const float* embed, const float* co
                       float top_p, uint64_t seed, int rank, float* h, float* c, float* h_tmp, float* x_tmp, int64_t* ids,
                       int64_t ids_stride, float* logp, int32_t* kept, float* logits_out, int64_t ldl, void* workspace,
                       int64_t ws_bytes, sat_stream_t stream);
+/* Constrained sampling (added within ABI 18): banned ids, n-gram blocking and a repetition penalty on the filtered draw.
+ * At step t row r has the prefix y_0 .. y_{t-1}, the tokens this decode drew for the row at earlier steps (the start token is not
+ * part of it), read from prefix[r*prefix_stride + j], j < t.  The row of logits x[0..V) is replaced by x', and EVERYTHING ELSE IS
+ * sat_sample_filtered's CONTRACT APPLIED TO x': candidates, total order, top-k, nucleus, the Gumbel-max draw with the same Philox
+ * counters, kept, and logp under the filtered distribution of x'.  The kernel never writes the row: a caller's logits stay raw.
+ *   penalty: repetition_penalty = theta (finite, > 0; 1: off).  For every v among the prefix tokens, once however often it
+ *     occurs: x'[v] = x[v] > 0 ? x[v] / theta : x[v] * theta -- ONE correctly rounded f32 division or multiplication.  -inf and NaN
+ *     stay what they are.
+ *   bans: x'[v] = -inf (no candidate) for v in the banned set of sat_beam_step_ex's four rules with i = t: (1) suppress_ids;
+ *     (2) end_id while t < min_length; (3) y_{t-1} if block_repeat and t >= 1; (4) if no_repeat_ngram = n >= 1 and t >= n: every
+ *     y_{j+n-1} with 0 <= j <= t-n and y[j..j+n-2] == y[t-n+1..t-1] (n = 1: every token already drawn; overlap with the tail
+ *     counts).  A ban wins over the penalty.
+ *   scope: every step of every row, also behind the row's end_id (rows keep running there; sat_kept_tokens truncates): there is no
+ *     finished row.  A row whose every candidate is banned is a row without a finite logit: id 0, kept 0, logp -inf.
+ *   memory safety: prefix tokens and suppressed ids outside [0, V) set nothing; in the n-gram compare every such prefix token is
+ *     one and the same "no token".
+ * sat_sample_filtered_ex: sat_sample_filtered under `c` at step t.  c == NULL, every field off, or a step at which `c` changes
+ *   nothing (no suppressed id, t >= min_length, and t == 0 or no rule that reads the prefix, or t < n with n-gram blocking alone):
+ *   the launch of sat_sample_filtered, bit-identical outputs; prefix is then not read and may be NULL.  workspace:
+ *   sat_sample_filtered_ws_bytes.
+ * sat_sample_decode_ex: sat_sample_decode's loop with the ids buffer itself as the prefix (row b: ids[b*ids_stride + j]);
+ *   workspace: sat_sample_decode_ex_ws_bytes (= sat_sample_decode_ws_bytes).
+ * Errors beside those of the plain entry points, before anything is enqueued.  SAT_ERR_ARG: n_suppress > 256 or > 0 with
+ *   suppress_ids NULL, a negative field, block_repeat not 0 / 1, repetition_penalty not finite or <= 0, min_length > 0 with
+ *   end_id < 0, prefix NULL (or prefix_stride < 0) at a step t > 0 whose rules read it.  SAT_ERR_UNSUPPORTED: a step whose rules
+ *   read the prefix with t >= 64 (lane j of one wave keeps y_j); steps > 64 in the loop under active constraints; V > 32768. */
+typedef struct {
+    const int64_t* suppress_ids;   /* device, or NULL with n_suppress 0 */
+    int n_suppress;                /* 0..256 */
+    int min_length;                /* >= 0; > 0 needs end_id >= 0 */
+    int no_repeat_ngram;           /* 0 off, n >= 1 */
+    int block_repeat;              /* 0 / 1 */
+    float repetition_penalty;      /* finite, > 0; 1 off */
+    int64_t end_id;                /* < 0: none */
+} sat_sample_constraints;
+int sat_sample_filtered_ex(const float* logits /*[R, ldl]*/, int64_t ldl, int R, int V, float temperature, int top_k, float top_p,
+                           uint64_t seed, int t, int rank, int64_t* ids, int64_t ids_stride, float* logp /*[R] or NULL*/,
+                           int32_t* kept /*[R] or NULL*/, const sat_sample_constraints* c /*[host], nullable*/,
+                           const int64_t* prefix, int64_t prefix_stride, void* workspace, int64_t ws_bytes, sat_stream_t stream);
+int64_t sat_sample_decode_ex_ws_bytes(int B, int E, int H, int V, int num_layers);
+int sat_sample_decode_ex(const float* features, const float* embed, const float* const* lstm_w /*[host]*/, int num_layers,
+                         const float* lin_w, const float* lin_b, int B, int E, int H, int V, int steps, float temperature, int top_k,
+                         float top_p, uint64_t seed, int rank, float* h, float* c, float* h_tmp, float* x_tmp, int64_t* ids,
+                         int64_t ids_stride, float* logp, int32_t* kept, float* logits_out, int64_t ldl,
+                         const sat_sample_constraints* cons /*[host], nullable*/, void* workspace, int64_t ws_bytes,
+                         sat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * CIDEr of decoded id rows against reference captions (added within ABI 18).

@@ -56,6 +56,12 @@ class SatBeamConstraints(C.Structure):
                 ("block_repeat", C.c_int), ("length_penalty", C.c_float)]
 
 
+class SatSampleConstraints(C.Structure):
+    """mirror of `sat_sample_constraints` (include/sat_hip.h)"""
+    _fields_ = [("suppress_ids", _vp), ("n_suppress", C.c_int), ("min_length", C.c_int), ("no_repeat_ngram", C.c_int),
+                ("block_repeat", C.c_int), ("repetition_penalty", C.c_float), ("end_id", C.c_int64)]
+
+
 class SatDecoderModel(C.Structure):
     """mirror of `sat_decoder_model` (include/sat_hip.h): one DecoderRNN of an ensemble, host struct of device pointers"""
     _fields_ = [("features", _vp), ("embed", _vp), ("lstm_w", C.POINTER(_vp)), ("num_layers", C.c_int), ("lin_w", _vp), ("lin_b", _vp),
@@ -240,6 +246,11 @@ SIGNATURES = {
     "sat_sample_decode_ws_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "sat_sample_decode": (_i, [_vp, _vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _f, C.c_uint64, _i, _vp, _vp, _vp,
                                _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "sat_sample_filtered_ex": (_i, [_vp, _i64, _i, _i, _f, _i, _f, C.c_uint64, _i, _i, _vp, _i64, _vp, _vp, C.POINTER(SatSampleConstraints),
+                                    _vp, _i64, _vp, _i64, _vp]),
+    "sat_sample_decode_ex_ws_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "sat_sample_decode_ex": (_i, [_vp, _vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _f, C.c_uint64, _i, _vp, _vp, _vp,
+                                  _vp, _vp, _i64, _vp, _vp, _vp, _i64, C.POINTER(SatSampleConstraints), _vp, _i64, _vp]),
     "sat_dropout_f32": (_i, [_vp, _i64, _vp, _i64, _i, _i, _f, C.c_uint64, _i, _i, _vp]),
     "sat_clamp_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp]),
     "sat_clamp_adam_step_guarded": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp, _vp]),
@@ -267,7 +278,8 @@ ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_at
                     "sat_beam_decode_groups_ws_bytes", "sat_beam_decode_groups", "sat_ce_rows_ls", "sat_vocab_ce_fwd_bf16_ls",
                     "sat_grad_sumsq_partials", "sat_grad_sumsq_ws_bytes", "sat_grad_sumsq", "sat_adamw_step",
                     "sat_ensemble_logprobs", "sat_beam_decode_ensemble_ws_bytes", "sat_beam_decode_ensemble",
-                    "sat_consensus_ws_bytes", "sat_consensus_rerank", "sat_scst_weights_group", "sat_group_sum_rows")
+                    "sat_consensus_ws_bytes", "sat_consensus_rerank", "sat_scst_weights_group", "sat_group_sum_rows",
+                    "sat_sample_filtered_ex", "sat_sample_decode_ex_ws_bytes", "sat_sample_decode_ex")
 
 _lib = None
 

@@ -27,7 +27,7 @@ import torch.nn as nn
 from . import _lib as L
 from .attend_bwd import PARAM_ORDER, attend_backward
 from .decoder import dropout_rows
-from .models import check_beam_constraints, check_beam_groups, check_dropout_p, check_sample_args, draw_ss_seed, lookahead_stream, refuse_dropout_with, stochastic_result
+from .models import check_beam_constraints, check_beam_groups, check_dropout_p, check_sample_args, check_sample_constraints, draw_ss_seed, lookahead_stream, refuse_dropout_with, stochastic_result
 from .pack import PackInfo
 from .scst import SelfCritical, check_group, repeat_rows
 from .vgg import VGG16_FEATURES, VggFeatures, VggProgram, _VggFn  # noqa: F401  (VggFeatures is re-exported by the package)
@@ -662,15 +662,22 @@ class ShowAttendTellModel(nn.Module):
         return (ids, d.maps((B,))) if return_alphas else ids
 
     @torch.no_grad()
-    def sample_stochastic(self, images, states=None, **kw):
-        """`sample_stochastic_features` behind the conv stack (arguments checked before it runs)."""
+    def sample_stochastic(self, images, states=None, *, suppress_ids=None, min_length=0, no_repeat_ngram_size=0, block_repeat=False,
+                          repetition_penalty=1.0, end_id=None, **kw):
+        """`sample_stochastic_features` behind the conv stack, its constraints included (arguments checked before it runs)."""
         check_sample_args(kw.get("temperature", 1.0), kw.get("top_k", 0), kw.get("top_p", 1.0), kw.get("num_samples", 1), kw.get("seed"))
+        cons = dict(suppress_ids=suppress_ids, min_length=min_length, no_repeat_ngram_size=no_repeat_ngram_size,
+                    block_repeat=block_repeat, repetition_penalty=repetition_penalty, end_id=end_id)
+        if check_sample_constraints(vocab_size=self.vocab_size, steps=kw.get("steps", 20), **cons).active:
+            kw.update(cons)
         feats, _ = self._encode(images)
         return self.sample_stochastic_features(feats, states, **kw)
 
     @torch.no_grad()
     def sample_stochastic_features(self, features, states=None, steps=20, start_id=1, temperature=1.0, top_k=0, top_p=1.0,
-                                   num_samples=1, seed=None, return_logprobs=False, return_logits=False, return_alphas=False):
+                                   num_samples=1, seed=None, return_logprobs=False, return_logits=False, return_alphas=False, *,
+                                   suppress_ids=None, min_length=0, no_repeat_ngram_size=0, block_repeat=False,
+                                   repetition_penalty=1.0, end_id=None):
         """`sample_features` with a DRAW where it takes the arg-max: every step's token comes from softmax(logits / temperature)
         restricted to the top_k most likely tokens (0: all) and then to the nucleus, the shortest most-likely-first prefix holding
         top_p of the remaining mass (1: all).  The loop is `sample_features`' own -- `_EvalDecoder.step`, the classifier as one
@@ -680,11 +687,15 @@ class ShowAttendTellModel(nn.Module):
         Returns ids i64 [B, steps], or [B, S, steps] with num_samples = S > 1 (features and states repeated per image, draw row
         b * S + s).  Then, in this order, as asked: return_logprobs a dict(logp f32, kept i32) shaped like ids; return_logits the
         exact-f32 logits [steps, B*S, V]; return_alphas the attention maps f32 [B, steps, P] ([B, S, steps, P]).  seed=None takes
-        `draw_ss_seed()`; the seed used stays on `last_sample_seed`; the draws are `ss_rank`'s stream."""
+        `draw_ss_seed()`; the seed used stays on `last_sample_seed`; the draws are `ss_rank`'s stream.
+        Constraints as `DecoderRNN.sample_stochastic` documents them (all off by default: the calls are then the ones above): the
+        draw of every step is `sat_sample_filtered_ex` with the ids drawn so far as the prefix; at most 64 steps."""
         tau, top_k, top_p, S, seed = check_sample_args(temperature, top_k, top_p, num_samples, seed)
         steps = int(steps)
         if steps < 1:
             raise ValueError("steps must be >= 1")
+        cons = check_sample_constraints(suppress_ids, min_length, no_repeat_ngram_size, block_repeat, repetition_penalty, end_id,
+                                        self.vocab_size, steps)
         d = _EvalDecoder(self, features, states, S, steps, start_id, return_alphas)
         lib, st, dev, cls = d.lib, L.stream(), features.device, self.classifier
         R, P, C, E, H, V = d.dims
@@ -702,9 +713,13 @@ class ShowAttendTellModel(nn.Module):
             lg, col = logits[i if return_logits else 0], ids[:, i]
             L.check(lib.sat_vocab_logits_fwd(L.ptr(d.Z), L.ptr(cls.weight), L.ptr(cls.bias), R, E, V, lg.data_ptr(), ldl, st),
                     "sat_vocab_logits_fwd")
-            L.check(lib.sat_sample_filtered(lg.data_ptr(), ldl, R, V, tau, top_k, top_p, seed, i, int(self.ss_rank), col.data_ptr(),
-                                            ids.stride(0), logp[i].data_ptr() if return_logprobs else None,
-                                            kept[i].data_ptr() if return_logprobs else None, L.ptr(ws), wsb, st), "sat_sample_filtered")
+            head = (lg.data_ptr(), ldl, R, V, tau, top_k, top_p, seed, i, int(self.ss_rank), col.data_ptr(), ids.stride(0),
+                    logp[i].data_ptr() if return_logprobs else None, kept[i].data_ptr() if return_logprobs else None)
+            if cons.active:
+                L.check(lib.sat_sample_filtered_ex(*head, cons.struct(dev), ids.data_ptr(), ids.stride(0), L.ptr(ws), wsb, st),
+                        "sat_sample_filtered_ex")
+            else:
+                L.check(lib.sat_sample_filtered(*head, L.ptr(ws), wsb, st), "sat_sample_filtered")
             return col.data_ptr(), ids.stride(0), d.ctxb
 
         d.run(pick)

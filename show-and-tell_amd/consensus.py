@@ -115,7 +115,9 @@ class ConsensusReranker:
     @torch.no_grad()
     def decode_samples(self, model, inputs, num_samples, **sample_kw):
         """the same over `model.sample_stochastic(inputs, num_samples=S, **sample_kw)`: the consensus pick of S draws per image,
-        equally weighted.  last_scores is None."""
+        equally weighted.  last_scores is None.  sample_kw also carries the constraints of `sample_stochastic` (suppress_ids,
+        min_length with end_id, no_repeat_ngram_size, block_repeat, repetition_penalty): the candidates then hold no <unk>, no
+        stutter and no two-token captions before the reranker sees them."""
         if int(num_samples) < 2:
             raise ValueError("a consensus needs num_samples > 1, got %r" % (num_samples,))
         if sample_kw.get("return_logprobs") or sample_kw.get("return_logits"):

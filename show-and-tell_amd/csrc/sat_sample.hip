@@ -66,9 +66,33 @@ __device__ __forceinline__ u64 mass_of(float x, float xmax, double tau) {
     return a <= 0.0 ? (u64)(exp(a) * kMassScale) : 0ull;
 }
 
+// CONSTRAINED (sat_sample_filtered_ex, include/sat_hip.h): the row x is replaced by x' BEFORE anything else looks at it -- the
+// maximum, both cuts, the draw and logp are those of x'.  Two LDS bitmaps of kMaxV bits: `ban` (x'[v] = -inf) and `seen` (the
+// prefix tokens: x'[v] = x[v] > 0 ? x[v] / theta : x[v] * theta, one correctly rounded f32 operation, a token penalised once
+// however often it occurs).  Every thread clears its words, one barrier, wave 0 asks for the row's prefix (lane j: y_j) and its
+// share of the suppressed ids, the row loads follow -- the other waves' are in flight meanwhile -- then wave 0 sets the bits (the
+// n-gram compare reads the neighbours' y by ds_bpermute, as the beam's row kernel does) and one barrier publishes them.  The
+// register path transforms once behind Row::load() -- one word of each bitmap per 16-byte chunk: chunk q is the nibble 4 (q & 7) of
+// word q >> 3, 8 neighbouring lanes read one word -- the looped path at every visit of Row::each.  Bans win over the penalty.
+struct SampleBan {
+    const int64_t* suppress;     // device [n_suppress]
+    const int64_t* prefix;       // row r's tokens y_0 .. y_{t-1} at prefix[r * prefix_stride + j]
+    long prefix_stride;
+    long end_id;                 // banned at this step when >= 0 (the host has already compared t with min_length)
+    int n_suppress;
+    int depth;                   // prefix tokens to read: t when a rule of this step reads them, else 0
+    int ngram;                   // n when n-gram blocking bans at this step (t >= n), else 0
+    int block_repeat;            // y_{t-1} is banned at this step
+    float theta;                 // repetition penalty of this step (1: none)
+};
+constexpr int kBanTMax = 64;     // prefix tokens a constrained step may read (lane j of wave 0 keeps y_j)
+constexpr int kBanWords = kMaxV / 32;
+
+__device__ __forceinline__ float penalised(float x, float theta) { return x > 0.0f ? __fdiv_rn(x, theta) : __fmul_rn(x, theta); }
+
 // The row of one workgroup.  REG: 16-byte chunk q = tid + c * NT of the row in rc[c], the V % 4 leftover column 4 * nq + tid in
 // xt, columns past V hold -inf (no candidates); masses, once filled, beside them.  !REG: every visit reloads from memory.
-template <bool REG>
+template <bool REG, bool CONS = false>
 struct Row {
     f32x4 rc[REG ? RC : 1];
     float xt;
@@ -77,6 +101,34 @@ struct Row {
     int V, nq, tid;
     float xmax;
     double tau;
+    const unsigned* ban;         // CONS only: the two bitmaps and the penalty
+    const unsigned* seen;
+    float theta;
+
+    // x'[v] of the (NaN-free) logit xv in column v < V
+    __device__ __forceinline__ float constrained(float xv, int v) const {
+        const unsigned bit = 1u << (v & 31);
+        if (seen[v >> 5] & bit) xv = penalised(xv, theta);
+        return (ban[v >> 5] & bit) ? -INFINITY : xv;
+    }
+    // REG: the row in registers becomes x' (after load() and the barrier that publishes the bitmaps)
+    __device__ __forceinline__ void constrain() {
+        if constexpr (REG && CONS) {
+#pragma unroll
+            for (int c = 0; c < RC; ++c) {
+                const int q = tid + c * NT;
+                const int w = q < nq ? q >> 3 : 0;           // (chunks past the row hold -inf whatever the bits say)
+                const unsigned nb = ban[w] >> (4 * (q & 7)), ns = seen[w] >> (4 * (q & 7));
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float xv = ((ns >> e) & 1u) ? penalised(rc[c][e], theta) : rc[c][e];
+                    rc[c][e] = ((nb >> e) & 1u) ? -INFINITY : xv;
+                }
+            }
+            const int tail = (nq << 2) + tid;
+            if (tail < V) xt = constrained(xt, tail);
+        }
+    }
 
     __device__ __forceinline__ void load() {
         if constexpr (REG) {
@@ -119,6 +171,7 @@ struct Row {
             for (int v = tid; v < V; v += NT) {
                 float xv = x[v];
                 xv = xv == xv ? xv : -INFINITY;
+                if constexpr (CONS) xv = constrained(xv, v);
                 f(xv, v, with_mass ? mass_of(xv, xmax, tau) : 0ull);
             }
         }
@@ -164,8 +217,8 @@ __device__ __forceinline__ Pick pick_bin(Shared& sh, bool asc, bool by_mass, u64
 
 // The shortest prefix of the total order, inside `cut`, whose weight (count, or MASS) reaches `target`: narrows `cut` to it and
 // sets n to its size.  target >= 1 and at most the weight inside `cut`.
-template <bool MASS, bool REG>
-__device__ __forceinline__ void select_prefix(Row<REG>& row, Shared& sh, Cut& cut, int& n, u64 target) {
+template <bool MASS, bool REG, bool CONS>
+__device__ __forceinline__ void select_prefix(Row<REG, CONS>& row, Shared& sh, Cut& cut, int& n, u64 target) {
     const int tid = threadIdx.x;
     const Cut prior = cut;
     unsigned prefix = 0, above = 0;
@@ -232,8 +285,8 @@ __device__ __forceinline__ void select_prefix(Row<REG>& row, Shared& sh, Cut& cu
 }
 
 // sum of the masses inside `cut` over the block (exact: integers)
-template <bool REG>
-__device__ __forceinline__ u64 mass_inside(Row<REG>& row, Shared& sh, const Cut& cut) {
+template <bool REG, bool CONS>
+__device__ __forceinline__ u64 mass_inside(Row<REG, CONS>& row, Shared& sh, const Cut& cut) {
     if (threadIdx.x == 0) sh.acc = 0;
     __syncthreads();
     u64 s = 0;
@@ -250,22 +303,73 @@ __device__ __forceinline__ u64 mass_inside(Row<REG>& row, Shared& sh, const Cut&
 
 __device__ __forceinline__ bool better(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
 
-template <bool REG>
+// wave 0, after the barrier behind the clearing: the bits of row r's step.  y: y_lane of the prefix (-1: none, or outside [0, V));
+// sup: the suppressed ids lane, lane + 64, .. of this lane
+__device__ __forceinline__ void gather_bans(const SampleBan& b, int V, int lane, int y, const int64_t (&sup)[4], unsigned* s_ban,
+                                            unsigned* s_seen) {
+    auto set = [&](unsigned* map, long v) {
+        if (v >= 0 && v < V) atomicOr(&map[v >> 5], 1u << (v & 31));
+    };
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        if (lane + 64 * u < b.n_suppress) set(s_ban, (long)sup[u]);
+    if (lane == 0) set(s_ban, b.end_id);
+    const int i = b.depth, n = b.ngram;
+    if (i <= 0) return;                                      // (uniform)
+    if (b.theta != 1.0f && lane < i) set(s_seen, y);
+    if (b.block_repeat && lane == i - 1) set(s_ban, y);
+    if (n >= 1 && i >= n) {
+        // lane j: the n-gram that starts at j, 0 <= j <= i - n, bans its last token when its first n - 1 equal the tail
+        bool same = true;
+        for (int m = 0; m + 1 < n; ++m) {                    // (both reads by the whole wave: no short-circuit around a bpermute)
+            const int mine = __shfl(y, (lane + m) & 63, 64), tail = __shfl(y, i - n + 1 + m, 64);
+            same = same & (mine == tail);
+        }
+        const int lastv = __shfl(y, (lane + n - 1) & 63, 64);
+        if (lane <= i - n && same) set(s_ban, lastv);
+    }
+}
+
+template <bool REG, bool CONS>
 __global__ __launch_bounds__(NT) void sample_filtered_kernel(const float* __restrict__ logits, long ldl, int V, float temperature,
                                                              int top_k, float top_p, unsigned key0, unsigned key1, unsigned t,
                                                              unsigned ctr3, int64_t* __restrict__ ids, long ids_stride,
                                                              float* __restrict__ logp, long logp_stride,
-                                                             int32_t* __restrict__ kept, long kept_stride) {
+                                                             int32_t* __restrict__ kept, long kept_stride, SampleBan ban) {
     __shared__ Shared sh;
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    Row<REG> row;
+    Row<REG, CONS> row;
     row.x = logits + (long)r * ldl;
     row.V = V;
     row.nq = V >> 2;
     row.tid = tid;
     row.tau = (double)temperature;
     row.xmax = -INFINITY;
-    row.load();
+    if constexpr (CONS) {
+        __shared__ unsigned s_ban[kBanWords], s_seen[kBanWords];
+        for (int w = tid; w < (V + 31) >> 5; w += NT) { s_ban[w] = 0u; s_seen[w] = 0u; }
+        __syncthreads();
+        int y = -1;
+        int64_t sup[4] = {-1, -1, -1, -1};
+        if (wave == 0) {                                     // asked for in front of the row: they arrive first
+            if (lane < ban.depth) {
+                const int64_t tk = ban.prefix[(long)r * ban.prefix_stride + lane];
+                y = (tk >= 0 && tk < V) ? (int)tk : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (lane + 64 * u < ban.n_suppress) sup[u] = ban.suppress[lane + 64 * u];
+        }
+        row.ban = s_ban;
+        row.seen = s_seen;
+        row.theta = ban.theta;
+        row.load();
+        if (wave == 0) gather_bans(ban, V, lane, y, sup, s_ban, s_seen);
+        __syncthreads();
+        row.constrain();
+    } else {
+        row.load();
+    }
 
     // the maximum and the number of candidates
     {
@@ -396,21 +500,54 @@ int filtered_check(const float* logits, int64_t ldl, int R, int V, float tempera
 
 int filtered_launch(const float* logits, int64_t ldl, int R, int V, float temperature, int top_k, float top_p, uint64_t seed, int t,
                     int rank, int64_t* ids, int64_t ids_stride, float* logp, int64_t logp_stride, int32_t* kept, int64_t kept_stride,
-                    hipStream_t s) {
+                    hipStream_t s, const SampleBan* ban = nullptr) {
     const unsigned key0 = (unsigned)(seed & 0xffffffffu), key1 = (unsigned)(seed >> 32);
     const int nq = V >> 2;
     // the register path: rows start on 16 bytes, hold a whole 16-byte chunk (nq - 1 clamps the loads past the row) and fit
     const bool reg = (ldl & 3) == 0 && (((uintptr_t)logits) & 15) == 0 && nq >= 1 && nq <= RC * NT;
-    if (reg)
-        hipLaunchKernelGGL(sample_filtered_kernel<true>, dim3(R), dim3(NT), 0, s, logits, (long)ldl, V, temperature, top_k, top_p, key0,
-                           key1, (unsigned)t, 2u * (unsigned)rank, ids, (long)ids_stride, logp, (long)logp_stride, kept,
-                           (long)kept_stride);
-    else
-        hipLaunchKernelGGL(sample_filtered_kernel<false>, dim3(R), dim3(NT), 0, s, logits, (long)ldl, V, temperature, top_k, top_p, key0,
-                           key1, (unsigned)t, 2u * (unsigned)rank, ids, (long)ids_stride, logp, (long)logp_stride, kept,
-                           (long)kept_stride);
+    const SampleBan none = {};
+#define SAT_SAMPLE_LAUNCH(REG, CONS)                                                                                                   \
+    hipLaunchKernelGGL((sample_filtered_kernel<REG, CONS>), dim3(R), dim3(NT), 0, s, logits, (long)ldl, V, temperature, top_k, top_p,  \
+                       key0, key1, (unsigned)t, 2u * (unsigned)rank, ids, (long)ids_stride, logp, (long)logp_stride, kept,             \
+                       (long)kept_stride, ban ? *ban : none)
+    if (ban) {
+        if (reg) SAT_SAMPLE_LAUNCH(true, true);
+        else SAT_SAMPLE_LAUNCH(false, true);
+    } else {
+        if (reg) SAT_SAMPLE_LAUNCH(true, false);
+        else SAT_SAMPLE_LAUNCH(false, false);
+    }
+#undef SAT_SAMPLE_LAUNCH
     SAT_LAUNCH_CHECK();
     return SAT_OK;
+}
+
+// The constraints of an `_ex` call: SAT_ERR_ARG for what the header lists; *active: some field differs from "off"
+int constraints_check(const sat_sample_constraints* c, bool* active) {
+    *active = false;
+    if (!c) return SAT_OK;
+    if (c->n_suppress < 0 || c->min_length < 0 || c->no_repeat_ngram < 0 || (c->block_repeat != 0 && c->block_repeat != 1))
+        return SAT_ERR_ARG;
+    if (c->n_suppress > 256 || (c->n_suppress > 0 && !c->suppress_ids)) return SAT_ERR_ARG;
+    if (!isfinite(c->repetition_penalty) || !(c->repetition_penalty > 0.0f)) return SAT_ERR_ARG;
+    if (c->min_length > 0 && c->end_id < 0) return SAT_ERR_ARG;
+    *active = c->n_suppress > 0 || c->min_length > 0 || c->no_repeat_ngram > 0 || c->block_repeat != 0 || c->repetition_penalty != 1.0f;
+    return SAT_OK;
+}
+
+// What `c` does at step t, for the kernel; false: nothing -- the plain kernel serves the step
+bool ban_of_step(const sat_sample_constraints* c, int t, const int64_t* prefix, int64_t prefix_stride, SampleBan* b) {
+    *b = SampleBan{};
+    b->suppress = c->suppress_ids;
+    b->n_suppress = c->n_suppress;
+    b->end_id = t < c->min_length ? (long)c->end_id : -1;
+    b->ngram = (c->no_repeat_ngram >= 1 && t >= c->no_repeat_ngram) ? c->no_repeat_ngram : 0;
+    b->block_repeat = (c->block_repeat && t >= 1) ? 1 : 0;
+    b->theta = t >= 1 ? c->repetition_penalty : 1.0f;
+    b->depth = (b->ngram || b->block_repeat || b->theta != 1.0f) ? t : 0;
+    b->prefix = prefix;
+    b->prefix_stride = (long)prefix_stride;
+    return b->n_suppress > 0 || b->end_id >= 0 || b->depth > 0;
 }
 
 }  // namespace
@@ -434,15 +571,19 @@ extern "C" int64_t sat_sample_decode_ws_bytes(int B, int E, int H, int V, int nu
     return al256((int64_t)B * ((V + 3) / 4 * 4) * 4) + al256(sat_sample_filtered_ws_bytes(B, V));
 }
 
-extern "C" int sat_sample_decode(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
-                                 const float* lin_w, const float* lin_b, int B, int E, int H, int V, int steps, float temperature,
-                                 int top_k, float top_p, uint64_t seed, int rank, float* h, float* c, float* h_tmp, float* x_tmp,
-                                 int64_t* ids, int64_t ids_stride, float* logp, int32_t* kept, float* logits_out, int64_t ldl,
-                                 void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+namespace {
+
+// sat_sample_decode's loop; cons (NULL: none) is applied with the ids buffer itself as every row's prefix
+int sample_decode(const float* features, const float* embed, const float* const* lstm_w, int num_layers, const float* lin_w,
+                  const float* lin_b, int B, int E, int H, int V, int steps, float temperature, int top_k, float top_p, uint64_t seed,
+                  int rank, float* h, float* c, float* h_tmp, float* x_tmp, int64_t* ids, int64_t ids_stride, float* logp,
+                  int32_t* kept, float* logits_out, int64_t ldl, const sat_sample_constraints* cons, void* workspace,
+                  int64_t ws_bytes, sat_stream_t stream) {
     SAT_TRY(sat_decode_check(features, embed, lstm_w, num_layers, lin_w, lin_b, B, E, H, V, steps, h, c, h_tmp, x_tmp, ids, ids_stride));
     if (!workspace || (logits_out && ldl < V)) return SAT_ERR_ARG;
     const int64_t lds = (V + 3) / 4 * 4, fws = al256((int64_t)B * lds * 4);
     SAT_TRY(filtered_check(features, V, B, V, temperature, top_k, top_p, 0, rank, ids, workspace, sat_sample_filtered_ws_bytes(B, V)));
+    if (cons && steps > kBanTMax) return SAT_ERR_UNSUPPORTED;
     if (ws_bytes < sat_sample_decode_ws_bytes(B, E, H, V, num_layers)) return SAT_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float* step_logits = (float*)workspace;                    // [B][lds] when the caller keeps no logits
@@ -458,10 +599,58 @@ extern "C" int sat_sample_decode(const float* features, const float* embed, cons
         float* lg = logits_out ? logits_out + (long)i * B * ldl : step_logits;
         const int64_t ld = logits_out ? ldl : lds;
         SAT_TRY(sat_vocab_logits_fwd(top, lin_w, lin_b, B, H, V, lg, ld, stream));
+        SampleBan ban;
+        const bool bans = cons && ban_of_step(cons, i, ids, ids_stride, &ban);     // (a step `cons` leaves alone: the plain kernel)
         SAT_TRY(filtered_launch(lg, ld, B, V, temperature, top_k, top_p, seed, i, rank, ids + i, ids_stride, logp ? logp + i : nullptr,
-                                steps, kept ? kept + i : nullptr, steps, s));
+                                steps, kept ? kept + i : nullptr, steps, s, bans ? &ban : nullptr));
         SAT_TRY(sat_embed_rows(embed, ids + i, ids_stride, B, E, V, x_tmp, stream));
         x = x_tmp;
     }
     return stack.finish();
+}
+
+}  // namespace
+
+extern "C" int sat_sample_decode(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
+                                 const float* lin_w, const float* lin_b, int B, int E, int H, int V, int steps, float temperature,
+                                 int top_k, float top_p, uint64_t seed, int rank, float* h, float* c, float* h_tmp, float* x_tmp,
+                                 int64_t* ids, int64_t ids_stride, float* logp, int32_t* kept, float* logits_out, int64_t ldl,
+                                 void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    return sample_decode(features, embed, lstm_w, num_layers, lin_w, lin_b, B, E, H, V, steps, temperature, top_k, top_p, seed, rank, h,
+                         c, h_tmp, x_tmp, ids, ids_stride, logp, kept, logits_out, ldl, nullptr, workspace, ws_bytes, stream);
+}
+
+// ---- the constrained entry points (include/sat_hip.h): banned ids, n-gram blocking, repetition penalty on the row BEFORE the cuts ----
+extern "C" int sat_sample_filtered_ex(const float* logits, int64_t ldl, int R, int V, float temperature, int top_k, float top_p,
+                                      uint64_t seed, int t, int rank, int64_t* ids, int64_t ids_stride, float* logp, int32_t* kept,
+                                      const sat_sample_constraints* c, const int64_t* prefix, int64_t prefix_stride, void* workspace,
+                                      int64_t ws_bytes, sat_stream_t stream) {
+    bool active = false;
+    SAT_TRY(constraints_check(c, &active));
+    SAT_TRY(filtered_check(logits, ldl, R, V, temperature, top_k, top_p, t, rank, ids, workspace, ws_bytes));
+    if (ids_stride < 1) return SAT_ERR_ARG;
+    SampleBan ban;
+    const bool bans = active && ban_of_step(c, t, prefix, prefix_stride, &ban);
+    if (bans && ban.depth > 0) {
+        if (t >= kBanTMax) return SAT_ERR_UNSUPPORTED;
+        if (!prefix || prefix_stride < 0) return SAT_ERR_ARG;
+    }
+    return filtered_launch(logits, ldl, R, V, temperature, top_k, top_p, seed, t, rank, ids, ids_stride, logp, 1, kept, 1,
+                           (hipStream_t)stream, bans ? &ban : nullptr);
+}
+
+extern "C" int64_t sat_sample_decode_ex_ws_bytes(int B, int E, int H, int V, int num_layers) {
+    return sat_sample_decode_ws_bytes(B, E, H, V, num_layers);
+}
+
+extern "C" int sat_sample_decode_ex(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
+                                    const float* lin_w, const float* lin_b, int B, int E, int H, int V, int steps, float temperature,
+                                    int top_k, float top_p, uint64_t seed, int rank, float* h, float* c, float* h_tmp, float* x_tmp,
+                                    int64_t* ids, int64_t ids_stride, float* logp, int32_t* kept, float* logits_out, int64_t ldl,
+                                    const sat_sample_constraints* cons, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    bool active = false;
+    SAT_TRY(constraints_check(cons, &active));
+    return sample_decode(features, embed, lstm_w, num_layers, lin_w, lin_b, B, E, H, V, steps, temperature, top_k, top_p, seed, rank, h,
+                         c, h_tmp, x_tmp, ids, ids_stride, logp, kept, logits_out, ldl, active ? cons : nullptr, workspace, ws_bytes,
+                         stream);
 }

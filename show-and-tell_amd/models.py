@@ -544,6 +544,51 @@ def check_beam_constraints(suppress_ids=None, min_length=0, no_repeat_ngram_size
     return c
 
 
+class SampleConstraints:
+    """The checked constraints of one `sample_stochastic` call (`check_sample_constraints`).  `active`: something differs from the
+    defaults, so the `_ex` entry points run; `struct(device)` is the `sat_sample_constraints` the library reads -- this object
+    keeps the `suppress_ids` device tensor it points to alive."""
+
+    def __init__(self, suppress_ids, min_length, no_repeat_ngram_size, block_repeat, repetition_penalty, end_id):
+        self.suppress_ids, self.min_length, self.no_repeat_ngram_size = suppress_ids, min_length, no_repeat_ngram_size
+        self.block_repeat, self.repetition_penalty, self.end_id = block_repeat, repetition_penalty, end_id
+        self.active = bool(suppress_ids or min_length or no_repeat_ngram_size or block_repeat or repetition_penalty != 1.0)
+        self._tensor = self._struct = None
+
+    def struct(self, device):
+        if self._struct is None or self._tensor is not None and self._tensor.device != torch.device(device):
+            self._tensor = torch.tensor(self.suppress_ids, dtype=torch.int64, device=device) if self.suppress_ids else None
+            self._struct = L.SatSampleConstraints(self._tensor.data_ptr() if self.suppress_ids else None, len(self.suppress_ids),
+                                                  self.min_length, self.no_repeat_ngram_size, int(self.block_repeat),
+                                                  self.repetition_penalty, self.end_id)
+        return self._struct
+
+
+SAMPLE_MAX_STEPS = 64                                                       # include/sat_hip.h, sat_sample_filtered_ex
+_NO_SAMPLE_CONSTRAINTS = SampleConstraints([], 0, 0, False, 1.0, -1)
+
+
+def check_sample_constraints(suppress_ids=None, min_length=0, no_repeat_ngram_size=0, block_repeat=False, repetition_penalty=1.0,
+                             end_id=None, vocab_size=None, steps=None):
+    """The constraint arguments of the `sample_stochastic` methods as a `SampleConstraints`; a ValueError names the bad one --
+    everything the library refuses, and an `end_id` among `suppress_ids`.  The ids, `min_length`, `no_repeat_ngram_size` and
+    `block_repeat` are checked by `check_beam_constraints`, whose rules they are.  Host arithmetic only: runs before the library is
+    loaded."""
+    import math
+    if suppress_ids is None and block_repeat is False and type(min_length) is int and type(no_repeat_ngram_size) is int and \
+            type(repetition_penalty) in (int, float) and min_length == 0 and no_repeat_ngram_size == 0 and repetition_penalty == 1 and \
+            (end_id is None or type(end_id) is int):
+        return _NO_SAMPLE_CONSTRAINTS                       # the defaults: nothing to check, nothing to build
+    b = check_beam_constraints(suppress_ids, min_length, no_repeat_ngram_size, block_repeat, 0.0, end_id, vocab_size)
+    theta = _as_f32(repetition_penalty)
+    if isinstance(repetition_penalty, bool) or theta is None or not math.isfinite(theta) or theta <= 0:
+        raise ValueError("repetition_penalty must be a finite number > 0 (as float32; 1: off), got %r" % (repetition_penalty,))
+    c = SampleConstraints(b.suppress_ids, b.min_length, b.no_repeat_ngram_size, b.block_repeat, theta, -1 if end_id is None else end_id)
+    if c.active and steps is not None and steps > SAMPLE_MAX_STEPS:
+        raise ValueError("a constrained stochastic decode runs at most %d steps, got %d" % (SAMPLE_MAX_STEPS, steps))
+    return c
+
+
 def check_beam_groups(beam_size, num_beam_groups=1, diversity_penalty=0.0):
     """The group arguments of the `sample_beam` methods (include/sat_hip.h, sat_beam_step_groups) -> (G, penalty as float32); a
     ValueError names the bad one.  Host arithmetic only: runs before the library is loaded."""
@@ -761,7 +806,8 @@ class DecoderRNN(nn.Module):
 
     @torch.no_grad()
     def sample_stochastic(self, features, states=None, temperature=1.0, top_k=0, top_p=1.0, num_samples=1, seed=None,
-                          return_logprobs=False, return_logits=False):
+                          return_logprobs=False, return_logits=False, *, suppress_ids=None, min_length=0, no_repeat_ngram_size=0,
+                          block_repeat=False, repetition_penalty=1.0, end_id=None):
         """`sample` with a DRAW where it takes the arg-max: every step's token comes from softmax(logits / temperature) restricted
         to the top_k most likely tokens (0: all) and then to the nucleus, the shortest most-likely-first prefix that holds top_p of
         the remaining mass (1: all).  20 steps as ONE `sat_sample_decode` call, no tapes, eval or train mode; rows keep running
@@ -774,8 +820,21 @@ class DecoderRNN(nn.Module):
         every step (last).  seed: None draws one from torch's CPU generator (`draw_ss_seed`: `torch.manual_seed` reproduces it);
         the seed used stays on `last_sample_seed`.  The draws are `ss_rank`'s stream and follow sat_vocab_sample's convention: with
         (temperature, top_k, top_p) = (1, 0, 1) the tokens are those `rollout` draws from the same seed; top_k=1 takes every step's
-        arg-max (`sample`, up to ties between logits: its projection is another kernel with another summation order)."""
+        arg-max (`sample`, up to ties between logits: its projection is another kernel with another summation order).
+
+        Constraints (all off by default: the call is then the `sat_sample_decode` above; otherwise ONE `sat_sample_decode_ex`).
+        They act on every step's row of logits BEFORE the top-k and nucleus cuts, so logp and kept are those of the constrained
+        distribution; `return_logits` still hands back the raw logits.  The prefix of a row is what this decode drew for it so far.
+        suppress_ids: up to 256 ids that are never drawn (<unk>, <pad>, <start>).  min_length: `end_id` is not drawn before that
+        step (needs end_id).  no_repeat_ngram_size = n: no n-gram twice (n = 1: no token twice).  block_repeat: never the previous
+        token again.  repetition_penalty = theta: the logit of every token already drawn is divided by theta when positive,
+        multiplied when not (1: off; a ban wins).  The rules hold at every step of every row, also behind its <end>.  Rollouts,
+        SCST and scheduled sampling (`sat_vocab_sample`: a banned policy would change the gradient's meaning), `Ensemble` and
+        `validation_step` do not take them; there are no frequency / presence penalties and no length penalty (a sample has no
+        ranking to re-order)."""
         tau, top_k, top_p, S, seed = check_sample_args(temperature, top_k, top_p, num_samples, seed)
+        cons = check_sample_constraints(suppress_ids, min_length, no_repeat_ngram_size, block_repeat, repetition_penalty, end_id,
+                                        self.vocab_size, 20)
         lib = L.load()
         features, h, c, h_tmp, xe = self._decode_state(features, states, S)
         dev, R = features.device, features.shape[0]
@@ -789,10 +848,13 @@ class DecoderRNN(nn.Module):
         logits = torch.zeros(steps * R, ldl, device=dev) if return_logits else None
         wsb = lib.sat_sample_decode_ws_bytes(R, E, H, V, self.num_layers)
         ws, ws_ptr = L.workspace256(wsb, dev)
-        L.check(lib.sat_sample_decode(L.ptr(features), L.ptr(self.embed.weight), self._lstm_ptrs(), self.num_layers,
-                                      L.ptr(self.linear.weight), L.ptr(self.linear.bias), R, E, H, V, steps, tau, top_k, top_p, seed,
-                                      int(self.ss_rank), L.ptr(h), L.ptr(c), L.ptr(h_tmp), L.ptr(xe), ids.data_ptr(), ids.stride(0),
-                                      L.ptr(logp), L.ptr(kept), L.ptr(logits), ldl, ws_ptr, wsb, L.stream()), "sat_sample_decode")
+        head = (L.ptr(features), L.ptr(self.embed.weight), self._lstm_ptrs(), self.num_layers, L.ptr(self.linear.weight),
+                L.ptr(self.linear.bias), R, E, H, V, steps, tau, top_k, top_p, seed, int(self.ss_rank), L.ptr(h), L.ptr(c), L.ptr(h_tmp),
+                L.ptr(xe), ids.data_ptr(), ids.stride(0), L.ptr(logp), L.ptr(kept), L.ptr(logits), ldl)
+        if cons.active:
+            L.check(lib.sat_sample_decode_ex(*head, cons.struct(dev), ws_ptr, wsb, L.stream()), "sat_sample_decode_ex")
+        else:
+            L.check(lib.sat_sample_decode(*head, ws_ptr, wsb, L.stream()), "sat_sample_decode")
         self.last_sample_seed = seed
         shape = (R // S, S, steps) if S > 1 else (R, steps)
         return stochastic_result(ids.view(shape), dict(logp=logp.view(shape), kept=kept.view(shape)) if return_logprobs else None,
@@ -977,10 +1039,15 @@ class ShowAndTell(nn.Module):
         return ids
 
     @torch.no_grad()
-    def sample_stochastic(self, images, state=None, **kw):
+    def sample_stochastic(self, images, state=None, *, suppress_ids=None, min_length=0, no_repeat_ngram_size=0, block_repeat=False,
+                          repetition_penalty=1.0, end_id=None, **kw):
         """`DecoderRNN.sample_stochastic` behind the encoder: temperature, top_k, top_p, num_samples, seed, return_logprobs,
-        return_logits as there (checked before the encoder runs)."""
+        return_logits and the constraints as there (checked before the encoder runs)."""
         check_sample_args(kw.get("temperature", 1.0), kw.get("top_k", 0), kw.get("top_p", 1.0), kw.get("num_samples", 1), kw.get("seed"))
+        cons = dict(suppress_ids=suppress_ids, min_length=min_length, no_repeat_ngram_size=no_repeat_ngram_size,
+                    block_repeat=block_repeat, repetition_penalty=repetition_penalty, end_id=end_id)
+        if check_sample_constraints(vocab_size=self.decoder.vocab_size, steps=20, **cons).active:
+            kw.update(cons)
         return self.decoder.sample_stochastic(self.encoder(images), state, **kw)
 
 
