@@ -1219,6 +1219,51 @@ int sat_colsum_f32(const float* x, int64_t ld, int rows, int cols, float* out, s
 int sat_cast_f32_bf16(const float* in, void* out, int64_t n, sat_stream_t stream);
 int sat_cast_bf16_f32(const void* in, float* out, int64_t n, sat_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scoring given captions (added within ABI 18): the model's log-probability of captions somebody hands it -- per-caption
+ * likelihood, likelihood reranking, image-sentence ranking by p(S|I) (Vinyals et al. 2015, section 4.3.5).
+ *
+ * sat_vocab_logp: the vocab projection (models.py:53), log-softmax and the pick of one column per row, WITHOUT the [N, V] logits:
+ *   tok_logp[n] = (Hs[n] . w[t_n] + b[t_n]) - logsumexp_v (Hs[n] . w[v] + b[v]),  t_n = targets[n] clamped into [0, V-1] (as
+ *   sat_ce_rows clamps it);  lse[n] (nullable) = that logsumexp.  Hs rows have pitch lda >= H floats.
+ *   Shapes sat_gemm_f32x3 takes (sat_gemm_f32x3_packed_bytes(V, H) > 0) with V % 4 == 0: sat_gemm_f32x3's tile loop with an
+ *   epilogue that leaves a (max, sum exp) pair per row and 128-column tile (8 bytes where the logits would be 512), joined per
+ *   row in ascending tile order in f64; w_packed = sat_gemm_f32x3_pack's copy of w, or NULL (the call then packs w into the
+ *   workspace itself).  Every other shape: chunks of rows through sat_vocab_logits_fwd's GEMM into a bounded scratch, then
+ *   sat_ce_rows(write_grad = 0).  No atomics: the same input gives the same bits, and a row gives the same bits in any batch.
+ *   workspace: sat_vocab_logp_ws_bytes(N, H, V) bytes (never N * V elements; the general path works in any workspace that holds
+ *   one row of logits and takes as many rows per chunk as fit -- sat_vocab_logp_ws_bytes_rows names the chunk height, for tests).
+ *   SAT_ERR_ARG before any launch: NULL pointers, N < 1, lda < H, lda or H no multiple of 4, Hs / w / workspace not 16-byte
+ *   aligned, a workspace too small.
+ * sat_caption_logp_sum: packed rows (time-major, rows of step t at [prefix[t], prefix[t+1]), row r present at step t while
+ *   r < prefix[t+1] - prefix[t]) to captions: logp[r] = f64 sum over t ascending (one thread per caption), len[r] = its steps,
+ *   tok_out[r][t] (nullable, pitch tok_stride >= T) = the token's log-probability, +0.0f beyond the caption's length.
+ * sat_score_captions: the decoder (models.py:47-53) teacher-forced on R rows, row r = (image row_image[r], caption
+ *   row_caption[r]) -- paired scoring and the B_img x C cross matrix are both this call.  Rows are ordered by caption length,
+ *   descending: batch_sizes [T] HOST, non-increasing, batch_sizes[0] = R, sum N; prefix [T+1] DEVICE, its running sum.  Step 0
+ *   feeds features and runs on the B_img image rows only (the state is then gathered to the rows); step t >= 1 feeds
+ *   embed[captions[c][t-1]] to the live rows through sat_lstm_step; step t is scored against captions[c][t] -- the rows
+ *   `decoder(features, captions, lengths)` is trained on against pack_padded_sequence(captions, lengths).  The top layer's h
+ *   of every live (step, row) goes through ONE sat_vocab_logp (weights packed once per call), then sat_caption_logp_sum.
+ *   captions [C][cap_stride] i64 (ids clamped for memory safety only: range-check them with sat_validate_ids); lstm_w: HOST
+ *   array of 4 * num_layers device pointers (w_ih, w_hh, b_ih, b_hh per layer), num_layers <= 8; E, H multiples of 4;
+ *   workspace 256-byte aligned, sat_score_captions_ws_bytes(...) bytes -- about N * (4 H + 8 ceil(V / 128)) plus state and
+ *   the packed weights.  SAT_ERR_ARG before any launch as above, and for batch_sizes that do not describe R rows / N steps. */
+int64_t sat_vocab_logp_ws_bytes(int N, int H, int V);
+int64_t sat_vocab_logp_ws_bytes_rows(int N, int H, int V, int chunk_rows);
+int sat_vocab_logp(const float* Hs /*[N,lda]*/, int64_t lda, const float* w /*[V,H]*/, const void* w_packed, const float* b /*[V]*/,
+                   const int64_t* targets /*[N]*/, int N, int H, int V, float* tok_logp /*[N]*/, float* lse /*[N] or NULL*/,
+                   void* workspace, int64_t ws_bytes, sat_stream_t stream);
+int sat_caption_logp_sum(const float* tok_logp /*[N]*/, const int32_t* prefix /*[T+1] device*/, int T, int R, double* logp /*[R]*/,
+                         int32_t* len /*[R]*/, float* tok_out /*[R][tok_stride] or NULL*/, int64_t tok_stride, sat_stream_t stream);
+int64_t sat_score_captions_ws_bytes(int B_img, int R, int N, int E, int H, int V, int num_layers);
+int sat_score_captions(const float* features /*[B_img,E]*/, const float* embed /*[V,E]*/, const float* const* lstm_w /*[host]*/,
+                       int num_layers, const float* lin_w /*[V,H]*/, const float* lin_b /*[V]*/, const int64_t* captions, int64_t cap_stride,
+                       int C, const int32_t* row_image /*[R] device*/, const int32_t* row_caption /*[R] device*/,
+                       const int32_t* batch_sizes /*[T] host*/, const int32_t* prefix /*[T+1] device*/, int T, int B_img, int R, int N,
+                       int E, int H, int V, double* logp /*[R]*/, int32_t* len /*[R]*/, float* tok_out /*[R][tok_stride] or NULL*/,
+                       int64_t tok_stride, void* workspace, int64_t ws_bytes, sat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@ from .input import DevicePrefetcher, ImageTransform, collate_batch, collate_on_d
 from .evaluate import kept_tokens, mean_cross_entropy, pack_validation_targets, sentences, validation_step  # noqa: F401
 from .cider import CiderScorer, encode_references  # noqa: F401
 from .consensus import ConsensusReranker  # noqa: F401
+from .score import CaptionScores, candidate_captions, rescore, retrieval_metrics, set_workspace_budget  # noqa: F401
 from .langstats import BleuScorer, MixedReward, RougeLScorer  # noqa: F401
 from .scst import SelfCritical, ce_rows_weighted, group_sum_rows, scst_loss, scst_weights, scst_weights_group  # noqa: F401
 from .criterion import CrossEntropy, cross_entropy  # noqa: F401

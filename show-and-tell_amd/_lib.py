@@ -262,6 +262,13 @@ SIGNATURES = {
     "sat_colsum_f32": (_i, [_vp, _i64, _i, _i, _vp, _vp]),
     "sat_cast_f32_bf16": (_i, [_vp, _vp, _i64, _vp]),
     "sat_cast_bf16_f32": (_i, [_vp, _vp, _i64, _vp]),
+    "sat_vocab_logp_ws_bytes": (_i64, [_i, _i, _i]),
+    "sat_vocab_logp_ws_bytes_rows": (_i64, [_i, _i, _i, _i]),
+    "sat_vocab_logp": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "sat_caption_logp_sum": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "sat_score_captions_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
+    "sat_score_captions": (_i, [_vp, _vp, C.POINTER(_vp), _i, _vp, _vp, _vp, _i64, _i, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _i, _i, _i,
+                                _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
 }
 
 # Symbols added since ABI_VERSION was last raised (additions do not raise it).  Another build of the same ABI version -- SAT_LIB,
@@ -279,7 +286,9 @@ ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_at
                     "sat_grad_sumsq_partials", "sat_grad_sumsq_ws_bytes", "sat_grad_sumsq", "sat_adamw_step",
                     "sat_ensemble_logprobs", "sat_beam_decode_ensemble_ws_bytes", "sat_beam_decode_ensemble",
                     "sat_consensus_ws_bytes", "sat_consensus_rerank", "sat_scst_weights_group", "sat_group_sum_rows",
-                    "sat_sample_filtered_ex", "sat_sample_decode_ex_ws_bytes", "sat_sample_decode_ex")
+                    "sat_sample_filtered_ex", "sat_sample_decode_ex_ws_bytes", "sat_sample_decode_ex", "sat_vocab_logp_ws_bytes",
+                    "sat_vocab_logp_ws_bytes_rows", "sat_vocab_logp", "sat_caption_logp_sum", "sat_score_captions_ws_bytes",
+                    "sat_score_captions")
 
 _lib = None
 

@@ -632,6 +632,27 @@ class ShowAttendTellModel(nn.Module):
         return self.last_scst.attend(self, feats, fmean, image_index, steps)
 
     @torch.no_grad()
+    def score_captions(self, images, captions, lengths, *, cross=False, normalize="none", return_tokens=False):
+        """The log-probability of GIVEN captions (`score.CaptionScores`), one image per caption: `score_captions_features` behind
+        the encoder."""
+        if cross:
+            raise NotImplementedError("cross scoring for Show-Attend-Tell is out of scope: score pairs (cross=False)")
+        feats, fmean = self._encode(images)
+        return self.score_captions_features(feats, fmean, captions, lengths, normalize=normalize, return_tokens=return_tokens)
+
+    @torch.no_grad()
+    def score_captions_features(self, features, fmean, captions, lengths, *, cross=False, normalize="none", return_tokens=False):
+        """... given the features [C, P, F] and their mean (`_encode`).  Scored tokens are the ones the model is trained on
+        (train.py:134-139): captions[:, 1:] with lengths - 1, so `lengths` (a Python list, ANY order, each >= 2) count the
+        `<start>` that is fed but not scored, and `length` of the result is lengths - 1.  The logits come from `decode`, the
+        model's own forward (a fixed, affordable size here), then `sat_ce_rows` without a gradient and `sat_caption_logp_sum`.
+        Eval or train mode, and as `DecoderRNN.score_captions` never with dropout or scheduled sampling: the forward runs as in
+        eval mode.  Paired only: cross=True raises NotImplementedError."""
+        from .score import attend_score_captions_features
+        return attend_score_captions_features(self, features, fmean, captions, lengths, cross=cross, normalize=normalize,
+                                              return_tokens=return_tokens)
+
+    @torch.no_grad()
     def sample(self, images, states=None, return_alphas=False):
         """Greedy search, 20 steps (model2.py:91-111; torch-0.1 keepdim semantics): i64 [B,20].  `states`: None = zeros (what
         eval.py:82-83 passes), a (h, c) pair of [B,H] tensors, or eval.py:89's stacked [2,B,H] tensor.  return_alphas: also the

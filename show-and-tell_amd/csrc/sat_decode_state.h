@@ -56,3 +56,45 @@ struct SatDecodeStack {
         return SAT_OK;
     }
 };
+
+// The same stack for teacher-forced SCORING (sat_score_captions), where the live rows of a step are a PREFIX of the R rows that
+// shrinks over the steps (rows ordered by caption length, descending).  State [num_layers][R][H]; a step runs on its first `rows`
+// rows only and leaves the others alone -- they are never read again.  The top layer's h is not kept here: the caller keeps every
+// step's top h (the projection's operand) and hands the previous step's rows in, this step's rows out.
+struct SatScoreStack {
+    const float* const* lstm_w;
+    float* hb[8][2];                  // layers below the top: two copies [R][H]
+    int cur[8];
+    float* c;
+    int num_layers, R, E, H;
+    sat_stream_t stream;
+
+    SatScoreStack(const float* const* lstm_w_, int num_layers_, int R_, int E_, int H_, float* low_h /*[2][num_layers - 1][R][H]*/,
+                  float* c_ /*[num_layers][R][H]*/, sat_stream_t stream_)
+        : lstm_w(lstm_w_), c(c_), num_layers(num_layers_), R(R_), E(E_), H(H_), stream(stream_) {
+        for (int l = 0; l + 1 < num_layers; ++l) {
+            hb[l][0] = low_h + (long)l * R * H;
+            hb[l][1] = low_h + (long)(num_layers - 1 + l) * R * H;
+            cur[l] = 0;
+        }
+    }
+
+    // where layer l < num_layers - 1 expects its initial h
+    float* h_live(int l) { return hb[l][cur[l]]; }
+
+    // one sat_lstm_step per layer on the first `rows` rows: x [rows][E]; top_in / top_out: the top layer's h before / after
+    int step(const float* x, int rows, const float* top_in, float* top_out) {
+        if (rows < 1 || rows > R) return SAT_ERR_ARG;
+        const float* inp = x;
+        for (int l = 0; l < num_layers; ++l) {
+            const bool top = l == num_layers - 1;
+            const float* h_in = top ? top_in : hb[l][cur[l]];
+            float* h_out = top ? top_out : hb[l][1 - cur[l]];
+            SAT_TRY(sat_lstm_step(inp, h_in, c + (long)l * R * H, lstm_w[4 * l], lstm_w[4 * l + 1], lstm_w[4 * l + 2], lstm_w[4 * l + 3],
+                                  rows, l == 0 ? E : H, H, h_out, stream));
+            if (!top) cur[l] = 1 - cur[l];
+            inp = h_out;
+        }
+        return SAT_OK;
+    }
+};

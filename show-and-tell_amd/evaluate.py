@@ -66,7 +66,7 @@ def kept_tokens(ids, end_id):
 @torch.no_grad()
 def validation_step(model, images, captions, lengths, state=None, end_id=2, beam_size=1, scorer=None, image_index=None,
                     bleu=None, rouge=None, *, suppress_ids=None, min_length=0, no_repeat_ngram_size=0, block_repeat=False,
-                    length_penalty=0.0, num_beam_groups=1, diversity_penalty=0.0, consensus=None):
+                    length_penalty=0.0, num_beam_groups=1, diversity_penalty=0.0, consensus=None, caption_logp=False):
     """One iteration of the loop body eval.py:71-118 (the caller has put the model in eval mode, eval.py:65).
     Returns dict(loss f32[1], ids i64[B,20], kept i32[B]) -- all on the device, nothing synchronised.  With a `CiderScorer`
     and `image_index` (the corpus image of every row) the dict gains cider f64[1] and cider_scores f64[B] of `ids`; with a
@@ -78,7 +78,10 @@ def validation_step(model, images, captions, lengths, state=None, end_id=2, beam
     consensus: a `ConsensusReranker` (consensus.py).  With one and beam_size > 1 the decoded `ids` are the consensus pick of the
     beam_size hypotheses (equal weights; the reranker's end_id must be `end_id`) instead of the likelihood winner, and the dict
     gains consensus_best i64[B] and consensus_utility f64[B,beam_size]; with beam_size == 1 there is nothing to pick from:
-    ValueError."""
+    ValueError.
+    caption_logp: also caption_logp f64[B], the log-probability of every given caption (the sum over its rows of the packed
+    logits `loss` averages, `score.logits_caption_logp`), and caption_token_count i32[B], the rows it sums: the token-weighted
+    mean of -caption_logp is `loss`.  Off (the default): the calls and the keys are what they were."""
     from .models import check_beam_constraints, check_beam_groups
     cons = dict(suppress_ids=suppress_ids, min_length=min_length, no_repeat_ngram_size=no_repeat_ngram_size,
                 block_repeat=block_repeat, length_penalty=length_penalty)
@@ -97,7 +100,7 @@ def validation_step(model, images, captions, lengths, state=None, end_id=2, beam
             raise ValueError("the reranker ends rows at id %d, validation_step at %d" % (consensus.end_id, end_id))
     if model.training:
         raise RuntimeError("validation_step expects model.eval() (eval.py:65)")
-    targets, _ = pack_validation_targets(captions, lengths)
+    targets, pi = pack_validation_targets(captions, lengths)
     outputs = model(images, captions, lengths)                          # eval.py:93
     if not outputs.is_contiguous():
         outputs = outputs.contiguous()
@@ -114,6 +117,9 @@ def validation_step(model, images, captions, lengths, state=None, end_id=2, beam
         if ids.dim() == 1:                                              # squeezed at batch 1 (models.py:67): one row
             ids = ids.view(1, -1)
     out = {"loss": loss, "ids": ids, "kept": kept_tokens(ids, end_id)}
+    if caption_logp:
+        from .score import logits_caption_logp
+        out["caption_logp"], out["caption_token_count"], _ = logits_caption_logp(outputs, targets, pi)
     if consensus is not None:
         out["consensus_best"], out["consensus_utility"] = consensus.last_best, consensus.last_utility
     if scorer is not None:

@@ -784,6 +784,20 @@ class DecoderRNN(nn.Module):
         ids = out["ids"]
         return (ids if S == 1 else ids.view(-1, S, ids.shape[1])), logits
 
+    def score_captions(self, features, captions, lengths, *, cross=False, normalize="none", return_tokens=False):
+        """The log-probability of GIVEN captions under this decoder (`score.CaptionScores`): with captions [C, T] i64 as the
+        data loader gives them (`<start>` ... `<end>`) and `lengths` a Python list in ANY order, step t predicts captions[c][t]
+        for t < lengths[c] -- the rows `forward` is trained on against pack_padded_sequence(captions, lengths) (models.py:47-53).
+        Paired (features [C, E]): logp f64 [C].  cross=True (features [B_img, E]): logp f64 [B_img, C], every caption under
+        every image, chunked over images so that one library call's workspace stays under `score.WORKSPACE_BUDGET`.
+        length i32 [C]; token_logp f32 [..., T] with return_tokens (+0.0 beyond a caption's length); score = logp
+        (normalize="none") or logp / length ("length").  Results come back in the caller's order.  One `sat_score_captions` call
+        per chunk: the [N, V] logits never exist.  Eval or train mode (no dropout, no sampling: the model's own distribution);
+        nothing is taped.  Caption ids are range-checked on the device (`id_guard`)."""
+        from .score import decoder_score_captions
+        return decoder_score_captions(self, features, captions, lengths, cross=cross, normalize=normalize,
+                                      return_tokens=return_tokens)
+
     @torch.no_grad()
     def sample(self, features, states=None):
         """Greedy search, 20 steps (models.py:56-67; torch-0.1 keepdim semantics): i64 [B,20].
@@ -1016,6 +1030,11 @@ class ShowAndTell(nn.Module):
         self.decoder.dropout_plan(sampling=True, what="a rollout (scst_forward)")            # before the encoder runs
         self.last_scst = SelfCritical(scorer, end_id, num_samples=num_samples, baseline=baseline)
         return self.last_scst(self.decoder, self.encoder(images), image_index)
+
+    @torch.no_grad()
+    def score_captions(self, images, captions, lengths, **kw):
+        """`DecoderRNN.score_captions` (cross, normalize, return_tokens as there) behind the encoder in its current mode."""
+        return self.decoder.score_captions(self.encoder(images), captions, lengths, **kw)
 
     @torch.no_grad()
     def sample(self, images, state=None):
