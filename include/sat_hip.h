@@ -1161,6 +1161,42 @@ int sat_vocab_ce_fwd_bf16_ls(const float* Hs /*[N,H]*/, const float* w /*[V,H]*/
                              int N, int H, int V, float inv_denom, float smoothing, float* logits /*[N,ldl]*/, int64_t ldl,
                              float* row_loss /*[N]*/, float* row_nll /*[N] or NULL*/, float* loss_out /*[1] or NULL*/,
                              float* nll_out /*[1] or NULL*/, void* workspace /*256-byte aligned*/, int64_t ws_bytes, sat_stream_t stream);
+/* Token-level unlikelihood training (added within ABI 18; Welleck et al. 2019, arXiv:1908.04319, fairseq's
+ * candidate_penalty_cross_entropy): every target row also pays for the probability it gives to the tokens already emitted in its own
+ * caption.  Packed rows are time-major: row n = prefix[t] + b is step t of sequence b (b < prefix[t+1] - prefix[t]); prefix is the
+ * DEVICE int32 [T+1] of pack_padded_sequence's batch sizes (prefix[0] = 0, prefix[T] = N, batch sizes non-increasing -- trusted).
+ * For row n with logits x[0..V), target y (clamped as sat_ce_rows clamps it), p = softmax(x), and m, s, lse, nll and the smoothing
+ * term exactly as sat_ce_rows_ls defines them:
+ *     C_n         = { targets[prefix[s] + b] : 0 <= s < t } \ { y }      a SET: ids clamped the same way, a repeated id counts once
+ *     q_c         = 1 - p_c
+ *     row_ul[n]   = sum_{c in C_n} -log(max(q_c, 1e-5))
+ *     w_c         = q_c > 1e-5 ? p_c / q_c : 0                           (torch's clamp(min=1e-5): gradient 0 where it clamps)
+ *     W_n         = sum_{c in C_n} w_c
+ *     row_loss[n] = (sat_ce_rows_ls's row_loss[n]) + alpha * row_ul[n]
+ *     g[n][v]     = (p_v * (1 - alpha * W_n) - (1 - smoothing) * [v == y] - smoothing / V + (v in C_n ? alpha * w_v : 0)) * inv_denom
+ *     loss_out[0] = inv_denom * sum_n row_loss[n],  nll_out[0] = inv_denom * sum_n row_nll[n],  ul_out[0] = inv_denom * sum_n row_ul[n]
+ *                   (ul_out is NOT weighted by alpha; all three in sat_ce_rows's fixed order)
+ * Both sums over C_n run over the set's representatives in ascending order of first occurrence s, so a row's outputs depend only on
+ * its own logits and its own prefix: the same bits in any batch and in every replay.  Rows of step 0 have no candidates.
+ * alpha == 0: row_loss, row_nll, loss_out, nll_out and the gradient are bit for bit sat_ce_rows_ls's / sat_vocab_ce_fwd_bf16_ls's
+ * (and, with smoothing == 0 too, sat_ce_rows's / sat_vocab_ce_fwd_bf16's), row_ul is 0.
+ * sat_ce_rows_ul: sat_ce_rows_ls's two paths, grad forms (out of place, NULL, or == logits in place) and pad rule; one read of the
+ *   logits and one write of the gradient.  row_nll, row_ul, loss_out, nll_out, ul_out may be NULL.
+ *   SAT_ERR_ARG before any launch: everything sat_ce_rows_ls rejects, NULL prefix, T < 1, alpha < 0 or NaN, ul_out without row_ul.
+ *   SAT_ERR_UNSUPPORTED: T > 64.
+ * sat_vocab_ce_fwd_bf16_ul: sat_vocab_ce_fwd_bf16_ls (same workspace, size query and shape limits) with the term above; the gradient
+ *   is rounded once to bf16 where sat_vocab_ce_bwd_bf16 expects it, pad columns zero.  The same argument errors. */
+int sat_ce_rows_ul(const float* logits /*[N,ldl]*/, int64_t ldl, const int64_t* targets /*[N] packed*/,
+                   const int32_t* prefix /*[T+1] device*/, int T, int N, int V, float inv_denom, float smoothing, float alpha,
+                   float* grad /*[N,ldg], NULL, or == logits*/, int64_t ldg, float* row_loss /*[N]*/, float* row_nll /*[N] or NULL*/,
+                   float* row_ul /*[N] or NULL*/, float* loss_out /*[1] or NULL*/, float* nll_out /*[1] or NULL*/,
+                   float* ul_out /*[1] or NULL*/, sat_stream_t stream);
+int sat_vocab_ce_fwd_bf16_ul(const float* Hs /*[N,H]*/, const float* w /*[V,H]*/, const float* b /*[V]*/,
+                             const int64_t* targets /*[N] packed*/, const int32_t* prefix /*[T+1] device*/, int T, int N, int H, int V,
+                             float inv_denom, float smoothing, float alpha, float* logits /*[N,ldl]*/, int64_t ldl,
+                             float* row_loss /*[N]*/, float* row_nll /*[N] or NULL*/, float* row_ul /*[N] or NULL*/,
+                             float* loss_out /*[1] or NULL*/, float* nll_out /*[1] or NULL*/, float* ul_out /*[1] or NULL*/,
+                             void* workspace /*256-byte aligned*/, int64_t ws_bytes, sat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * clip_gradient (train.py:88-91) + optim.Adam step (train.py:56,146) over one flat buffer.

@@ -238,6 +238,9 @@ SIGNATURES = {
     "sat_group_sum_rows": (_i, [_vp, _i64, _i, _i, _i64, _vp, _i64, _vp]),
     "sat_ce_rows_ls": (_i, [_vp, _i64, _vp, _i, _i, _f, _f, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sat_vocab_ce_fwd_bf16_ls": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sat_ce_rows_ul": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sat_vocab_ce_fwd_bf16_ul": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _i64, _vp]),
     "sat_rollout_attend_fwd_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
     "sat_rollout_attend_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _i64,
                                     _i, _i64, C.c_uint64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -288,7 +291,7 @@ ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_at
                     "sat_consensus_ws_bytes", "sat_consensus_rerank", "sat_scst_weights_group", "sat_group_sum_rows",
                     "sat_sample_filtered_ex", "sat_sample_decode_ex_ws_bytes", "sat_sample_decode_ex", "sat_vocab_logp_ws_bytes",
                     "sat_vocab_logp_ws_bytes_rows", "sat_vocab_logp", "sat_caption_logp_sum", "sat_score_captions_ws_bytes",
-                    "sat_score_captions")
+                    "sat_score_captions", "sat_ce_rows_ul", "sat_vocab_ce_fwd_bf16_ul")
 
 _lib = None
 

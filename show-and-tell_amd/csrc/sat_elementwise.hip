@@ -6,6 +6,7 @@
 //   trainer : fused elementwise clamp + Adam over one flat buffer (train.py:88-91,146)
 #include "sat_bn_stats.h"
 #include "sat_ce_ls.h"
+#include "sat_ce_ul.h"
 #include <stdlib.h>
 
 namespace {
@@ -724,6 +725,104 @@ __global__ __launch_bounds__(256) void ce_rows_ls_kernel(const float* logits, lo
     }
 }
 
+// sat_ce_rows_ul: ce_rows_ls_kernel's two paths with the unlikelihood term of sat_ce_ul.h (shared with the bf16 form).  After the
+// row statistics wave 0 gathers the row's candidates -- the targets of the earlier steps of its sequence -- and their logits, and
+// leaves the set with its weights in LDS; the dense gradient pass looks every column up there (one 32-bit LDS read per 16-byte
+// chunk).  Still one read and one write of the row.  alpha == 0 and rows of step 0 skip all of it.
+__global__ __launch_bounds__(256) void ce_rows_ul_kernel(const float* logits, long ldl, const int64_t* __restrict__ targets,
+                                                         const int32_t* __restrict__ prefix, int T, int V, float inv_denom, float eps,
+                                                         float alpha, float* grad, long ldg, float* __restrict__ row_loss,
+                                                         float* __restrict__ row_nll, float* __restrict__ row_ul) {
+    __shared__ float sh[4];
+    __shared__ CeUlShared u;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* x = logits + (long)row * ldl;
+    float* g = grad ? grad + (long)row * ldg : nullptr;
+    const CeLsCoef k = ce_ls_coef(eps, V);
+    auto reduce = [&](float v, bool is_max) { return block_reduce(v, is_max, sh); };
+    long tgt = targets[row];
+    tgt = tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt);
+    int b, pstart;
+    const int t = ce_ul_locate(prefix, T, row, b, pstart);
+    const bool ul_on = alpha > 0.0f && t > 0;      // uniform over the workgroup
+    if (ul_on) ce_ul_clear(u);                      // the barriers of the reductions below order it before ce_ul_candidates
+    // after the row statistics: the candidates, then what every thread needs of them
+    float ul = 0.0f, scale = 1.0f;
+    bool clash = false;
+    auto candidates = [&](float lse) {
+        if (!ul_on) return;
+        if (tid < 64) ce_ul_candidates(x, targets, (int)gridDim.x, pstart, t, b, (int)tgt, V, lse, alpha, u);
+        // this barrier publishes u; with grad == logits it is also what guarantees that every candidate logit (and, on the strided
+        // path, x[tgt]) has been read before any thread overwrites the row: the gradient pass comes after it
+        __syncthreads();
+        ul = u.ul;
+        scale = 1.0f - alpha * u.W;
+        clash = u.clash != 0;
+    };
+    auto report = [&](float nll, float smooth) {
+        row_loss[row] = ce_ul_loss(k, nll, smooth, alpha, ul);
+        if (row_nll) row_nll[row] = nll;
+        if (row_ul) row_ul[row] = ul;
+    };
+    constexpr int RC = 12;                       // as ce_rows_kernel
+    const int nq = V >> 2;
+    if ((ldl & 3) == 0 && nq <= RC * 256 && (((uintptr_t)logits) & 15) == 0 && (!grad || ((ldg & 3) == 0 && (((uintptr_t)grad) & 15) == 0))) {
+        f32x4 rc[RC];
+#pragma unroll
+        for (int c = 0; c < RC; ++c)
+            if (tid + c * 256 < nq) rc[c] = *(const f32x4*)(x + 4 * (tid + c * 256));
+        const int tail = (nq << 2) + tid;
+        const float xt = tail < V ? x[tail] : -INFINITY;
+        const CeLsRow r = ce_ls_row_stats<RC>(rc, nq, xt, tail < V, V, reduce);
+        candidates(r.lse);
+        const int tq = (int)(tgt >> 2), te = (int)(tgt & 3);
+        // the thread that holds the target logit reports the row
+#pragma unroll
+        for (int c = 0; c < RC; ++c)
+            if (tid + c * 256 == tq && tq < nq) report(r.lse - rc[c][te], r.smooth);
+        if (tail == (int)tgt && tq >= nq) report(r.lse - xt, r.smooth);
+        if (g) {
+#pragma unroll
+            for (int c = 0; c < RC; ++c) {
+                const int q = tid + c * 256;
+                if (q < nq) {
+                    const unsigned slots = ul_on ? *(const unsigned*)&u.slot[(4 * q) & (SAT_UL_HASH - 1)] : 0u;
+                    f32x4 o;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        o[e] = ce_ul_grad(k, rc[c][e], r.lse, (4 * q + e) == (int)tgt, scale,
+                                          ce_ul_addend(u, (slots >> (8 * e)) & 255u, 4 * q + e, t, clash), inv_denom);
+                    *(f32x4*)(g + 4 * q) = o;
+                }
+            }
+            if (tail < V)
+                g[tail] = ce_ul_grad(k, xt, r.lse, tail == (int)tgt, scale,
+                                     ce_ul_addend(u, ul_on ? u.slot[tail & (SAT_UL_HASH - 1)] : 0u, tail, t, clash), inv_denom);
+        }
+        return;
+    }
+    float m = -INFINITY;
+    for (int i = tid; i < V; i += 256) m = fmaxf(m, x[i]);
+    m = reduce(m, true);
+    float s = 0.0f, d = 0.0f;
+    for (int i = tid; i < V; i += 256) {
+        s += expf(x[i] - m);
+        d += x[i] - m;
+    }
+    s = reduce(s, false);
+    d = reduce(d, false);
+    const float logs = logf(s), lse = m + logs;
+    const float xtgt = tid == 0 ? x[tgt] : 0.0f;
+    candidates(lse);
+    if (tid == 0) report(lse - xtgt, logs - d / (float)V);
+    if (g) {
+        if (!ul_on) __syncthreads();   // x[tgt] read above before any overwrite (in place); with candidates, their barrier does it
+        for (int i = tid; i < V; i += 256)
+            g[i] = ce_ul_grad(k, x[i], lse, i == (int)tgt, scale, ce_ul_addend(u, ul_on ? u.slot[i & (SAT_UL_HASH - 1)] : 0u, i, t, clash),
+                              inv_denom);
+    }
+}
+
 // out[0] = sum_n w[n] * v[n] in sum_scale_kernel's order; a term of weight 0 is exactly 0 whatever v[n] holds
 __global__ __launch_bounds__(256) void weighted_sum_kernel(const float* __restrict__ v, const float* __restrict__ w, int n, float* out) {
     __shared__ float sh[256];
@@ -881,6 +980,15 @@ __global__ __launch_bounds__(256) void sum_scale_pair_kernel(const float* __rest
                                                              float* out0, float* out1) {
     if (blockIdx.x == 0) sum_scale_block(v0, n, scale, out0);
     else sum_scale_block(v1, n, scale, out1);
+}
+
+// up to three such sums as one launch of three workgroups (sat_ce_rows_ul: loss, plain NLL, unlikelihood term); a NULL out is skipped
+__global__ __launch_bounds__(256) void sum_scale_triple_kernel(const float* __restrict__ v0, const float* __restrict__ v1,
+                                                               const float* __restrict__ v2, int n, float scale, float* out0, float* out1,
+                                                               float* out2) {
+    const float* v = blockIdx.x == 0 ? v0 : (blockIdx.x == 1 ? v1 : v2);
+    float* out = blockIdx.x == 0 ? out0 : (blockIdx.x == 1 ? out1 : out2);
+    if (out) sum_scale_block(v, n, scale, out);
 }
 
 // out[c] = sum_r x[r*ld + c]; block = 32 columns x 8 row groups, fixed order
@@ -1461,6 +1569,25 @@ extern "C" int sat_ce_rows_ls(const float* logits, int64_t ldl, const int64_t* t
         SAT_LAUNCH_CHECK();
     } else if (loss_out || nll_out) {
         hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(256), 0, s, loss_out ? row_loss : row_nll, N, inv_denom, loss_out ? loss_out : nll_out);
+        SAT_LAUNCH_CHECK();
+    }
+    return SAT_OK;
+}
+
+extern "C" int sat_ce_rows_ul(const float* logits, int64_t ldl, const int64_t* targets, const int32_t* prefix, int T, int N, int V,
+                              float inv_denom, float smoothing, float alpha, float* grad, int64_t ldg, float* row_loss, float* row_nll,
+                              float* row_ul, float* loss_out, float* nll_out, float* ul_out, sat_stream_t stream) {
+    if (!logits || !targets || !row_loss || N < 1 || V < 1 || ldl < V || (grad && ldg < V)) return SAT_ERR_ARG;
+    if (!(smoothing >= 0.0f && smoothing < 1.0f) || (nll_out && !row_nll)) return SAT_ERR_ARG;     // (a NaN fails the first)
+    if (!prefix || T < 1 || !(alpha >= 0.0f) || (ul_out && !row_ul)) return SAT_ERR_ARG;           // (a NaN alpha fails too)
+    if (T > SAT_UL_MAX_T) return SAT_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ce_rows_ul_kernel, dim3(N), dim3(256), 0, s, logits, (long)ldl, targets, prefix, T, V, inv_denom, smoothing, alpha,
+                       grad, (long)ldg, row_loss, row_nll, row_ul);
+    SAT_LAUNCH_CHECK();
+    if (loss_out || nll_out || ul_out) {
+        hipLaunchKernelGGL(sum_scale_triple_kernel, dim3(3), dim3(256), 0, s, row_loss, row_nll, row_ul, N, inv_denom, loss_out, nll_out,
+                           ul_out);
         SAT_LAUNCH_CHECK();
     }
     return SAT_OK;

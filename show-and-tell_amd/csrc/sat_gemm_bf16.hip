@@ -14,6 +14,7 @@
 // logits), the bias gradient and every accumulation stay f32.  d loss / d logits is written ONCE, as bf16, by the CE kernel.
 #include "sat_internal.h"
 #include "sat_ce_ls.h"
+#include "sat_ce_ul.h"
 
 namespace {
 
@@ -394,6 +395,65 @@ __global__ __launch_bounds__(256) void ce_rows_ls_bf16grad_kernel(const float* _
     }
 }
 
+// ce_rows_ls_bf16grad_kernel with the unlikelihood term of sat_ce_ul.h: ce_rows_ul_kernel's register path (sat_elementwise.hip) with
+// the gradient leaving once, as bf16, pad columns zero.  The logits are only read, so the candidates' barrier just publishes the set.
+__global__ __launch_bounds__(256) void ce_rows_ul_bf16grad_kernel(const float* __restrict__ logits, long ldl, const int64_t* __restrict__ targets,
+                                                                  const int32_t* __restrict__ prefix, int T, int V, float inv_denom, float eps,
+                                                                  float alpha, float* __restrict__ row_loss, float* __restrict__ row_nll,
+                                                                  float* __restrict__ row_ul, bf16_t* __restrict__ grad, long ldg) {
+    __shared__ float sh[4];
+    __shared__ CeUlShared u;
+    constexpr int RC = 12;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* x = logits + (long)row * ldl;
+    const int nq = V >> 2;
+    const CeLsCoef k = ce_ls_coef(eps, V);
+    long tgt = targets[row];
+    tgt = tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt);
+    int b, pstart;
+    const int t = ce_ul_locate(prefix, T, row, b, pstart);
+    const bool ul_on = alpha > 0.0f && t > 0;      // uniform over the workgroup
+    if (ul_on) ce_ul_clear(u);                      // the barriers of the reductions below order it before ce_ul_candidates
+    f32x4 rc[RC];
+#pragma unroll
+    for (int c = 0; c < RC; ++c)
+        if (tid + c * 256 < nq) rc[c] = *(const f32x4*)(x + 4 * (tid + c * 256));
+    const CeLsRow r = ce_ls_row_stats<RC>(rc, nq, -INFINITY, false, V, [&](float v, bool is_max) { return blk_reduce(v, is_max, sh); });
+    float ul = 0.0f, scale = 1.0f;
+    bool clash = false;
+    if (ul_on) {
+        if (tid < 64) ce_ul_candidates(x, targets, (int)gridDim.x, pstart, t, b, (int)tgt, V, r.lse, alpha, u);
+        __syncthreads();                            // publishes u
+        ul = u.ul;
+        scale = 1.0f - alpha * u.W;
+        clash = u.clash != 0;
+    }
+    const int tq = (int)(tgt >> 2), te = (int)(tgt & 3);
+    bf16_t* g = grad + (long)row * ldg;
+#pragma unroll
+    for (int c = 0; c < RC; ++c) {
+        const int q = tid + c * 256;
+        if (q < nq) {
+            if (q == tq) {
+                const float nll = r.lse - rc[c][te];
+                row_loss[row] = ce_ul_loss(k, nll, r.smooth, alpha, ul);
+                if (row_nll) row_nll[row] = nll;
+                if (row_ul) row_ul[row] = ul;
+            }
+            const unsigned slots = ul_on ? *(const unsigned*)&u.slot[(4 * q) & (SAT_UL_HASH - 1)] : 0u;
+            bf16x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                o[e] = (bf16_t)ce_ul_grad(k, rc[c][e], r.lse, (4 * q + e) == (int)tgt, scale,
+                                          ce_ul_addend(u, (slots >> (8 * e)) & 255u, 4 * q + e, t, clash), inv_denom);
+            *(bf16x4*)(g + 4 * q) = o;
+        } else if (4 * q < ldg) {                       // pad columns [V, ldg): zeros (the K axis of the dHs product)
+            bf16x4 o = {(bf16_t)0.0f, (bf16_t)0.0f, (bf16_t)0.0f, (bf16_t)0.0f};
+            *(bf16x4*)(g + 4 * q) = o;
+        }
+    }
+}
+
 __device__ __forceinline__ void sum_scale_b_block(const float* __restrict__ v, int n, float scale, float* out) {
     __shared__ float sh[4];
     float s = 0.0f;
@@ -411,6 +471,15 @@ __global__ __launch_bounds__(256) void sum_scale_b_pair_kernel(const float* __re
                                                                float* out0, float* out1) {
     if (blockIdx.x == 0) sum_scale_b_block(v0, n, scale, out0);
     else sum_scale_b_block(v1, n, scale, out1);
+}
+
+// up to three such sums as one launch of three workgroups (loss, plain NLL, unlikelihood term); a NULL out is skipped
+__global__ __launch_bounds__(256) void sum_scale_b_triple_kernel(const float* __restrict__ v0, const float* __restrict__ v1,
+                                                                 const float* __restrict__ v2, int n, float scale, float* out0,
+                                                                 float* out1, float* out2) {
+    const float* v = blockIdx.x == 0 ? v0 : (blockIdx.x == 1 ? v1 : v2);
+    float* out = blockIdx.x == 0 ? out0 : (blockIdx.x == 1 ? out1 : out2);
+    if (out) sum_scale_b_block(v, n, scale, out);
 }
 
 int pad64(int x) { return (x + 63) / 64 * 64; }
@@ -523,12 +592,23 @@ extern "C" int64_t sat_vocab_bf16_ws_bytes(int N, int H, int V) { return vocab_b
 
 // models.py:53 + train.py:143 in the bf16 throughput mode: logits (f32, from bf16 operands) + mean CE; d loss / d logits is
 // left in the workspace as bf16 for sat_vocab_ce_bwd_bf16, next to the bf16 operand copies both calls share.
-// `ls`: the label-smoothed form (sat_vocab_ce_fwd_bf16_ls: smoothing, row_nll, nll_out); else sat_vocab_ce_fwd_bf16's own kernel
+// `ls`: the label-smoothed form (sat_vocab_ce_fwd_bf16_ls: smoothing, row_nll, nll_out); else sat_vocab_ce_fwd_bf16's own kernel.
+// `ul` (with ls): the unlikelihood form on top of it (sat_vocab_ce_fwd_bf16_ul: prefix, T, alpha, row_ul, ul_out)
+struct VocabUl {
+    const int32_t* prefix;
+    int T;
+    float alpha;
+    float *row_ul, *ul_out;
+};
+
 static int vocab_ce_fwd_bf16(const float* Hs, const float* w, const float* b, const int64_t* targets, int N, int H, int V,
                              float inv_denom, bool ls, float smoothing, float* logits, int64_t ldl, float* row_loss, float* row_nll,
-                             float* loss_out, float* nll_out, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+                             float* loss_out, float* nll_out, void* workspace, int64_t ws_bytes, sat_stream_t stream,
+                             const VocabUl* ul = nullptr) {
     if (!Hs || !w || !b || !targets || !logits || !row_loss || !workspace || ldl < V || (ldl % 4)) return SAT_ERR_ARG;
     if (ls && (!(smoothing >= 0.0f && smoothing < 1.0f) || (nll_out && !row_nll))) return SAT_ERR_ARG;      // (a NaN fails the first)
+    if (ul && (!ul->prefix || ul->T < 1 || !(ul->alpha >= 0.0f) || (ul->ul_out && !ul->row_ul))) return SAT_ERR_ARG;
+    if (ul && ul->T > SAT_UL_MAX_T) return SAT_ERR_UNSUPPORTED;
     if (!vocab_bf16_ok(N, H, V)) return SAT_ERR_UNSUPPORTED;
     const VocabWs L = vocab_ws(N, H, V);
     if (ws_bytes < L.total) return SAT_ERR_WORKSPACE;
@@ -549,7 +629,10 @@ static int vocab_ce_fwd_bf16(const float* Hs, const float* w, const float* b, co
                        (long)L.Npad, (float*)nullptr);
     SAT_LAUNCH_CHECK();
     SAT_TRY(launch_gemm(hsb, H, wb, H, logits, (long)ldl, b, N, V, H, 1, 0, s));
-    if (ls)
+    if (ul)
+        hipLaunchKernelGGL(ce_rows_ul_bf16grad_kernel, dim3(N), dim3(256), 0, s, logits, (long)ldl, targets, ul->prefix, ul->T, V, inv_denom,
+                           smoothing, ul->alpha, row_loss, row_nll, ul->row_ul, gb, (long)L.Vpad);
+    else if (ls)
         hipLaunchKernelGGL(ce_rows_ls_bf16grad_kernel, dim3(N), dim3(256), 0, s, logits, (long)ldl, targets, V, inv_denom, smoothing,
                            row_loss, row_nll, gb, (long)L.Vpad);
     else
@@ -557,6 +640,14 @@ static int vocab_ce_fwd_bf16(const float* Hs, const float* w, const float* b, co
                            (long)L.Vpad);
     SAT_LAUNCH_CHECK();
     if (!ls) nll_out = nullptr;
+    if (ul) {
+        if (loss_out || nll_out || ul->ul_out) {
+            hipLaunchKernelGGL(sum_scale_b_triple_kernel, dim3(3), dim3(256), 0, s, row_loss, row_nll, ul->row_ul, N, inv_denom, loss_out,
+                               nll_out, ul->ul_out);
+            SAT_LAUNCH_CHECK();
+        }
+        return SAT_OK;
+    }
     if (loss_out && nll_out) {
         hipLaunchKernelGGL(sum_scale_b_pair_kernel, dim3(2), dim3(256), 0, s, row_loss, row_nll, N, inv_denom, loss_out, nll_out);
         SAT_LAUNCH_CHECK();
@@ -581,6 +672,16 @@ extern "C" int sat_vocab_ce_fwd_bf16_ls(const float* Hs, const float* w, const f
                                         float* loss_out, float* nll_out, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
     return vocab_ce_fwd_bf16(Hs, w, b, targets, N, H, V, inv_denom, true, smoothing, logits, ldl, row_loss, row_nll, loss_out, nll_out,
                              workspace, ws_bytes, stream);
+}
+
+// the same with the unlikelihood term of sat_ce_ul.h on top (the candidates of a packed row come from `prefix`)
+extern "C" int sat_vocab_ce_fwd_bf16_ul(const float* Hs, const float* w, const float* b, const int64_t* targets, const int32_t* prefix, int T,
+                                        int N, int H, int V, float inv_denom, float smoothing, float alpha, float* logits, int64_t ldl,
+                                        float* row_loss, float* row_nll, float* row_ul, float* loss_out, float* nll_out, float* ul_out,
+                                        void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    const VocabUl ul = {prefix, T, alpha, row_ul, ul_out};
+    return vocab_ce_fwd_bf16(Hs, w, b, targets, N, H, V, inv_denom, true, smoothing, logits, ldl, row_loss, row_nll, loss_out, nll_out,
+                             workspace, ws_bytes, stream, &ul);
 }
 
 // train.py:144 for the vocab projection: dW[V,H], db[V], dHs[N,H] (all f32) from the workspace sat_vocab_ce_fwd_bf16 left

@@ -15,9 +15,11 @@ LSTM_NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
 # the bf16 throughput mode's projection + cross entropy (train.py:143) as one call, `sat_vocab_ce_fwd_bf16`: targets i64 [N],
 # inv_denom the loss scale, row_loss f32 [N], loss_out the 1-element loss slot, ws the uint8 workspace that keeps
 # d(loss)/d(logits) (bf16) for the backward's `sat_vocab_ce_bwd_bf16`.  smoothing > 0: label smoothing, `sat_vocab_ce_fwd_bf16_ls`, with
-# the plain NLL of the rows in row_nll f32 [N] and their scaled sum in nll_out f32 [1]; with 0 those two are not touched
-VocabCE = collections.namedtuple("VocabCE", "targets inv_denom row_loss loss_out ws smoothing row_nll nll_out",
-                                 defaults=(0.0, None, None))
+# the plain NLL of the rows in row_nll f32 [N] and their scaled sum in nll_out f32 [1]; with 0 those two are not touched.
+# alpha > 0: the unlikelihood term on top, `sat_vocab_ce_fwd_bf16_ul` over the pack layout of the call, with the rows' unweighted
+# terms in row_ul f32 [N] and their scaled sum in ul_out f32 [1] (row_nll / nll_out are then written too)
+VocabCE = collections.namedtuple("VocabCE", "targets inv_denom row_loss loss_out ws smoothing row_nll nll_out alpha row_ul ul_out",
+                                 defaults=(0.0, None, None, 0.0, None, None))
 
 
 def lstm_layers(params):
@@ -248,7 +250,13 @@ def decoder_forward(lib, features, params, captions, pi, ws=None, logits=None, c
     if ce is not None:
         # bf16 throughput mode: the projection on the bf16 matrix pipe (f32 accumulate, f32 logits), CE in f32 from them,
         # d(loss)/d(logits) left as bf16 in the workspace for decoder_backward
-        if ce.smoothing > 0:
+        if ce.alpha > 0:
+            L.check(lib.sat_vocab_ce_fwd_bf16_ul(L.ptr(tapes["X"][-1]), L.ptr(lin_w), L.ptr(lin_b), L.ptr(ce.targets), L.ptr(pi.prefix_dev),
+                                                 pi.T, N, lin_w.shape[1], V, float(ce.inv_denom), float(ce.smoothing), float(ce.alpha),
+                                                 L.ptr(logits), logits.stride(0), L.ptr(ce.row_loss), L.ptr(ce.row_nll),
+                                                 L.ptr(ce.row_ul), L.ptr(ce.loss_out), L.ptr(ce.nll_out), L.ptr(ce.ul_out),
+                                                 L.ptr(ce.ws), ce.ws.numel(), st), "sat_vocab_ce_fwd_bf16_ul")
+        elif ce.smoothing > 0:
             L.check(lib.sat_vocab_ce_fwd_bf16_ls(L.ptr(tapes["X"][-1]), L.ptr(lin_w), L.ptr(lin_b), L.ptr(ce.targets), N, lin_w.shape[1],
                                                  V, float(ce.inv_denom), float(ce.smoothing), L.ptr(logits), logits.stride(0),
                                                  L.ptr(ce.row_loss), L.ptr(ce.row_nll), L.ptr(ce.loss_out), L.ptr(ce.nll_out),

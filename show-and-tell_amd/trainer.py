@@ -16,7 +16,7 @@ as each bucket's gradients become final and overlapped with the rest of the back
 import torch
 
 from . import _lib as L
-from .criterion import _check_smoothing
+from .criterion import MAX_UL_STEPS, _check_smoothing, _check_unlikelihood
 from .decoder import LSTMWorkspaces, VocabCE, decoder_backward, decoder_forward, rollout_forward
 from .models import ShowAndTell, draw_ss_seed, fc_bn1d_backward, fc_bn1d_forward
 from .optim import check_max_norm, check_weight_decay, exempt_array, group_weight_decay, merge_ranges
@@ -100,7 +100,15 @@ class TrainStep:
     inv_denom * sum of the rows' plain NLL, for a perplexity -- it is not all-reduced: in a data-parallel step inv_denom is the
     global token count, so the ranks' values add up to the global NLL.  With label_smoothing == 0 the loss is the NLL and `last_nll`
     is the loss slot itself (which a data-parallel step does all-reduce).  `scst_step` and `validation_step` ignore the attribute:
-    SCST weights its own rows, validation reports the plain CE of eval.py:95."""
+    SCST weights its own rows, validation reports the plain CE of eval.py:95.
+    unlikelihood (a settable, checked attribute like max_grad_norm, not a constructor argument; a finite value >= 0, default 0): token-level unlikelihood training (criterion.py's module
+    docstring; arithmetic at `sat_ce_rows_ul` in include/sat_hip.h) -- every target row also pays that weight times
+    sum_c -log(1 - p_c) over the distinct ground-truth tokens c of the earlier steps of its own caption.  The candidates are always
+    the ground-truth targets, whatever scheduled sampling feeds.  `sat_ce_rows_ul` in place in the f32 mode,
+    `sat_vocab_ce_fwd_bf16_ul` in the bf16 mode; with 0 both modes make exactly the calls they make without it.  Captions of more
+    than 65 tokens (64 target steps) are a ValueError.  `last_ul` (1-element device tensor, None with 0) holds THIS RANK's inv_denom *
+    sum of the rows' unweighted terms, rank-local like `last_nll`, which is then the plain NLL as with label smoothing.  `scst_step`
+    and `validation_step` ignore it too."""
 
     def __init__(self, model, lr=1e-3, grad_clip=0.1, betas=(0.9, 0.999), eps=1e-8, label_smoothing=0.0):
         if not isinstance(model, ShowAndTell):
@@ -111,7 +119,7 @@ class TrainStep:
         self.flat = FlatParams(model)
         self.lr, self.grad_clip, self.betas, self.eps = lr, grad_clip, betas, eps
         self.label_smoothing = label_smoothing
-        self.last_nll = None
+        self.last_nll = self.last_ul = None
         self.step_count = 0
         self.buckets = self.flat.buckets
         self.flat_grad = self.flat.grads
@@ -134,6 +142,16 @@ class TrainStep:
     @label_smoothing.setter
     def label_smoothing(self, value):
         self._label_smoothing = _check_smoothing(value)
+
+    _unlikelihood = 0.0
+
+    @property
+    def unlikelihood(self):
+        return self._unlikelihood
+
+    @unlikelihood.setter
+    def unlikelihood(self, value):
+        self._unlikelihood = _check_unlikelihood(value)
 
     # -- global-norm clipping and decoupled weight decay (attributes, not constructor arguments) ---------------------------------
     # max_grad_norm: torch.nn.utils.clip_grad_norm_'s max_norm over the whole flat gradient (after the bucket all-reduces in a
@@ -262,18 +280,25 @@ class TrainStep:
         params = dict(dec.named_parameters())
         loss_slot = flat.grads[flat.loss_slot:flat.loss_slot + 1]
         ce = mixed_ws = None
-        smoothing = self._label_smoothing
-        if smoothing > 0 and "row_nll" not in bufs:
+        smoothing, alpha = self._label_smoothing, self._unlikelihood
+        if alpha > 0 and pi.T > MAX_UL_STEPS:
+            raise ValueError("unlikelihood supports captions of at most %d target steps (got %d)" % (MAX_UL_STEPS, pi.T))
+        if (smoothing > 0 or alpha > 0) and "row_nll" not in bufs:
             bufs["row_nll"], bufs["nll"] = torch.empty(N, device=dev), torch.empty(1, device=dev)
-        self.last_nll = bufs["nll"] if smoothing > 0 else loss_slot
+        if alpha > 0 and "row_ul" not in bufs:
+            bufs["row_ul"], bufs["ul"] = torch.empty(N, device=dev), torch.empty(1, device=dev)
+        self.last_nll = bufs["nll"] if (smoothing > 0 or alpha > 0) else loss_slot
+        self.last_ul = bufs["ul"] if alpha > 0 else None
         if self.decoder_gemm_dtype == "bf16":
             wsb = lib.sat_vocab_bf16_ws_bytes(N, dec.hidden_size, V)
             if wsb > 0:
                 if "vocab_bf16_ws" not in bufs:
                     bufs["vocab_bf16_ws"] = torch.empty(wsb, dtype=torch.uint8, device=dev)
                 ce = VocabCE(bufs["targets"], inv_denom, bufs["row_loss"], loss_slot, bufs["vocab_bf16_ws"])
-                if smoothing > 0:
+                if smoothing > 0 or alpha > 0:
                     ce = ce._replace(smoothing=smoothing, row_nll=bufs["row_nll"], nll_out=bufs["nll"])
+                if alpha > 0:
+                    ce = ce._replace(alpha=alpha, row_ul=bufs["row_ul"], ul_out=bufs["ul"])
             # the LSTM layers' batched GEMMs on the bf16 matrix pipe too
             if "lstm_mixed_ws" not in bufs:
                 need = max(lib.sat_lstm_mixed_ws_bytes(N, E if l == 0 else dec.hidden_size, dec.hidden_size) for l in range(dec.num_layers))
@@ -293,7 +318,13 @@ class TrainStep:
         self.last_dropped_tape = tapes["X"][-1] if dropout is not None else None
         if ss is not None:
             dec.last_ss_inputs, dec.last_ss_seed = tapes["captions"], ss[1]
-        if ce is None and smoothing > 0:
+        if ce is None and alpha > 0:
+            # ---- the same with the unlikelihood term over each row's earlier ground-truth targets, in place ----
+            L.check(lib.sat_ce_rows_ul(L.ptr(logits), logits.stride(0), L.ptr(bufs["targets"]), L.ptr(pi.prefix_dev), pi.T, N, V,
+                                       float(inv_denom), smoothing, alpha, L.ptr(logits), logits.stride(0), L.ptr(bufs["row_loss"]),
+                                       L.ptr(bufs["row_nll"]), L.ptr(bufs["row_ul"]), L.ptr(loss_slot), L.ptr(bufs["nll"]),
+                                       L.ptr(bufs["ul"]), st), "sat_ce_rows_ul")
+        elif ce is None and smoothing > 0:
             # ---- smoothed loss, plain NLL + d(loss)/d(logits) in place (nn.CrossEntropyLoss(label_smoothing=)) ----
             L.check(lib.sat_ce_rows_ls(L.ptr(logits), logits.stride(0), L.ptr(bufs["targets"]), N, V, float(inv_denom), smoothing,
                                        L.ptr(logits), logits.stride(0), L.ptr(bufs["row_loss"]), L.ptr(bufs["row_nll"]),
