@@ -1249,6 +1249,26 @@ int sat_adamw_step(float* p, float* g, float* m, float* v, int64_t n, float lr, 
                    int step, float weight_decay, const int64_t* exempt, int n_exempt, float max_norm, const double* partials,
                    int n_partials, double* norm_out, const float* skip_if_nonzero, sat_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Exponential moving average of the parameters (Polyak averaging; added within ABI 18; sat_optim.hip), one launch behind the
+ * update on the same stream, and the exchange that puts the average into the model and takes it out again.
+ * sat_ema_update: ema[i] = fma(w, p[i] - ema[i], ema[i]) with w = (float)(1.0 - (double)decay) formed on the host, the difference
+ *   rounded to f32, then ONE fused multiply-add: two roundings per element, the same in the 16-byte loop and in the n % 4 tail,
+ *   so an element's bits do not depend on n, the grid or the pointer offset.  12 B per parameter.
+ *   The whole launch does nothing -- ema keeps every bit -- when the update in front of it was dropped:
+ *     skip_if_nonzero (device f32 word, may be NULL) is non-zero: the step's fault word, which sat_clamp_adam_step_guarded and
+ *       sat_adamw_step read and neither of them writes;
+ *     norm_state (2 device doubles, may be NULL) has norm_state[1] > 0 or a norm_state[0] that is not finite: the
+ *       {norm, non-finite elements} pair sat_adamw_step wrote to norm_out in front of this launch.
+ *   SAT_ERR_ARG before any launch: NULL ema / p, n < 1, ema or p not 16-byte aligned, norm_state not 8-byte aligned, decay NaN or
+ *   outside (0, 1).  ema and p must not overlap.
+ * sat_swap_f32: a[i] <-> b[i], exact, no third buffer.  SAT_ERR_ARG before any launch: NULL or misaligned (16 bytes) a / b,
+ *   n < 1, overlapping ranges (a == b included).
+ * Both: 256 threads, 16-byte accesses, a grid that depends on n only (at most 768 workgroups), no atomics, no LDS. */
+int sat_ema_update(float* ema, const float* p, int64_t n, float decay, const float* skip_if_nonzero, const double* norm_state,
+                   sat_stream_t stream);
+int sat_swap_f32(float* a, float* b, int64_t n, sat_stream_t stream);
+
 /* column sums: out[c] = sum_r x[r*ld + c]  (bias gradients) */
 int sat_colsum_f32(const float* x, int64_t ld, int rows, int cols, float* out, sat_stream_t stream);
 /* f32 -> bf16 / bf16 -> f32 casts (weight shadow copies) */

@@ -25,7 +25,7 @@ from .score import CaptionScores, candidate_captions, rescore, retrieval_metrics
 from .langstats import BleuScorer, MixedReward, RougeLScorer  # noqa: F401
 from .scst import SelfCritical, ce_rows_weighted, group_sum_rows, scst_loss, scst_weights, scst_weights_group  # noqa: F401
 from .criterion import CrossEntropy, cross_entropy  # noqa: F401
-from .optim import FusedClampAdam, no_decay_names, no_decay_params  # noqa: F401
+from .optim import FusedClampAdam, ema_decay_at, no_decay_names, no_decay_params  # noqa: F401
 from .pack import PackInfo, pack_targets  # noqa: F401
 from .resnet import RESNET152, conv_flops  # noqa: F401
 from .trainer import (DataParallelStep, FlatParams, TrainStep, decode_shard, dp_shard, gather_decoded,  # noqa: F401

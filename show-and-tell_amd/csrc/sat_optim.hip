@@ -12,6 +12,10 @@
 //                       is the same in every workgroup: all of them hold the same bits of `total` and `nonfinite` and so take the
 //                       same decision with no second launch and no host read.  nonfinite > 0 or a non-finite total: the kernel
 //                       returns without touching p, g, m, v -- the contract of the skip word.
+//   ema_kernel        : the exponential moving average of the parameters, ema += (1 - decay) (p - ema), one launch behind the update
+//                       (12 B/param: read p and ema, write ema).  It reads the two things that say "the update was dropped" -- the
+//                       skip word, and the {norm, nonfinite} pair adamw_kernel wrote -- and then leaves ema alone as well.
+//   swap_kernel       : a <-> b element by element (the averaged weights in and out of the model, no third buffer).
 #include "sat_internal.h"
 
 #include <cmath>
@@ -153,6 +157,45 @@ __global__ __launch_bounds__(OPT_BLOCK) void adamw_kernel(float* __restrict__ p,
     }
 }
 
+// The difference rounded, then one fma: every element sees the same two roundings in the 16-byte loop and in the scalar tail.
+__device__ __forceinline__ float ema_one(float e, float p, float w) { return __fmaf_rn(w, __fsub_rn(p, e), e); }
+
+// `skip`, `norm_state` (either may be NULL): the conditions under which clamp_adam_kernel / adamw_kernel returned without touching
+// p -- a non-zero fault word; a non-finite-element count > 0 or a norm that is not finite (norm = sqrt(total): finite exactly when
+// adamw_kernel's `total` is).  Then nothing is written here either.
+__global__ __launch_bounds__(OPT_BLOCK) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float w,
+                                                        const float* __restrict__ skip, const double* __restrict__ norm_state) {
+    if (skip && *skip != 0.0f) return;
+    if (norm_state && (norm_state[1] > 0.0 || !(fabs(norm_state[0]) <= 1.79769313486231570815e+308))) return;
+    const long n4 = n >> 2;
+    for (long i = (long)blockIdx.x * OPT_BLOCK + threadIdx.x; i < n4; i += (long)gridDim.x * OPT_BLOCK) {
+        f32x4 ee = ((f32x4*)ema)[i];
+        const f32x4 pp = ((const f32x4*)p)[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ee[k] = ema_one(ee[k], pp[k], w);
+        ((f32x4*)ema)[i] = ee;
+    }
+    // tail (n % 4): the first lanes of workgroup 0
+    const long i = (n4 << 2) + threadIdx.x;
+    if (blockIdx.x == 0 && i < n) ema[i] = ema_one(ema[i], p[i], w);
+}
+
+// the host has checked that the two ranges do not overlap
+__global__ __launch_bounds__(OPT_BLOCK) void swap_kernel(float* __restrict__ a, float* __restrict__ b, long n) {
+    const long n4 = n >> 2;
+    for (long i = (long)blockIdx.x * OPT_BLOCK + threadIdx.x; i < n4; i += (long)gridDim.x * OPT_BLOCK) {
+        const f32x4 x = ((f32x4*)a)[i], y = ((f32x4*)b)[i];
+        ((f32x4*)a)[i] = y;
+        ((f32x4*)b)[i] = x;
+    }
+    const long i = (n4 << 2) + threadIdx.x;
+    if (blockIdx.x == 0 && i < n) {
+        const float x = a[i], y = b[i];
+        a[i] = y;
+        b[i] = x;
+    }
+}
+
 }  // namespace
 
 extern "C" int sat_grad_sumsq_partials(int64_t n) { return n < 1 ? 0 : sumsq_grid((long)n); }
@@ -200,6 +243,29 @@ extern "C" int sat_adamw_step(float* p, float* g, float* m, float* v, int64_t n,
     const int grid = (int)(blocks > OPT_GRID_CAP ? OPT_GRID_CAP : blocks);             // clamp_adam_kernel's grid
     hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(OPT_BLOCK), 0, (hipStream_t)stream, p, g, m, v, (long)n, beta1, beta2, eps,
                        clip, step_size, bc2_sqrt, decay, table, (double)max_norm, partials, n_partials, norm_out, skip_if_nonzero);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
+extern "C" int sat_ema_update(float* ema, const float* p, int64_t n, float decay, const float* skip_if_nonzero,
+                              const double* norm_state, sat_stream_t stream) {
+    if (!ema || !p || n < 1) return SAT_ERR_ARG;
+    if ((((uintptr_t)ema | (uintptr_t)p) & 15) != 0 || ((uintptr_t)norm_state & 7) != 0) return SAT_ERR_ARG;
+    if (!(decay > 0.0f && decay < 1.0f)) return SAT_ERR_ARG;                           // (NaN fails the comparison)
+    const float w = (float)(1.0 - (double)decay);
+    hipLaunchKernelGGL(ema_kernel, dim3(sumsq_grid((long)n)), dim3(OPT_BLOCK), 0, (hipStream_t)stream, ema, p, (long)n, w,
+                       skip_if_nonzero, norm_state);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
+extern "C" int sat_swap_f32(float* a, float* b, int64_t n, sat_stream_t stream) {
+    if (!a || !b || n < 1) return SAT_ERR_ARG;
+    if ((((uintptr_t)a | (uintptr_t)b) & 15) != 0) return SAT_ERR_ARG;
+    const uintptr_t lo = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)a : (uintptr_t)b;
+    const uintptr_t hi = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)b : (uintptr_t)a;
+    if ((hi - lo) / sizeof(float) < (uintptr_t)n) return SAT_ERR_ARG;                   // the ranges overlap
+    hipLaunchKernelGGL(swap_kernel, dim3(sumsq_grid((long)n)), dim3(OPT_BLOCK), 0, (hipStream_t)stream, a, b, (long)n);
     SAT_LAUNCH_CHECK();
     return SAT_OK;
 }

@@ -15,7 +15,17 @@ is set too), then one `sat_adamw_step`.  Nothing is read back: `last_grad_norm` 
 Inf / NaN gradient elements} (None until a step with `max_norm` has run; `max_norm=float("inf")` measures without clipping).
 A step whose gradient holds an Inf or NaN is DROPPED on the device -- parameters, moments and gradient stay bit for bit what they
 were -- while `step_count` still advances (the bias correction of later steps sees one step more); `last_grad_norm[1] > 0` tells.
-With `max_norm=None` and `weight_decay=0` the step makes exactly the calls it makes without the keywords."""
+With `max_norm=None` and `weight_decay=0` the step makes exactly the calls it makes without the keywords.
+
+`ema_decay`, `ema_warmup` (checked, settable ATTRIBUTES, not constructor keywords; 0.0 = off, otherwise a float in (0, 1)) keep an
+exponential moving average of the parameters in a twin of the flat buffer (`ema`, None until the attribute first becomes non-zero,
+then a copy of the parameters): ONE `sat_ema_update` launch over the whole buffer behind the update(s) of a `step()`,
+ema += (1 - d) (p - ema) with d = `ema_decay_at(ema_decay, step_count, ema_warmup)`.  A parameter whose gradient is None does not
+move, and an average that equals it does not either; with `max_norm` the launch reads `last_grad_norm`, so a step dropped for a
+non-finite gradient leaves the average alone.  `with opt.averaged_weights():` exchanges parameters and averages in place
+(`sat_swap_f32`; `step()` inside raises), `ema_params()` are views of the averages in the order of the parameters, `reset_ema()`
+copies the parameters again, and `state_dict()` has an `"ema"` entry {"decay", "warmup", "params"} only once the buffer exists."""
+import contextlib
 import ctypes
 import math
 
@@ -55,6 +65,72 @@ def check_max_norm(value, what="max_norm"):
     if isinstance(value, bool) or not isinstance(value, (int, float)) or not value > 0:
         raise ValueError("%s must be a number > 0 (got %r)" % (what, value))
     return float(value)
+
+
+def check_ema_decay(value, what="ema_decay"):
+    """0 (off), or a finite float in (0, 1)"""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (value == 0 or 0.0 < value < 1.0):
+        raise ValueError("%s must be 0 (off) or a number in (0, 1) (got %r)" % (what, value))
+    return float(value)
+
+
+def check_ema_warmup(value):
+    if not isinstance(value, bool):
+        raise ValueError("ema_warmup must be a bool (got %r)" % (value,))
+    return value
+
+
+def ema_decay_at(decay, t, warmup=False):
+    """The decay of the update that follows optimizer step `t` (1-based: `step_count` after its increment).  With warm-up
+    min(decay, (1 + t) / (10 + t)) -- TensorFlow's `num_updates` rule for ExponentialMovingAverage, which timm's ModelEma uses too: the
+    first averages follow the parameters closely instead of remembering the initial ones for 1 / (1 - decay) steps."""
+    return min(decay, (1 + t) / (10 + t)) if warmup else decay
+
+
+def ema_update(lib, ema, params, n, decay, skip=None, norm_state=None):
+    """one sat_ema_update launch on the current stream (addresses or tensors; `skip`, `norm_state`: the words of the update in front)"""
+    L.check(lib.sat_ema_update(L.ptr(ema), L.ptr(params), n, decay, L.ptr(skip), L.ptr(norm_state), L.stream()), "sat_ema_update")
+
+
+def ema_entry(decay, warmup, tensors):
+    """the "ema" entry of an optimizer state dict"""
+    return {"decay": decay, "warmup": warmup, "params": tensors}
+
+
+def check_ema_entry(entry, shapes):
+    """(decay, warmup, tensors) of a loaded "ema" entry, checked like the moments (ValueError)"""
+    tensors = list(entry["params"])
+    if len(tensors) != len(shapes):
+        raise ValueError("the averaged weights hold %d parameters, expected %d" % (len(tensors), len(shapes)))
+    for i, (t, shape) in enumerate(zip(tensors, shapes)):
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("averaged parameter %d has shape %s, expected %s" % (i, tuple(t.shape), tuple(shape)))
+    return check_ema_decay(entry["decay"]), check_ema_warmup(entry["warmup"]), tensors
+
+
+@contextlib.contextmanager
+def swapped_in(owner, live, ema, n, params):
+    """`averaged_weights()` of both optimizers: `live` <-> `ema` in place (sat_swap_f32) with the version counters of `params` (views
+    of `live`) bumped, and back on the way out.  `owner._averaged` is set in between: its update entry points refuse then."""
+    if ema is None:
+        raise RuntimeError("averaged_weights(): no average is kept (ema_decay has never been set)")
+    if owner._averaged:
+        raise RuntimeError("averaged_weights() is already active: the blocks do not nest")
+
+    def swap():
+        L.check(owner.lib.sat_swap_f32(L.ptr(live), L.ptr(ema), n, L.stream()), "sat_swap_f32")
+        torch.autograd.graph.increment_version(params)       # caches keyed on `_version` see the exchange
+
+    swap()
+    owner._averaged = True
+    try:
+        yield owner
+    finally:
+        owner._averaged = False
+        swap()
+
+
+AVERAGED_NOTE = "inside averaged_weights() the parameters are the averaged ones: %s is refused until the block is left"
 
 
 def merge_ranges(ranges):
@@ -120,6 +196,48 @@ class FusedClampAdam(torch.optim.Optimizer):
             self._views.append(self.flat_grad[o:o + n].view(p.shape))
             p.grad = self._views[-1]
 
+    # -- averaged weights: ema_decay / ema_warmup are checked, settable attributes (0.0 = off; see the module docstring) ------------
+    _ema_decay, _ema_warmup, _averaged, ema = 0.0, False, False, None
+
+    @property
+    def ema_decay(self):
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, value):
+        self._ema_decay = check_ema_decay(value)
+        # (an optimizer made without __init__ has no flat buffer: the first step() copies)
+        if self._ema_decay > 0 and self.ema is None and getattr(self, "flat", None) is not None:
+            self.ema = self.flat.clone()
+
+    @property
+    def ema_warmup(self):
+        return self._ema_warmup
+
+    @ema_warmup.setter
+    def ema_warmup(self, value):
+        self._ema_warmup = check_ema_warmup(value)
+
+    def reset_ema(self):
+        """the average starts again from the parameters as they are now"""
+        if self.ema is None:
+            raise RuntimeError("reset_ema(): no average is kept (ema_decay has never been set)")
+        if self._averaged:
+            raise RuntimeError(AVERAGED_NOTE % "reset_ema()")
+        self.ema.copy_(self.flat)
+
+    def ema_params(self):
+        """views of the averaged weights, in the order (and shapes) of the optimizer's parameters"""
+        if self.ema is None:
+            raise RuntimeError("ema_params(): no average is kept (ema_decay has never been set)")
+        src = self.flat if self._averaged else self.ema        # (inside averaged_weights() the two buffers have changed places)
+        return [src[o:o + n].view(p.shape) for p, (o, n) in zip(self._params, self._slices)]
+
+    def averaged_weights(self):
+        """`with opt.averaged_weights():` -- the parameters hold the averaged weights inside the block (exchanged in place, version
+        counters bumped) and their own values again after it; `step()` inside and a nested entry raise RuntimeError"""
+        return swapped_in(self, self.flat, self.ema, self.n, self._params)
+
     def zero_grad(self, set_to_none=False):
         """One memset; the `.grad` of every parameter stays the view into the flat gradient buffer, so the backward
         accumulates in place.  (`model.zero_grad()` -- train.py:137 -- drops the views; `step()` then copies the gradients in.)"""
@@ -129,6 +247,10 @@ class FusedClampAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if self._averaged:
+            raise RuntimeError(AVERAGED_NOTE % "step()")
+        if self._ema_decay > 0 and self.ema is None:
+            self.ema = self.flat.clone()                      # (the attribute was set before the buffers existed)
         loss = closure() if closure is not None else None
         src, dst, missing = [], [], []
         for i, (p, v) in enumerate(zip(self._params, self._views)):
@@ -159,6 +281,11 @@ class FusedClampAdam(torch.optim.Optimizer):
                                                      self.step_count, L.stream()), "sat_clamp_adam_step")
         elif segs:
             self._adamw_segments(segs, g, clip)
+        if self._ema_decay > 0:
+            # ONE launch over the whole buffer behind the update(s): a parameter without a gradient did not move, and an average
+            # that equals it does not either; a step dropped for a non-finite gradient (max_norm) leaves the average alone too
+            ema_update(self.lib, self.ema, self.flat, self.n, ema_decay_at(self._ema_decay, self.step_count, self._ema_warmup),
+                       norm_state=self.last_grad_norm if self.max_norm is not None else None)
         # the kernel wrote the parameters through raw pointers: move their version counters as an in-place torch update
         # would, so that caches keyed on `_version` (kernel-layout weight copies of a conv stack) see the step
         torch.autograd.graph.increment_version(self._params)
@@ -200,7 +327,10 @@ class FusedClampAdam(torch.optim.Optimizer):
         group = {"lr": g["lr"], "betas": tuple(g["betas"]), "eps": g["eps"], "weight_decay": wd if wd > 0 else 0, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "decoupled_weight_decay": wd > 0, "params": list(range(len(self._params)))}
-        return {"state": state, "param_groups": [group], "grad_clip": self.clip, "max_grad_norm": self.max_norm}
+        sd = {"state": state, "param_groups": [group], "grad_clip": self.clip, "max_grad_norm": self.max_norm}
+        if self.ema is not None:
+            sd["ema"] = ema_entry(self._ema_decay, self._ema_warmup, [t.clone() for t in self.ema_params()])
+        return sd
 
     def load_state_dict(self, sd):
         group = sd["param_groups"][0]
@@ -212,6 +342,15 @@ class FusedClampAdam(torch.optim.Optimizer):
         if "max_grad_norm" in sd:
             off = sd["max_grad_norm"] is None or sd["max_grad_norm"] == 0          # (0.0: TrainStep's "off")
             self.max_norm = None if off else check_max_norm(sd["max_grad_norm"])
+        if "ema" in sd:                                       # (absent: the averaging state stays what it is)
+            if self._averaged:
+                raise RuntimeError(AVERAGED_NOTE % "load_state_dict() with averaged weights")
+            decay, warmup, tensors = check_ema_entry(sd["ema"], [p.shape for p in self._params])
+            if self.ema is None:
+                self.ema = torch.zeros_like(self.flat)
+            for t, (o, n) in zip(tensors, self._slices):
+                self.ema[o:o + n].copy_(t.reshape(-1))
+            self._ema_decay, self._ema_warmup = decay, warmup
         self.exp_avg.zero_()
         self.exp_avg_sq.zero_()
         steps = set()

@@ -19,7 +19,8 @@ from . import _lib as L
 from .criterion import MAX_UL_STEPS, _check_smoothing, _check_unlikelihood
 from .decoder import LSTMWorkspaces, VocabCE, decoder_backward, decoder_forward, rollout_forward
 from .models import ShowAndTell, draw_ss_seed, fc_bn1d_backward, fc_bn1d_forward
-from .optim import check_max_norm, check_weight_decay, exempt_array, group_weight_decay, merge_ranges
+from .optim import (AVERAGED_NOTE, check_ema_decay, check_ema_entry, check_ema_warmup, check_max_norm, check_weight_decay,
+                    ema_decay_at, ema_entry, ema_update, exempt_array, group_weight_decay, merge_ranges, swapped_in)
 from .pack import PackInfo
 from .scst import SelfCritical, ce_rows_weighted, check_group, group_sum_rows, scst_weights, scst_weights_group
 from .watch import ResidencyWatch, StatusRing
@@ -79,6 +80,7 @@ class FlatParams:
         self.grads = torch.zeros(off + 4, device=dev)
         self.m = torch.zeros(off, device=dev)
         self.v = torch.zeros(off, device=dev)
+        self.ema = None          # the averaged weights, a twin of `params`: made when TrainStep.ema_decay first becomes non-zero
         for g in groups:
             for name, p in g:
                 o, n, shape = self.slices[name]
@@ -208,6 +210,74 @@ class TrainStep:
             raise ValueError("no_decay: %s are not parameters of the flat buffer (%s)" % (unknown, sorted(slices)))
         return merge_ranges([(slices[n][0], slices[n][0] + slices[n][1]) for n in set(names or ())])
 
+    # -- averaged weights (Polyak / exponential moving average of the trained parameters; attributes, not constructor arguments) --
+    # ema_decay: 0.0 = off, otherwise a float in (0, 1).  `flat.ema` is None until the attribute first becomes non-zero; it then
+    #   starts as a copy of `flat.params` (`reset_ema()` copies again), and every `optimizer_step` launches sat_ema_update behind the
+    #   update on the same stream: ema += (1 - d) (params - ema), d = `ema_decay_at(ema_decay, step_count, ema_warmup)`.  The launch
+    #   reads the step's fault word and, with max_grad_norm set, `last_grad_norm`: an update dropped on the device for a fault or a
+    #   non-finite gradient does not move the average either, and nothing is read back.  Setting 0 again stops the updates and
+    #   keeps the buffer.  `scst_step` and `DataParallelStep` come through `optimizer_step`; every rank computes the same bits
+    #   from the same parameters, so nothing is exchanged.  With 0 `optimizer_step` makes exactly the calls it makes without it.
+    # ema_warmup (bool): the decay of step t is min(ema_decay, (1 + t) / (10 + t)), t = `step_count` after this step's increment --
+    #   which a fault rolls back, so the schedule follows the rollback.
+    _ema_decay, _ema_warmup, _averaged = 0.0, False, False
+
+    @property
+    def ema_decay(self):
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, value):
+        self._ema_decay = check_ema_decay(value)
+        # an engine made without __init__ has no flat buffer yet: the first optimizer_step then copies, before its update
+        if self._ema_decay > 0 and getattr(self, "flat", None) is not None:
+            self._start_ema()
+
+    @property
+    def ema_warmup(self):
+        return self._ema_warmup
+
+    @ema_warmup.setter
+    def ema_warmup(self, value):
+        self._ema_warmup = check_ema_warmup(value)
+
+    def _ema(self):
+        return getattr(self.flat, "ema", None)
+
+    def _start_ema(self):
+        if self._ema() is None:
+            self.flat.ema = self.flat.params.clone()
+
+    def reset_ema(self):
+        """the average starts again from the parameters as they are now"""
+        if self._ema() is None:
+            raise RuntimeError("reset_ema(): no average is kept (ema_decay has never been set)")
+        if self._averaged:
+            raise RuntimeError(AVERAGED_NOTE % "reset_ema()")
+        self.flat.ema.copy_(self.flat.params)
+
+    def averaged_weights(self):
+        """`with step.averaged_weights():` -- `flat.params` and `flat.ema` change places (sat_swap_f32, in place, no third buffer)
+        and the parameters' version counters are bumped, so the weight caches keyed on `_version` see it: the model's parameters
+        are views of the flat buffer, hence every decode, `validation_step` and `score_captions` inside the block runs on the
+        averaged weights.  On the way out (also by an exception) they change places again.  Inside the block `optimizer_step`,
+        `step`, `scst_step`, `forward_backward` and a nested entry raise RuntimeError; so does the entry when no average is kept.
+        BatchNorm running statistics and the frozen stack are the live model's: they are not averaged."""
+        return swapped_in(self, self.flat.params, self._ema(), self.flat.n, self._params_list)
+
+    def averaged_state_dict(self):
+        """`model.state_dict()` with the trainable entries taken from the average and everything else -- the frozen conv weights,
+        every BatchNorm buffer, num_batches_tracked -- cloned from the live model: what to save as `model-best.pth`.  It loads into
+        a fresh ShowAndTell, and so into a member of `sat.Ensemble`."""
+        if self._ema() is None:
+            raise RuntimeError("averaged_state_dict(): no average is kept (ema_decay has never been set)")
+        src = self.flat.params if self._averaged else self.flat.ema       # (inside averaged_weights() they have changed places)
+        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        for name, _ in self._trainable():
+            o, n, shape = self.flat.slices[name]
+            sd[name] = src[o:o + n].view(shape).clone()
+        return sd
+
     # -- encoder look-ahead ---------------------------------------------------------------------------
     def prefetch_encoder(self, images):
         """Start the frozen conv stack of a LATER batch on a side stream (`EncoderCNN.prefetch`: up to three batches' stacks in
@@ -250,6 +320,8 @@ class TrainStep:
         images, captions, lengths = batch
         lib, model, flat = self.lib, self.model, self.flat
         dec = model.decoder
+        if self._averaged:
+            raise RuntimeError(AVERAGED_NOTE % "a training step")
         if not model.training:
             raise RuntimeError("TrainStep needs model.train() (batch-statistics BatchNorm, train.py never calls eval())")
         dropout = dec.dropout_plan(sampling=dec.ss_prob > 0)         # host checks, before anything is launched or drawn
@@ -409,6 +481,8 @@ class TrainStep:
         S, baseline = check_group(num_samples, baseline)             # host checks, before anything is launched
         lib, model, flat = self.lib, self.model, self.flat
         dec = model.decoder
+        if self._averaged:
+            raise RuntimeError(AVERAGED_NOTE % "a training step")
         if not model.training:
             raise RuntimeError("TrainStep needs model.train() (batch-statistics BatchNorm, train.py never calls eval())")
         dec.dropout_plan(sampling=True, what="a rollout (scst_step)")
@@ -498,9 +572,13 @@ class TrainStep:
         every later one until the host has seen the flag (sticky), raised RuntimeError (at the latest on the next submit;
         `check_ids()` at once) and rolled the step count back.  fixed_lag (data-parallel steps): look at the flag of the step
         submitted `fixed_lag` steps ago, blocking, instead of polling (`_watch_fixed_lag`)."""
+        if self._averaged:
+            raise RuntimeError(AVERAGED_NOTE % "optimizer_step()")
         before = self.step_count
         self.step_count += 1
         f = self.flat
+        if self._ema_decay > 0:
+            self._start_ema()                # (only an engine that had no flat buffer when the attribute was set copies here)
         if self._max_grad_norm == 0 and self._weight_decay == 0:
             L.check(self.lib.sat_clamp_adam_step_guarded(L.ptr(f.params), L.ptr(f.grads), L.ptr(f.m), L.ptr(f.v), f.n,
                                                          float(self.lr if lr is None else lr), self.betas[0], self.betas[1],
@@ -508,6 +586,11 @@ class TrainStep:
                                                          L.stream()), "sat_clamp_adam_step_guarded")
         else:
             self._adamw_step(float(self.lr if lr is None else lr))
+        if self._ema_decay > 0:
+            # behind the update on its stream, behind the same two words: the fault slot (neither update kernel writes it: it lies
+            # past the n elements they cover) and, with a norm, the {norm, non-finite} pair sat_adamw_step has just written
+            ema_update(self.lib, f.ema, f.params, f.n, ema_decay_at(self._ema_decay, self.step_count, self._ema_warmup),
+                       skip=self.fault_slot, norm_state=self.last_grad_norm if self._max_grad_norm > 0 else None)
         torch.autograd.graph.increment_version(self._params_list)     # written through raw pointers: bump `_version` like torch would
         if fixed_lag is not None:
             self._watch_fixed_lag(before, int(fixed_lag))
@@ -555,8 +638,13 @@ class TrainStep:
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": wd if wd > 0 else 0, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "decoupled_weight_decay": wd > 0, "params": list(range(len(names)))}
-        return {"state": state, "param_groups": [group], "param_names": names, "grad_clip": self.grad_clip,
-                "max_grad_norm": self._max_grad_norm}
+        sd = {"state": state, "param_groups": [group], "param_names": names, "grad_clip": self.grad_clip,
+              "max_grad_norm": self._max_grad_norm}
+        if getattr(f, "ema", None) is not None:      # the averaged weights, one tensor per parameter in `param_names` order
+            src = f.params if self._averaged else f.ema
+            sd["ema"] = ema_entry(self._ema_decay, self._ema_warmup,
+                                  [src[f.slices[n][0]:f.slices[n][0] + f.slices[n][1]].view(f.slices[n][2]).clone() for n in names])
+        return sd
 
     def load_optimizer_state_dict(self, sd):
         f, trainable = self.flat, self._trainable()
@@ -568,6 +656,15 @@ class TrainStep:
         self.weight_decay = group_weight_decay(group)
         if "max_grad_norm" in sd:
             self.max_grad_norm = 0.0 if sd["max_grad_norm"] is None else sd["max_grad_norm"]     # (None: FusedClampAdam's "off")
+        if "ema" in sd:                              # (absent: the averaging state stays what it is)
+            if self._averaged:
+                raise RuntimeError(AVERAGED_NOTE % "load_optimizer_state_dict() with averaged weights")
+            decay, warmup, tensors = check_ema_entry(sd["ema"], [f.slices[name][2] for name, _ in trainable])
+            self._start_ema()
+            for t, (name, _) in zip(tensors, trainable):
+                o, n, _ = f.slices[name]
+                f.ema[o:o + n].copy_(t.reshape(-1))
+            self._ema_decay, self._ema_warmup = decay, warmup
         steps = set()
         f.m.zero_()
         f.v.zero_()

@@ -6,12 +6,14 @@
   norm_scales  the same with a max_norm below the norm: every gradient is multiplied by the coefficient
   norm_decay   norm_scales + weight_decay 0.01 with six exempt ranges (the 1-D parameters)
   decay        sat_adamw_step alone, weight_decay 0.01, no norm pass
+  ema          `off` + sat_ema_update behind it (decay 0.999, the same fault word): what `optimizer_step` launches with ema_decay set
   parent_off   (--parent-lib) sat_clamp_adam_step_guarded of ANOTHER build of the library, the parent commit's: `off` makes the
                same call into the same code, so the two must lie inside each other's spread
 
 All with clip 0.1 and the fault word (zero) as in the trainer.  The sides ALTERNATE region by region (REGIONS regions of STEPS steps
 each); a region is timed with HIP events around its launches, the median region and the lowest and highest are reported per side in
-microseconds per step, with the bytes a step must move (28 B / parameter, + 4 B for the norm pass) over the median.  The kernels run
+microseconds per step, with the bytes a step must move (28 B / parameter, + 4 B for the norm pass, + 12 B for the average) over
+the median.  The kernels run
 on their own output again and again: a fixed Adam step count, values stay finite, the work does not depend on them (in `norm_scales`
 the written-back gradient settles at norm = max_norm, where the coefficient max_norm / (max_norm + 1e-6) still is not 1).
 One JSON object on stdout."""
@@ -108,7 +110,16 @@ def main():
                                            norm_out.data_ptr() if norm else None, skip.data_ptr(), st))
             return fn
 
-        fns = {"off": guarded(lib, state()), "norm": adamw(state(), float("inf"), 0.0), "norm_scales": adamw(state(), 1.0, 0.0),
+        def with_ema(bufs):
+            update, avg = guarded(lib, bufs), bufs[0].clone()
+            ptrs = (avg.data_ptr(), bufs[0].data_ptr())
+
+            def fn():
+                update()
+                L.check(lib.sat_ema_update(*ptrs, n, 0.999, skip.data_ptr(), None, st))
+            return fn
+
+        fns = {"off": guarded(lib, state()), "ema": with_ema(state()), "norm": adamw(state(), float("inf"), 0.0), "norm_scales": adamw(state(), 1.0, 0.0),
                "norm_decay": adamw(state(), 1.0, 0.01), "decay": adamw(state(), None, 0.01)}
         if parent is not None:
             fns["parent_off"] = guarded(parent, state())
@@ -116,7 +127,7 @@ def main():
         torch.cuda.synchronize()
         assert norm_out[1].item() == 0.0, "a benchmark buffer went non-finite"
         for k, v in r.items():
-            nbytes = n * (28 + (4 if k.startswith("norm") else 0))
+            nbytes = n * (28 + (4 if k.startswith("norm") else 0) + (12 if k == "ema" else 0))
             v["bytes_per_step"] = nbytes
             v["TB_per_s_at_median"] = round(nbytes / (v["median_us"] * 1e-6) / 1e12, 3)
         res["sizes"][name] = {"n": n, "exempt_ranges": len(ranges), "partial_pairs": P, "settings": r}
