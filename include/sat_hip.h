@@ -1269,6 +1269,25 @@ int sat_ema_update(float* ema, const float* p, int64_t n, float decay, const flo
                    sat_stream_t stream);
 int sat_swap_f32(float* a, float* b, int64_t n, sat_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Gradient accumulation (added within ABI 18; sat_optim.hip): one finished backward folded into a second flat buffer, so that K
+ * micro-batches (or a cross-entropy and a self-critical backward) make ONE update.  acc and g hold n + 2 floats each in the layout
+ * of the flat gradient buffer: n gradients, the loss slot, the step's fault word.
+ *   elements i <= n (gradients and the loss slot):
+ *     first != 0: acc[i] = weight * g[i]              (one rounding; the old acc[i] is never read: stale NaN cannot leak)
+ *     first == 0: acc[i] = fma(weight, g[i], acc[i])  (one rounding)
+ *   element n + 1 (the fault word): acc = ((first ? 0 : acc != 0) || g != 0) ? 1.0f : 0.0f -- a micro-batch whose fault word is
+ *     set poisons the whole accumulated update, which sat_clamp_adam_step_guarded / sat_adamw_step / sat_ema_update then drop
+ *     when handed acc + n + 1 as their skip word.
+ *   Contracts: weight == 1 gives exactly the f32 sum in call order; first with weight == 1 gives exactly a copy; the result is a
+ *   function of (acc, g, weight, first) only -- the same arithmetic in the 16-byte loop and in the tail, no atomics, nothing
+ *   depends on the grid: the same bits in every launch shape.  Inf / NaN take no special path: they go through the fma, and
+ *   sat_adamw_step's count drops the update when a norm is set.
+ *   SAT_ERR_ARG before any launch: NULL acc / g, n < 0, acc or g not 16-byte aligned, weight not finite, overlapping ranges.
+ *   256 threads, 16-byte accesses, a grid that depends on n only (at most 768 workgroups), no LDS.  12 B per parameter (8 with
+ *   first). */
+int sat_grad_accumulate(float* acc, const float* g, int64_t n, float weight, int first, sat_stream_t stream);
+
 /* column sums: out[c] = sum_r x[r*ld + c]  (bias gradients) */
 int sat_colsum_f32(const float* x, int64_t ld, int rows, int cols, float* out, sat_stream_t stream);
 /* f32 -> bf16 / bf16 -> f32 casts (weight shadow copies) */

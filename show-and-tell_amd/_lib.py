@@ -264,6 +264,7 @@ SIGNATURES = {
     "sat_adamw_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f, C.POINTER(_i64), _i, _f, _vp, _i, _vp, _vp, _vp]),
     "sat_ema_update": (_i, [_vp, _vp, _i64, _f, _vp, _vp, _vp]),
     "sat_swap_f32": (_i, [_vp, _vp, _i64, _vp]),
+    "sat_grad_accumulate": (_i, [_vp, _vp, _i64, _f, _i, _vp]),
     "sat_colsum_f32": (_i, [_vp, _i64, _i, _i, _vp, _vp]),
     "sat_cast_f32_bf16": (_i, [_vp, _vp, _i64, _vp]),
     "sat_cast_bf16_f32": (_i, [_vp, _vp, _i64, _vp]),
@@ -293,7 +294,8 @@ ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_at
                     "sat_consensus_ws_bytes", "sat_consensus_rerank", "sat_scst_weights_group", "sat_group_sum_rows",
                     "sat_sample_filtered_ex", "sat_sample_decode_ex_ws_bytes", "sat_sample_decode_ex", "sat_vocab_logp_ws_bytes",
                     "sat_vocab_logp_ws_bytes_rows", "sat_vocab_logp", "sat_caption_logp_sum", "sat_score_captions_ws_bytes",
-                    "sat_score_captions", "sat_ce_rows_ul", "sat_vocab_ce_fwd_bf16_ul", "sat_ema_update", "sat_swap_f32")
+                    "sat_score_captions", "sat_ce_rows_ul", "sat_vocab_ce_fwd_bf16_ul", "sat_ema_update", "sat_swap_f32",
+                    "sat_grad_accumulate")
 
 _lib = None
 

@@ -16,6 +16,9 @@
 //                       (12 B/param: read p and ema, write ema).  It reads the two things that say "the update was dropped" -- the
 //                       skip word, and the {norm, nonfinite} pair adamw_kernel wrote -- and then leaves ema alone as well.
 //   swap_kernel       : a <-> b element by element (the averaged weights in and out of the model, no third buffer).
+//   grad_accumulate_kernel : acc (+)= weight * g over the n gradients and the loss slot of a flat gradient buffer, and the OR of the
+//                       two fault words behind them (12 B/param; 8 on the first fold, which does not read acc): micro-batches are
+//                       folded into one update.  One fma per element, the same in the 16-byte loop and in the tail.
 #include "sat_internal.h"
 
 #include <cmath>
@@ -196,6 +199,30 @@ __global__ __launch_bounds__(OPT_BLOCK) void swap_kernel(float* __restrict__ a, 
     }
 }
 
+// One rounding per element: the product on the first fold (acc is NOT read: stale bits, NaN included, cannot leak), one fma after it.
+__device__ __forceinline__ float acc_one(float a, float g, float w, bool first) { return first ? __fmul_rn(w, g) : __fmaf_rn(w, g, a); }
+
+// Elements 0 .. n (the n gradients and the loss slot) take the rule above; element n + 1 is the fault word: it stays set once any
+// fold has brought a non-zero one, and the update kernels drop on it.  The 16-byte chunks end at or in front of n + 1, the tail
+// (at most 3 elements) and the fault word belong to workgroup 0.  The host has checked that the two ranges do not overlap.
+__global__ __launch_bounds__(OPT_BLOCK) void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, long n,
+                                                                    float w, int first) {
+    const long n1 = n + 1;
+    const long n4 = n1 >> 2;
+    for (long i = (long)blockIdx.x * OPT_BLOCK + threadIdx.x; i < n4; i += (long)gridDim.x * OPT_BLOCK) {
+        const f32x4 gg = ((const f32x4*)g)[i];
+        f32x4 aa = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (!first) aa = ((f32x4*)acc)[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) aa[k] = acc_one(aa[k], gg[k], w, first != 0);
+        ((f32x4*)acc)[i] = aa;
+    }
+    if (blockIdx.x != 0) return;
+    const long i = (n4 << 2) + threadIdx.x;
+    if (i < n1) acc[i] = acc_one(first ? 0.0f : acc[i], g[i], w, first != 0);
+    if (threadIdx.x == OPT_BLOCK - 1) acc[n1] = ((!first && acc[n1] != 0.0f) || g[n1] != 0.0f) ? 1.0f : 0.0f;
+}
+
 }  // namespace
 
 extern "C" int sat_grad_sumsq_partials(int64_t n) { return n < 1 ? 0 : sumsq_grid((long)n); }
@@ -266,6 +293,19 @@ extern "C" int sat_swap_f32(float* a, float* b, int64_t n, sat_stream_t stream) 
     const uintptr_t hi = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)b : (uintptr_t)a;
     if ((hi - lo) / sizeof(float) < (uintptr_t)n) return SAT_ERR_ARG;                   // the ranges overlap
     hipLaunchKernelGGL(swap_kernel, dim3(sumsq_grid((long)n)), dim3(OPT_BLOCK), 0, (hipStream_t)stream, a, b, (long)n);
+    SAT_LAUNCH_CHECK();
+    return SAT_OK;
+}
+
+extern "C" int sat_grad_accumulate(float* acc, const float* g, int64_t n, float weight, int first, sat_stream_t stream) {
+    if (!acc || !g || n < 0) return SAT_ERR_ARG;
+    if ((((uintptr_t)acc | (uintptr_t)g) & 15) != 0) return SAT_ERR_ARG;
+    if (!(fabsf(weight) <= 3.402823466e+38f)) return SAT_ERR_ARG;                      // (NaN fails the comparison)
+    const uintptr_t lo = (uintptr_t)acc < (uintptr_t)g ? (uintptr_t)acc : (uintptr_t)g;
+    const uintptr_t hi = (uintptr_t)acc < (uintptr_t)g ? (uintptr_t)g : (uintptr_t)acc;
+    if ((hi - lo) / sizeof(float) < (uintptr_t)n + 2) return SAT_ERR_ARG;               // the ranges (n + 2 floats each) overlap
+    hipLaunchKernelGGL(grad_accumulate_kernel, dim3(sumsq_grid((long)n + 1)), dim3(OPT_BLOCK), 0, (hipStream_t)stream, acc, g,
+                       (long)n, weight, first);
     SAT_LAUNCH_CHECK();
     return SAT_OK;
 }

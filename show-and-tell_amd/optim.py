@@ -92,6 +92,18 @@ def ema_update(lib, ema, params, n, decay, skip=None, norm_state=None):
     L.check(lib.sat_ema_update(L.ptr(ema), L.ptr(params), n, decay, L.ptr(skip), L.ptr(norm_state), L.stream()), "sat_ema_update")
 
 
+def check_accumulate_weight(value, what="weight"):
+    """a finite float: the factor of one folded backward"""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value):
+        raise ValueError("%s must be a finite number (got %r)" % (what, value))
+    return float(value)
+
+
+def grad_accumulate(lib, acc, grads, n, weight, first):
+    """one sat_grad_accumulate launch on the current stream (addresses or tensors of n + 2 floats: gradients, loss slot, fault word)"""
+    L.check(lib.sat_grad_accumulate(L.ptr(acc), L.ptr(grads), n, weight, 1 if first else 0, L.stream()), "sat_grad_accumulate")
+
+
 def ema_entry(decay, warmup, tensors):
     """the "ema" entry of an optimizer state dict"""
     return {"decay": decay, "warmup": warmup, "params": tensors}

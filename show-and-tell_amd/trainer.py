@@ -19,8 +19,9 @@ from . import _lib as L
 from .criterion import MAX_UL_STEPS, _check_smoothing, _check_unlikelihood
 from .decoder import LSTMWorkspaces, VocabCE, decoder_backward, decoder_forward, rollout_forward
 from .models import ShowAndTell, draw_ss_seed, fc_bn1d_backward, fc_bn1d_forward
-from .optim import (AVERAGED_NOTE, check_ema_decay, check_ema_entry, check_ema_warmup, check_max_norm, check_weight_decay,
-                    ema_decay_at, ema_entry, ema_update, exempt_array, group_weight_decay, merge_ranges, swapped_in)
+from .optim import (AVERAGED_NOTE, check_accumulate_weight, check_ema_decay, check_ema_entry, check_ema_warmup, check_max_norm,
+                    check_weight_decay, ema_decay_at, ema_entry, ema_update, exempt_array, grad_accumulate, group_weight_decay,
+                    merge_ranges, swapped_in)
 from .pack import PackInfo
 from .scst import SelfCritical, ce_rows_weighted, check_group, group_sum_rows, scst_weights, scst_weights_group
 from .watch import ResidencyWatch, StatusRing
@@ -81,6 +82,7 @@ class FlatParams:
         self.m = torch.zeros(off, device=dev)
         self.v = torch.zeros(off, device=dev)
         self.ema = None          # the averaged weights, a twin of `params`: made when TrainStep.ema_decay first becomes non-zero
+        self.acc = None          # the accumulated gradient, a twin of `grads` (4 B/param): made by the first TrainStep.accumulate()
         for g in groups:
             for name, p in g:
                 o, n, shape = self.slices[name]
@@ -277,6 +279,46 @@ class TrainStep:
             o, n, shape = self.flat.slices[name]
             sd[name] = src[o:o + n].view(shape).clone()
         return sd
+
+    # -- gradient accumulation: K backwards, ONE update ------------------------------------------------------------------------
+    # `flat.acc` (None until the first `accumulate()`, then a twin of `flat.grads`: the n gradients, the loss slot, the fault word;
+    # 4 B per trainable parameter).  `accumulate(weight)` folds the backward that `forward_backward` / `scst_forward_backward` has
+    # just left in `flat.grads` into it with one sat_grad_accumulate launch on the step's stream: acc = weight * g on the first fold
+    # after an update (or after `discard_accumulated()`), acc = fma(weight, g, acc) on the later ones, and the fault words OR-ed.
+    # `optimizer_step` with `accumulated > 0` then runs its usual sequence on `flat.acc` and its fault word and closes the
+    # accumulation: step_count, the bias correction, the EMA and `last_grad_norm` advance once per UPDATE, and a fault or a
+    # non-finite value in any micro-batch drops the one update.  With `accumulated == 0` it makes exactly the calls it makes without.
+    # BatchNorm (the head's BatchNorm1d, the frozen stack's train-mode statistics) sees each micro-batch on its own, as in torch
+    # gradient accumulation: accumulated micro-batches equal the big batch only where no BatchNorm lies in the path (cached 2-D
+    # features).  Scheduled sampling and dropout draw per call.
+    _accumulated = 0
+
+    @property
+    def accumulated(self):
+        """micro-batches folded into `flat.acc` since the last update (or `discard_accumulated()`)"""
+        return self._accumulated
+
+    def accumulate(self, weight=1.0):
+        """Fold the finished backward in `flat.grads` (gradients, loss slot, fault word) into `flat.acc`, times `weight` (a finite
+        float, ValueError otherwise).  Nothing is read on the host.  Returns the accumulated loss slot (1-element device view)."""
+        if self._averaged:
+            raise RuntimeError(AVERAGED_NOTE % "accumulate()")
+        weight = check_accumulate_weight(weight)
+        f = self.flat
+        if getattr(f, "acc", None) is None:
+            f.acc = torch.zeros_like(f.grads)
+        grad_accumulate(self.lib, f.acc, f.grads, f.n, weight, first=self._accumulated == 0)
+        self._accumulated += 1
+        return f.acc[f.loss_slot:f.loss_slot + 1]
+
+    def discard_accumulated(self):
+        """close an open accumulation without an update: the next `accumulate()` starts afresh and does not read what was folded"""
+        self._accumulated = 0
+
+    @property
+    def acc_grad(self):
+        """`flat.acc` (None before the first fold): what a data-parallel step all-reduces bucket by bucket"""
+        return getattr(self.flat, "acc", None)
 
     # -- encoder look-ahead ---------------------------------------------------------------------------
     def prefetch_encoder(self, images):
@@ -543,7 +585,7 @@ class TrainStep:
         self.step_count = step_before
         self._fault_sticky.zero_()
 
-    def _watch_fixed_lag(self, before, lag):
+    def _watch_fixed_lag(self, before, lag, fault_slot=None):
         """The host half of the fault path for DATA-PARALLEL steps.  The device half is rank-consistent by construction (the flag
         rides the all-reduce); the host half must be too: with the non-blocking poll of the single-rank path, ranks could see
         the flag one step apart, the early one would clear its sticky word, and the late one's next update -- no longer dropped --
@@ -552,7 +594,7 @@ class TrainStep:
         point in the loop, same decision on every rank.  While the faulted rank's sticky word is set, every rank's reduced flag is
         non-zero, so the steps between the fault and the raise are dropped everywhere; the raise rolls the step count back to the
         faulted step's on every rank and clears the sticky word."""
-        self._lag_ring.push(self.fault_slot.view(torch.int32), before)
+        self._lag_ring.push((self.fault_slot if fault_slot is None else fault_slot).view(torch.int32), before)
         self._retire_fixed_lag(lag)
 
     def _retire_fixed_lag(self, keep):
@@ -577,31 +619,37 @@ class TrainStep:
         before = self.step_count
         self.step_count += 1
         f = self.flat
+        # an open accumulation: the same sequence on `flat.acc` and ITS fault word (the OR over the micro-batches), closed here
+        grads, fault_slot = f.grads, self.fault_slot
+        if self._accumulated > 0:
+            grads, fault_slot = f.acc, f.acc[f.loss_slot + 1:f.loss_slot + 2]
+            self._accumulated = 0
         if self._ema_decay > 0:
             self._start_ema()                # (only an engine that had no flat buffer when the attribute was set copies here)
         if self._max_grad_norm == 0 and self._weight_decay == 0:
-            L.check(self.lib.sat_clamp_adam_step_guarded(L.ptr(f.params), L.ptr(f.grads), L.ptr(f.m), L.ptr(f.v), f.n,
+            L.check(self.lib.sat_clamp_adam_step_guarded(L.ptr(f.params), L.ptr(grads), L.ptr(f.m), L.ptr(f.v), f.n,
                                                          float(self.lr if lr is None else lr), self.betas[0], self.betas[1],
-                                                         self.eps, float(self.grad_clip), self.step_count, L.ptr(self.fault_slot),
+                                                         self.eps, float(self.grad_clip), self.step_count, L.ptr(fault_slot),
                                                          L.stream()), "sat_clamp_adam_step_guarded")
         else:
-            self._adamw_step(float(self.lr if lr is None else lr))
+            self._adamw_step(float(self.lr if lr is None else lr), grads, fault_slot)
         if self._ema_decay > 0:
             # behind the update on its stream, behind the same two words: the fault slot (neither update kernel writes it: it lies
             # past the n elements they cover) and, with a norm, the {norm, non-finite} pair sat_adamw_step has just written
             ema_update(self.lib, f.ema, f.params, f.n, ema_decay_at(self._ema_decay, self.step_count, self._ema_warmup),
-                       skip=self.fault_slot, norm_state=self.last_grad_norm if self._max_grad_norm > 0 else None)
+                       skip=fault_slot, norm_state=self.last_grad_norm if self._max_grad_norm > 0 else None)
         torch.autograd.graph.increment_version(self._params_list)     # written through raw pointers: bump `_version` like torch would
         if fixed_lag is not None:
-            self._watch_fixed_lag(before, int(fixed_lag))
+            self._watch_fixed_lag(before, int(fixed_lag), fault_slot)
             return
-        ResidencyWatch.get(f.params.device).submit(self.fault_slot.view(torch.int32), "a persistent LSTM recurrence of a training step",
+        ResidencyWatch.get(f.params.device).submit(fault_slot.view(torch.int32), "a persistent LSTM recurrence of a training step",
                                                    lambda: self._on_fault(before), note=self.FAULT_NOTE)
 
-    def _adamw_step(self, lr):
+    def _adamw_step(self, lr, grads, fault_slot):
         """the update with a global norm and / or weight decay: the sum of squares over the n parameter gradients -- the loss and
         fault slots behind them are no gradients and stay out --, then sat_adamw_step behind the same fault word; it drops the
-        update by itself when the gradient holds an Inf or NaN (see `last_grad_norm`)"""
+        update by itself when the gradient holds an Inf or NaN (see `last_grad_norm`).  grads, fault_slot: `flat.grads` and the
+        step's word, or `flat.acc` and its word"""
         f, lib, st = self.flat, self.lib, L.stream()
         if self._exempt is None:
             self._exempt = self._ranges_of(self._no_decay)
@@ -611,11 +659,11 @@ class TrainStep:
                 self._norm_ws = torch.empty(lib.sat_grad_sumsq_ws_bytes(f.n) // 8, dtype=torch.float64, device=f.params.device)
                 self.last_grad_norm = torch.zeros(2, dtype=torch.float64, device=f.params.device)
             partials, count, norm_out = L.ptr(self._norm_ws), lib.sat_grad_sumsq_partials(f.n), L.ptr(self.last_grad_norm)
-            L.check(lib.sat_grad_sumsq(L.ptr(f.grads), f.n, float(self.grad_clip), partials, 0, count, st), "sat_grad_sumsq")
+            L.check(lib.sat_grad_sumsq(L.ptr(grads), f.n, float(self.grad_clip), partials, 0, count, st), "sat_grad_sumsq")
         ex, nex = exempt_array(self._exempt) if self._weight_decay > 0 else (None, 0)
-        L.check(lib.sat_adamw_step(L.ptr(f.params), L.ptr(f.grads), L.ptr(f.m), L.ptr(f.v), f.n, lr, self.betas[0], self.betas[1],
+        L.check(lib.sat_adamw_step(L.ptr(f.params), L.ptr(grads), L.ptr(f.m), L.ptr(f.v), f.n, lr, self.betas[0], self.betas[1],
                                    self.eps, float(self.grad_clip), self.step_count, self._weight_decay, ex, nex,
-                                   self._max_grad_norm, partials, count, norm_out, L.ptr(self.fault_slot), st), "sat_adamw_step")
+                                   self._max_grad_norm, partials, count, norm_out, L.ptr(fault_slot), st), "sat_adamw_step")
 
     # -- optimizer checkpoint interchange (the reference's load_optimizer is an empty stub, ------
     #    train.py:60-64, and only model.state_dict() is saved, train.py:191-193) ---------------------------
@@ -700,6 +748,73 @@ class TrainStep:
         self.optimizer_step(lr)
         return loss
 
+    def step_accumulated(self, batches, lr=None, next_images=None):
+        """One update from K micro-batches: `batches` is a sequence of (images, captions, lengths).  Every micro-batch runs
+        `forward_backward` with inv_denom = 1 / (target tokens of ALL micro-batches) and is folded with weight 1, so the update
+        is that of the mean CE over the union -- the rule `DataParallelStep` applies across ranks -- with gradients summed in f32
+        in call order.  Returns the accumulated loss as a 1-element device tensor (no host sync).  Look-ahead: micro-batch k
+        hands micro-batch k + 1's images on as `next_images`, the last one the caller's.  `last_nll` / `last_ul` are the sums of
+        the micro-batches' values in fresh 1-element tensors.  BatchNorm sees each micro-batch on its own (see `accumulate`)."""
+        batches = list(batches)
+        if not batches:
+            raise ValueError("step_accumulated needs at least one micro-batch")
+        if self._accumulated:
+            raise RuntimeError("step_accumulated: an accumulation is open (%d folded): optimizer_step() or discard_accumulated() "
+                               "first" % self._accumulated)
+        inv_denom = 1.0 / sum(int(l) - 1 for _, _, lengths in batches for l in lengths)
+        nll = ul = None
+        try:
+            for k, batch in enumerate(batches):
+                nxt = batches[k + 1][0] if k + 1 < len(batches) else next_images
+                self.forward_backward(tuple(batch), inv_denom, next_images=nxt)
+                self.accumulate()
+                nll = self.last_nll.clone() if nll is None else nll + self.last_nll
+                if self.last_ul is not None:
+                    ul = self.last_ul.clone() if ul is None else ul + self.last_ul
+        except BaseException:
+            self.discard_accumulated()
+            raise
+        self.last_nll, self.last_ul = nll, ul
+        loss = self.flat.acc[self.flat.loss_slot:self.flat.loss_slot + 1].clone()
+        self.optimizer_step(lr)
+        return loss
+
+    def mixed_step(self, images, captions, lengths, image_index, scorer, rl_weight, lr=None, next_images=None, **scst):
+        """One update of (1 - rl_weight) * XE + rl_weight * SCST (Paulus et al. 2017): a teacher-forced `forward_backward` folded
+        with weight 1 - rl_weight, a `scst_forward_backward` (keywords end_id, steps, num_samples, baseline in `scst`) folded with
+        weight rl_weight, one `optimizer_step`: one bias-correction step and one EMA update, where alternating `step` and
+        `scst_step` takes two.  rl_weight lies in [0, 1] (ValueError); at exactly 0 or 1 the call IS `step` / `scst_step`: no
+        accumulate launch, the same bits.  Returns the mixed loss (1-element device tensor, no host sync); `last_scst` is what
+        `scst_step` leaves, `last_nll` / `last_ul` what the XE half leaves (unweighted).  BOTH halves run the encoder head on
+        `images`: the frozen stack (unless cached [B, E] features are handed in) runs twice and the BatchNorm running statistics
+        are updated once by each half.  `next_images` goes to the second half."""
+        if isinstance(rl_weight, bool) or not isinstance(rl_weight, (int, float)) or not 0.0 <= rl_weight <= 1.0:
+            raise ValueError("rl_weight must be a number in [0, 1] (got %r)" % (rl_weight,))
+        unknown = sorted(set(scst) - {"end_id", "steps", "num_samples", "baseline"})
+        if unknown:
+            raise TypeError("mixed_step: unexpected keywords %s" % unknown)
+        if rl_weight == 0:
+            return self.step(images, captions, lengths, lr, next_images)
+        if rl_weight == 1:
+            return self.scst_step(images, image_index, scorer, lr, next_images, **scst)
+        if self._accumulated:
+            raise RuntimeError("mixed_step: an accumulation is open (%d folded): optimizer_step() or discard_accumulated() first"
+                               % self._accumulated)
+        try:
+            n_tokens = sum(int(l) - 1 for l in lengths)
+            self.forward_backward((images, captions, lengths), 1.0 / n_tokens)
+            self.accumulate(1.0 - float(rl_weight))
+            nll, ul = self.last_nll.clone(), None if self.last_ul is None else self.last_ul.clone()
+            self.scst_forward_backward(images, image_index, scorer, next_images=next_images, **scst)
+            self.accumulate(float(rl_weight))
+        except BaseException:
+            self.discard_accumulated()
+            raise
+        self.last_nll, self.last_ul = nll, ul
+        loss = self.flat.acc[self.flat.loss_slot:self.flat.loss_slot + 1].clone()
+        self.optimizer_step(lr)
+        return loss
+
 
 def dp_shard(images, captions, lengths, rank, world):
     """Interleaved shard of a length-sorted global batch: rank r takes rows r, r+world, ...  Every shard stays
@@ -742,7 +857,10 @@ class DataParallelStep:
         the remaining backward kernels; the loss rides in the last bucket;
       * clamp + Adam run AFTER the reduction (train.py:144-146 order), identically on every rank;
       * BatchNorm uses per-rank batch statistics (what nn.DataParallel replicas do as well).
-    `engine` needs: .flat_grad, .buckets, .forward_backward(batch, inv_denom, on_bucket_ready), .optimizer_step(lr).
+    `engine` needs: .flat_grad, .buckets, .forward_backward(batch, inv_denom, on_bucket_ready), .optimizer_step(lr); for
+    `step_accumulated` also .accumulate(weight) (folds the finished backward in .flat_grad into .acc_grad), .acc_grad (the
+    accumulated twin of .flat_grad, same buckets) and .accumulated (folds since the last update), and an .optimizer_step that
+    updates from .acc_grad while an accumulation is open.
     """
 
     def __init__(self, engine, process_group=None):
@@ -791,6 +909,42 @@ class DataParallelStep:
         loss = loss.clone()          # the slot in the flat gradient buffer is overwritten by the next step
         if self.world > 1 and hasattr(eng, "DP_FAULT_LAG"):
             eng.optimizer_step(lr, fixed_lag=eng.DP_FAULT_LAG)     # rank-consistent fault handling (TrainStep._watch_fixed_lag)
+        else:
+            eng.optimizer_step(lr)
+        return loss
+
+    def step_accumulated(self, batches, global_tokens, lr=None, next_images=None):
+        """One update from K micro-batches per rank with ONE gradient exchange (torch DDP's `no_sync` for the first K - 1):
+        every micro-batch runs `forward_backward` with 1 / global_tokens -- the target tokens of all micro-batches on ALL ranks --
+        without bucket callbacks and is folded into `engine.acc_grad`; after the last fold each bucket of `acc_grad` is
+        all-reduced once (async, waited for before the update; loss and fault word ride in the last bucket) and the update runs
+        on it.  The exchange starts behind the last fold: it is not overlapped with the last backward.  Returns the global loss."""
+        eng, dist = self.engine, self.dist
+        batches = list(batches)
+        if not batches:
+            raise ValueError("step_accumulated needs at least one micro-batch")
+        if eng.accumulated:
+            raise RuntimeError("step_accumulated: an accumulation is open on the engine (%d folded)" % eng.accumulated)
+        inv_denom = 1.0 / float(global_tokens)
+        lookahead = hasattr(eng, "prefetch_encoder")       # (an engine without one is not handed the keyword, as in `step`)
+        for k, batch in enumerate(batches):
+            nxt = next_images if k + 1 == len(batches) else (batches[k + 1][0] if lookahead else None)
+            if nxt is not None:
+                eng.forward_backward(batch, inv_denom, next_images=nxt)
+            else:
+                eng.forward_backward(batch, inv_denom)
+            eng.accumulate(1.0)
+        acc = eng.acc_grad
+        works = []
+        if self.world > 1:
+            for s_, e_ in eng.buckets:
+                works.append(dist.all_reduce(acc[s_:e_], op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+        for w in works:
+            w.wait()                 # every bucket is reduced before clamp + Adam read the accumulated gradients
+        end = eng.buckets[-1][1]     # the 4 trailing floats of the last bucket: loss, fault word, padding
+        loss = acc[end - 4:end - 3].clone()
+        if self.world > 1 and hasattr(eng, "DP_FAULT_LAG"):
+            eng.optimizer_step(lr, fixed_lag=eng.DP_FAULT_LAG)
         else:
             eng.optimizer_step(lr)
         return loss
