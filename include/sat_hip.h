@@ -317,6 +317,12 @@ int64_t sat_lstm_fwd_ws_bytes(int B, int H);
  * INVALID: the caller must copy the word out behind the call (hipMemcpyAsync to pinned memory) and treat non-zero as an
  * error -- `show-and-tell_amd.watch.ResidencyWatch` raises RuntimeError and switches the process to per-step launches. */
 int64_t sat_lstm_fwd_status_offset(int B, int H);
+/* Which form of the recurrence a call would run on the current device -- what sat_lstm_fwd / sat_lstm_bwd themselves decide
+ * (SAT_LSTM_PERSIST, SAT_LSTM_PERSIST_BWD and sat_lstm_persist_enable included), so a test can prove the form it means to check.
+ * fwd: rows per group of the persistent forward given a workspace of sat_lstm_fwd_ws_bytes: 8 or 16, 0 = one launch per step.
+ * bwd: 1 = the backward recurrence runs as one persistent launch given the full workspace, 0 = one launch per step. */
+int sat_lstm_fwd_plan(int B, int H, int T);
+int sat_lstm_bwd_plan(int B, int H, int T);
 /* process-wide switch of the persistent recurrence (default on); returns the previous setting.  Off: one launch per step. */
 int sat_lstm_persist_enable(int on);
 int64_t sat_lstm_bwd_ws_bytes(int B, int H);          /* minimum */

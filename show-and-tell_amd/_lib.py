@@ -135,6 +135,8 @@ SIGNATURES = {
                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "sat_lstm_fwd_ws_bytes": (_i64, [_i, _i]),
     "sat_lstm_fwd_status_offset": (_i64, [_i, _i]),
+    "sat_lstm_fwd_plan": (_i, [_i, _i, _i]),
+    "sat_lstm_bwd_plan": (_i, [_i, _i, _i]),
     "sat_lstm_persist_enable": (_i, [_i]),
     "sat_lstm_bwd_ws_bytes": (_i64, [_i, _i]),
     "sat_lstm_bwd_ws_bytes_full": (_i64, [_i, _i, _i, _i]),
@@ -295,7 +297,7 @@ ADDED_WITHIN_ABI = ("sat_conv_resolved_variant", "sat_image_augment_u8", "sat_at
                     "sat_sample_filtered_ex", "sat_sample_decode_ex_ws_bytes", "sat_sample_decode_ex", "sat_vocab_logp_ws_bytes",
                     "sat_vocab_logp_ws_bytes_rows", "sat_vocab_logp", "sat_caption_logp_sum", "sat_score_captions_ws_bytes",
                     "sat_score_captions", "sat_ce_rows_ul", "sat_vocab_ce_fwd_bf16_ul", "sat_ema_update", "sat_swap_f32",
-                    "sat_grad_accumulate")
+                    "sat_grad_accumulate", "sat_lstm_fwd_plan", "sat_lstm_bwd_plan")
 
 _lib = None
 

@@ -213,6 +213,21 @@ static int device_cu_count() {
     return n;
 }
 
+// The form of the recurrence, decided in ONE place each (lstm_fwd_impl / lstm_bwd_impl and the plan queries call these).
+// Forward: rows per group of the ONE persistent launch (W_hh in registers, per-group hidden-state exchange) when every workgroup
+// can be resident and the caller brought the exchange workspace (`ws_ok`); 0 = one launch per step
+static int lstm_fwd_rows(int B, int H, int T, bool ws_ok) {
+    static const int persist_env = getenv("SAT_LSTM_PERSIST") ? atoi(getenv("SAT_LSTM_PERSIST")) : 1;
+    return (persist_env && ws_ok) ? sat_lstm_persist_rows(B, H, T, device_cu_count()) : 0;
+}
+// Backward: ONE persistent launch when every workgroup can be resident and the caller brought the full workspace (`roomy`)
+static bool lstm_bwd_persistent(int B, int H, int T, bool roomy) {
+    static const int persist_bwd = getenv("SAT_LSTM_PERSIST_BWD") ? atoi(getenv("SAT_LSTM_PERSIST_BWD")) : 1;
+    return roomy && persist_bwd && sat_lstm_persist_bwd_ws_bytes(B, H) > 0 && sat_lstm_persist_ok(B, H, T, device_cu_count());
+}
+extern "C" int sat_lstm_fwd_plan(int B, int H, int T) { return (B < 1 || H < 1) ? 0 : lstm_fwd_rows(B, H, T, true); }
+extern "C" int sat_lstm_bwd_plan(int B, int H, int T) { return (B < 1 || H < 1) ? 0 : (lstm_bwd_persistent(B, H, T, true) ? 1 : 0); }
+
 static int lstm_fwd_impl(const float* X, const float* w_ih, const float* w_hh, const float* b_ih,
                          const float* b_hh, const int32_t* batch_sizes, int T, int In, int H, float* GA,
                          float* CS, float* HS, float* HP, float* c_state, void* workspace, int64_t ws_bytes,
@@ -235,10 +250,9 @@ static int lstm_fwd_impl(const float* X, const float* w_ih, const float* w_hh, c
         SAT_TRY(sat_gemm_f32(0, 0, X, In, w_ih, In, GA, 4L * H, b_ih, b_hh, (int)N, 4 * H, In, stream));
     hipError_t e = hipMemsetAsync(HP, 0, (size_t)B * H * sizeof(float), s);   // h_{-1} = 0 for the rows of step 0
     if (e != hipSuccess) return (int)e;
-    // the recurrence: ONE persistent launch (W_hh in registers, per-group hidden-state exchange) when every workgroup
-    // can be resident and the caller brought the exchange workspace; otherwise one launch per step
-    static const int persist_env = getenv("SAT_LSTM_PERSIST") ? atoi(getenv("SAT_LSTM_PERSIST")) : 1;
-    const int prow = (persist_env && workspace && ws_bytes >= sat_lstm_fwd_ws_bytes(B, H)) ? sat_lstm_persist_rows(B, H, T, device_cu_count()) : 0;
+    // the recurrence: ONE persistent launch when every workgroup can be resident and the caller brought the exchange workspace
+    // (lstm_fwd_rows); otherwise one launch per step
+    const int prow = lstm_fwd_rows(B, H, T, workspace && ws_bytes >= sat_lstm_fwd_ws_bytes(B, H));
     if (prow) return sat_lstm_persist_launch(GA, w_hh, CS, HS, HP, batch_sizes, T, H, prow, workspace, ws_bytes, s);
     // one launch per step: the status word the caller reads back (sat_lstm_fwd_status_offset) reports a clean run
     const int64_t soff = sat_lstm_fwd_status_offset(B, H);
@@ -376,12 +390,11 @@ static int lstm_bwd_impl(const float* dHS, const float* X, const float* w_ih, co
     if (e != hipSuccess) return (int)e;
     // the recurrence: ONE persistent launch (W_hh in registers, per-group exchange of the d(pre-activation) rows) when every
     // workgroup can be resident and the caller brought the full workspace (its last 64 bytes = the status word); otherwise one
-    // launch per step
-    static const int persist_bwd = getenv("SAT_LSTM_PERSIST_BWD") ? atoi(getenv("SAT_LSTM_PERSIST_BWD")) : 1;
+    // launch per step (lstm_bwd_persistent)
     bool recurrence_done = false;
     if (roomy) {
         unsigned* status = (unsigned*)(ws0 + sat_lstm_bwd_status_offset((int)N, B, In, H));
-        if (persist_bwd && sat_lstm_persist_bwd_ws_bytes(B, H) > 0 && sat_lstm_persist_ok(B, H, T, device_cu_count())) {
+        if (lstm_bwd_persistent(B, H, T, roomy)) {
             SAT_TRY(sat_lstm_persist_bwd_launch(dHS, GA, CS, w_hh, DG, batch_sizes, T, H, ws0, status, s));
             recurrence_done = true;
         } else {

@@ -239,3 +239,24 @@ def test_write_through_store_keeps_its_wait_states(tmp_path):
     assert stores, "the write-through store disappeared from the generated code"
     for i in stores:
         assert lines[i + 1].startswith("s_nop 1"), (lines[i], lines[i + 1])
+
+
+def test_lstm_plan_queries_are_exported_and_answer_without_a_launch():
+    """sat_lstm_fwd_plan / sat_lstm_bwd_plan (added within the ABI version): which form of the recurrence a call would run.  Outside
+    every persistent envelope -- H < 16, H % 16 != 0, an H with no instance, T > 64 -- the answer is 0 on any device and with none;
+    inside it the answer is one of the documented values, and sat_lstm_persist_enable(0) turns both to 0 (the queries ask what
+    sat_lstm_fwd / sat_lstm_bwd themselves ask)."""
+    lib = L.load()
+    assert {"sat_lstm_fwd_plan", "sat_lstm_bwd_plan"} <= set(L.ADDED_WITHIN_ABI) & set(header_symbols())
+    assert L.SIGNATURES["sat_lstm_fwd_plan"] == L.SIGNATURES["sat_lstm_bwd_plan"] == (C.c_int, [C.c_int] * 3)
+    for B, H, T in [(1, 4, 1), (3, 20, 5), (8, 32, 65), (8, 48, 4), (8, 32, 0), (0, 32, 4), (100000, 512, 4)]:
+        assert lib.sat_lstm_fwd_plan(B, H, T) == 0 and lib.sat_lstm_bwd_plan(B, H, T) == 0, (B, H, T)
+    inside = [(8, 32, 4), (17, 96, 6), (64, 512, 19), (64, 1024, 19)]
+    for B, H, T in inside:
+        assert lib.sat_lstm_fwd_plan(B, H, T) in (0, 8, 16) and lib.sat_lstm_bwd_plan(B, H, T) in (0, 1)
+    assert lib.sat_lstm_bwd_plan(64, 1024, 19) == 0                 # the backward has no 16-row form
+    prev = lib.sat_lstm_persist_enable(0)
+    try:
+        assert all(lib.sat_lstm_fwd_plan(*s) == 0 and lib.sat_lstm_bwd_plan(*s) == 0 for s in inside)
+    finally:
+        lib.sat_lstm_persist_enable(prev)
