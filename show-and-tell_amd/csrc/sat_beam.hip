@@ -731,16 +731,36 @@ void beam_row_launch(hipStream_t s, const float* logits, long ldl, const float* 
     }
 }
 
+// the rows a merge wave moves once it has selected (beam_move_rows): the embedding rows of the chosen tokens into x_next and the
+// (h, c) rows they extend, by parent.  All zero: the merge only selects; h_src NULL: embedding rows only
+struct BeamMove {
+    const float* embed;
+    int E;
+    float* x_next;
+    long ldx;
+    const float *h_src, *c_src;
+    int H;
+    float* h_dst;
+    long ldh;
+    float* c_dst;
+};
+
 // the merge launch of one step: the grouped kernel for groups of Kg < K slots, the plain one otherwise
 void beam_merge_launch(hipStream_t s, int B, const float* cand_val, const int* cand_idx, int K, int V, int Kg, float lambda,
-                       const int64_t* last, long end_id, int32_t* parent, int64_t* token, float* scores_out, const float* embed, int E,
-                       float* x_next, long ldx, const float* h_src, const float* c_src, int H, float* h_dst, long ldh, float* c_dst) {
+                       const int64_t* last, long end_id, int32_t* parent, int64_t* token, float* scores_out, const BeamMove& m) {
     if (Kg < K)
         hipLaunchKernelGGL(beam_merge_groups_kernel, dim3(B), dim3(256), 0, s, cand_val, cand_idx, K, V, Kg, lambda, last, end_id, parent,
-                           token, scores_out, embed, E, x_next, ldx, h_src, c_src, H, h_dst, ldh, c_dst);
+                           token, scores_out, m.embed, m.E, m.x_next, m.ldx, m.h_src, m.c_src, m.H, m.h_dst, m.ldh, m.c_dst);
     else
-        hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, s, cand_val, cand_idx, K, V, parent, token, scores_out, embed, E, x_next,
-                           ldx, h_src, c_src, H, h_dst, ldh, c_dst);
+        hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, s, cand_val, cand_idx, K, V, parent, token, scores_out, m.embed, m.E,
+                           m.x_next, m.ldx, m.h_src, m.c_src, m.H, m.h_dst, m.ldh, m.c_dst);
+}
+
+// the checks of the grouped entry points, before anything is enqueued (G == 1: lambda is not read)
+int beam_groups_check(int K, int G, float lambda) {
+    if (G < 1 || K <= 0 || K % G != 0) return SAT_ERR_ARG;
+    if (G > 1 && (!(lambda >= 0.0f) || lambda == INFINITY)) return SAT_ERR_ARG;
+    return SAT_OK;
 }
 
 }  // namespace
@@ -756,93 +776,65 @@ extern "C" int sat_kept_tokens(const int64_t* ids, int64_t stride, int B, int T,
 
 extern "C" int64_t sat_beam_step_ws_bytes(int B, int K) { return (int64_t)B * K * K * 8; }
 
-extern "C" int sat_beam_step(const float* logits, int64_t ldl, const float* scores_in, const int64_t* last_tokens,
-                             int64_t end_id, int B, int K, int V, int32_t* parent, int64_t* token, float* scores_out,
-                             void* workspace, int64_t ws_bytes, sat_stream_t stream) {
-    if (!logits || !scores_in || !parent || !token || !scores_out || !workspace) return SAT_ERR_ARG;
-    if (B <= 0 || K <= 0 || V <= 0 || ldl < V) return SAT_ERR_ARG;
-    if (K > KMAX || (long)K * V > INT_MAX - 1) return SAT_ERR_UNSUPPORTED;
-    if (ws_bytes < sat_beam_step_ws_bytes(B, K)) return SAT_ERR_WORKSPACE;
-    float* cand_val = (float*)workspace;                       // [B*K rows][K]
-    int* cand_idx = (int*)(cand_val + (long)B * K * K);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(beam_row_kernel<256>, dim3(B * K), dim3(256), 0, s, logits, (long)ldl, scores_in, last_tokens,
-                       (long)end_id, K, V, cand_val, cand_idx);
-    SAT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, s, cand_val, cand_idx, K, V, parent, token, scores_out,
-                       (const float*)nullptr, 0, (float*)nullptr, 0L, (const float*)nullptr, (const float*)nullptr, 0, (float*)nullptr, 0L,
-                       (float*)nullptr);
-    SAT_LAUNCH_CHECK();
-    return SAT_OK;
-}
-
 extern "C" int64_t sat_beam_step_ex_ws_bytes(int B, int K, int V, int T) {
     if (B <= 0 || K <= 0 || V <= 0 || T <= 0) return 0;
     return sat_beam_step_ws_bytes(B, K);                       // the prefix is walked from the records: no state in the workspace
 }
 
-extern "C" int sat_beam_step_ex(const float* logits, int64_t ldl, const float* scores_in, const int64_t* last_tokens,
-                                int64_t end_id, int B, int K, int V, const sat_beam_constraints* c, const int32_t* parents,
-                                const int64_t* tokens, int i, int T, int32_t* parent, int64_t* token, float* scores_out,
-                                void* workspace, int64_t ws_bytes, sat_stream_t stream) {
-    if (!logits || !scores_in || !parent || !token || !scores_out || !workspace) return SAT_ERR_ARG;
-    if (B <= 0 || K <= 0 || V <= 0 || ldl < V || T <= 0 || i < 0 || i >= T) return SAT_ERR_ARG;
-    bool active = false;
-    SAT_TRY(beam_constraints_check(c, end_id, &active));
-    if (active && i > 0 && (!parents || !tokens)) return SAT_ERR_ARG;
-    if (K > KMAX || (long)K * V > INT_MAX - 1) return SAT_ERR_UNSUPPORTED;
-    if (active && (T > kBanTMax || V > kBanVMax)) return SAT_ERR_UNSUPPORTED;
-    if (ws_bytes < sat_beam_step_ex_ws_bytes(B, K, V, T)) return SAT_ERR_WORKSPACE;
-    float* cand_val = (float*)workspace;                       // [B*K rows][K]
-    int* cand_idx = (int*)(cand_val + (long)B * K * K);
-    hipStream_t s = (hipStream_t)stream;
-    beam_row_launch(s, logits, (long)ldl, scores_in, last_tokens, (long)end_id, B * K, K, V, cand_val, cand_idx, active ? c : nullptr,
-                    parents, tokens, i);
-    SAT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, s, cand_val, cand_idx, K, V, parent, token, scores_out,
-                       (const float*)nullptr, 0, (float*)nullptr, 0L, (const float*)nullptr, (const float*)nullptr, 0, (float*)nullptr, 0L,
-                       (float*)nullptr);
-    SAT_LAUNCH_CHECK();
-    return SAT_OK;
-}
-
-// the checks of the two grouped entry points, before anything is enqueued (G == 1: lambda is not read)
-static int beam_groups_check(int K, int G, float lambda) {
-    if (G < 1 || K <= 0 || K % G != 0) return SAT_ERR_ARG;
-    if (G > 1 && (!(lambda >= 0.0f) || lambda == INFINITY)) return SAT_ERR_ARG;
-    return SAT_OK;
-}
-
 extern "C" int64_t sat_beam_step_groups_ws_bytes(int B, int K, int V, int T) { return sat_beam_step_ex_ws_bytes(B, K, V, T); }
 
-extern "C" int sat_beam_step_groups(const float* logits, int64_t ldl, const float* scores_in, const int64_t* last_tokens,
-                                    int64_t end_id, int B, int K, int V, const sat_beam_constraints* c, const int32_t* parents,
-                                    const int64_t* tokens, int i, int T, int num_groups, float diversity_penalty, int32_t* parent,
-                                    int64_t* token, float* scores_out, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+// ONE step for sat_beam_step, sat_beam_step_ex and sat_beam_step_groups: the row launch (the constrained kernel where step i of a
+// decode under c bans something) and the merge launch (the grouped kernel for G > 1), which here only selects
+static int beam_step_impl(const float* logits, int64_t ldl, const float* scores_in, const int64_t* last_tokens, int64_t end_id, int B,
+                          int K, int V, const sat_beam_constraints* c, const int32_t* parents, const int64_t* tokens, int i, int T, int G,
+                          float lambda, int32_t* parent, int64_t* token, float* scores_out, void* workspace, int64_t ws_bytes,
+                          sat_stream_t stream) {
     if (!logits || !scores_in || !parent || !token || !scores_out || !workspace) return SAT_ERR_ARG;
     if (B <= 0 || K <= 0 || V <= 0 || ldl < V || T <= 0 || i < 0 || i >= T) return SAT_ERR_ARG;
-    SAT_TRY(beam_groups_check(K, num_groups, diversity_penalty));
-    if (num_groups == 1)                                       // the launches of sat_beam_step_ex
-        return sat_beam_step_ex(logits, ldl, scores_in, last_tokens, end_id, B, K, V, c, parents, tokens, i, T, parent, token, scores_out,
-                                workspace, ws_bytes, stream);
-    if (end_id >= 0 && i > 0 && !last_tokens) return SAT_ERR_ARG;      // which rows are finished decides what is penalised and counted
+    SAT_TRY(beam_groups_check(K, G, lambda));
+    if (G > 1 && end_id >= 0 && i > 0 && !last_tokens) return SAT_ERR_ARG;      // which rows are finished decides what is penalised and counted
     bool active = false;
     SAT_TRY(beam_constraints_check(c, end_id, &active));
     if (active && i > 0 && (!parents || !tokens)) return SAT_ERR_ARG;
     if (K > KMAX || (long)K * V > INT_MAX - 1) return SAT_ERR_UNSUPPORTED;
     if (active && (T > kBanTMax || V > kBanVMax)) return SAT_ERR_UNSUPPORTED;
-    if (ws_bytes < sat_beam_step_groups_ws_bytes(B, K, V, T)) return SAT_ERR_WORKSPACE;
+    if (ws_bytes < sat_beam_step_ws_bytes(B, K)) return SAT_ERR_WORKSPACE;
     float* cand_val = (float*)workspace;                       // [B*K rows][K]: deep enough for every group (the lemma at the kernel)
     int* cand_idx = (int*)(cand_val + (long)B * K * K);
     hipStream_t s = (hipStream_t)stream;
     beam_row_launch(s, logits, (long)ldl, scores_in, last_tokens, (long)end_id, B * K, K, V, cand_val, cand_idx, active ? c : nullptr,
                     parents, tokens, i);
     SAT_LAUNCH_CHECK();
-    beam_merge_launch(s, B, cand_val, cand_idx, K, V, K / num_groups, diversity_penalty, last_tokens, (long)end_id, parent, token, scores_out,
-                      nullptr, 0, nullptr, 0L, nullptr, nullptr, 0, nullptr, 0L, nullptr);
+    beam_merge_launch(s, B, cand_val, cand_idx, K, V, K / G, lambda, last_tokens, (long)end_id, parent, token, scores_out, BeamMove{});
     SAT_LAUNCH_CHECK();
     return SAT_OK;
 }
+
+// (no constraints, no step index: one step of a decode of one step)
+extern "C" int sat_beam_step(const float* logits, int64_t ldl, const float* scores_in, const int64_t* last_tokens,
+                             int64_t end_id, int B, int K, int V, int32_t* parent, int64_t* token, float* scores_out,
+                             void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    return beam_step_impl(logits, ldl, scores_in, last_tokens, end_id, B, K, V, nullptr, nullptr, nullptr, 0, 1, 1, 0.0f, parent, token,
+                          scores_out, workspace, ws_bytes, stream);
+}
+
+extern "C" int sat_beam_step_ex(const float* logits, int64_t ldl, const float* scores_in, const int64_t* last_tokens,
+                                int64_t end_id, int B, int K, int V, const sat_beam_constraints* c, const int32_t* parents,
+                                const int64_t* tokens, int i, int T, int32_t* parent, int64_t* token, float* scores_out,
+                                void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    return beam_step_impl(logits, ldl, scores_in, last_tokens, end_id, B, K, V, c, parents, tokens, i, T, 1, 0.0f, parent, token,
+                          scores_out, workspace, ws_bytes, stream);
+}
+
+// (num_groups == 1: the launches of sat_beam_step_ex)
+extern "C" int sat_beam_step_groups(const float* logits, int64_t ldl, const float* scores_in, const int64_t* last_tokens,
+                                    int64_t end_id, int B, int K, int V, const sat_beam_constraints* c, const int32_t* parents,
+                                    const int64_t* tokens, int i, int T, int num_groups, float diversity_penalty, int32_t* parent,
+                                    int64_t* token, float* scores_out, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    return beam_step_impl(logits, ldl, scores_in, last_tokens, end_id, B, K, V, c, parents, tokens, i, T, num_groups, diversity_penalty,
+                          parent, token, scores_out, workspace, ws_bytes, stream);
+}
+
 
 extern "C" int sat_beam_rerank(const int64_t* ids, const float* scores, int B, int K, int T, int64_t end_id, float length_penalty,
                                int64_t* ids_out, float* scores_out, float* norm_out, int32_t* order_out, sat_stream_t stream) {
@@ -854,266 +846,6 @@ extern "C" int sat_beam_rerank(const int64_t* ids, const float* scores, int B, i
                        scores_out, norm_out, order_out);
     SAT_LAUNCH_CHECK();
     return SAT_OK;
-}
-
-// ---- the whole beam decode of one batch as ONE call (eval.py:99's `model.sample` loop, models.py:56-67, widened to a beam; the
-//      reference's own sample_beam is a stub, model2.py:113-114).  Round 4 drove the 20 steps from Python: seven launches per step
-//      through ctypes, 2.44 ms per 20 steps of which the GPU was busy ~1.3 ms -- the loop was host-bound.  Here the host enqueues
-//      5 launches per step (one LSTM layer) from C with no Python in between: LSTM step, exact-f32 vocab projection, per-row
-//      log-softmax + top-K, per-image merge (which also gathers the next step's embedding rows), ONE (h, c) re-ordering launch per
-//      layer.  Same kernels, same order, same arithmetic as the step-by-step entry points: bit-identical ids and scores. ----
-constexpr int kBeamKSplitMax = 8;      // K-split slices of the wide LSTM step's gate GEMM (the workspace holds that many [R][4H] slabs)
-
-extern "C" int64_t sat_beam_decode_ws_bytes(int B, int K, int E, int H, int V, int num_layers, int steps) {
-    if (B <= 0 || K <= 0 || K > KMAX || E <= 0 || H <= 0 || V <= 0 || num_layers < 1 || steps < 1) return 0;
-    const int64_t R = (int64_t)B * K, ldl = (V + 3) / 4 * 4;
-    // (+ the wide path's buffers: two [R][E + H] input rows, W_cat [4H][E + H], gates [R][4H])
-    // (+ the vocab projection's weights split three ways for the bf16 pipe, when the wide path runs it: sat_gemm_f32x3)
-    return al256(sat_gemm_f32x3_packed_bytes(V, H)) +
-           al256(4 * (int64_t)num_layers * R * H * 4) + al256(R * ldl * 4) + 2 * al256(R * 4) + al256(sat_beam_step_ws_bytes(B, K)) +
-           al256((int64_t)steps * R * 4) + al256((int64_t)steps * R * 8) + 2 * al256(R * E * 4) +
-           2 * al256(R * (int64_t)(E + H) * 4) + al256(4 * (int64_t)H * (E + H) * 4) + al256(kBeamKSplitMax * R * 4 * (int64_t)H * 4);
-}
-
-// what sat_beam_decode_ex adds to the workspace: the ids in search order (the rerank writes the caller's), scores, norm, order,
-// and the two planes of the per-slot prefix history
-static int64_t beam_decode_ex_extra(int64_t R, int steps) { return al256(R * steps * 8) + 3 * al256(R * 4) + al256(2 * R * kBanTMax * 4); }
-
-extern "C" int64_t sat_beam_decode_ex_ws_bytes(int B, int K, int E, int H, int V, int num_layers, int steps) {
-    const int64_t base = sat_beam_decode_ws_bytes(B, K, E, H, V, num_layers, steps);
-    return base <= 0 ? 0 : base + beam_decode_ex_extra((int64_t)B * K, steps);
-}
-
-// ONE loop for sat_beam_decode (ex false, c NULL), sat_beam_decode_ex and sat_beam_decode_groups: with constraints the row launch of a
-// step that bans something is the constrained kernel; with G > 1 groups the first slot of every group starts live and the merge
-// launch of every step is the grouped one; with a length penalty or with groups the rerank runs behind the backtrack; nothing else
-// differs
-static int beam_decode_impl(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
-                            const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
-                            int64_t end_id, bool ex, const sat_beam_constraints* c, int G, float lambda, int64_t* ids, float* scores_out,
-                            float* norm_scores, int32_t* order, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
-    if (!features || !embed || !lstm_w || !lin_w || !lin_b || !ids || !workspace) return SAT_ERR_ARG;
-    SAT_TRY(beam_groups_check(K, G, lambda));
-    const int64_t need = ex ? sat_beam_decode_ex_ws_bytes(B, K, E, H, V, num_layers, steps)
-                            : sat_beam_decode_ws_bytes(B, K, E, H, V, num_layers, steps);
-    if (need <= 0) return SAT_ERR_ARG;
-    bool active = false;
-    SAT_TRY(beam_constraints_check(c, end_id, &active));
-    if ((E & 3) || (long)K * V > INT_MAX - 1) return SAT_ERR_UNSUPPORTED;
-    if (active && (steps > kBanTMax || V > kBanVMax)) return SAT_ERR_UNSUPPORTED;
-    const bool rerank = (c && c->length_penalty > 0.0f) || G > 1;      // (groups: the results leave in (norm desc, slot asc) order)
-    const int Kg = K / G;
-    const float c_length_penalty = c ? c->length_penalty : 0.0f;
-    if (!active) c = nullptr;
-    if (ws_bytes < need || (((uintptr_t)workspace) & 255)) return SAT_ERR_WORKSPACE;
-    for (int i = 0; i < 4 * num_layers; ++i)
-        if (!lstm_w[i]) return SAT_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t R = (int64_t)B * K, ldl = (V + 3) / 4 * 4;
-    char* w = (char*)workspace;
-    float* hc = (float*)w;                                     // [layer][h0, h1, c0, c1][R][H]
-    w += al256(4 * (int64_t)num_layers * R * H * 4);
-    float* logits = (float*)w; w += al256(R * ldl * 4);
-    float* sc[2];
-    sc[0] = (float*)w; w += al256(R * 4);
-    sc[1] = (float*)w; w += al256(R * 4);
-    void* cand = w; w += al256(sat_beam_step_ws_bytes(B, K));
-    int32_t* parents = (int32_t*)w; w += al256((int64_t)steps * R * 4);
-    int64_t* tokens = (int64_t*)w; w += al256((int64_t)steps * R * 8);
-    float* x0 = (float*)w; w += al256(R * E * 4);
-    float* xe = (float*)w; w += al256(R * E * 4);
-    float* xh[2];
-    xh[0] = (float*)w; w += al256(R * (int64_t)(E + H) * 4);
-    xh[1] = (float*)w; w += al256(R * (int64_t)(E + H) * 4);
-    float* wcat = (float*)w; w += al256(4 * (int64_t)H * (E + H) * 4);
-    float* gates = (float*)w; w += al256(kBeamKSplitMax * R * 4 * (int64_t)H * 4);
-    int64_t* ids_search = nullptr;
-    float *sc_ranked = nullptr, *norm_tmp = nullptr;
-    int32_t* order_tmp = nullptr;
-    int* hist = nullptr;
-    if (ex) {
-        ids_search = (int64_t*)w; w += al256(R * steps * 8);
-        sc_ranked = (float*)w; w += al256(R * 4);
-        norm_tmp = (float*)w; w += al256(R * 4);
-        order_tmp = (int32_t*)w; w += al256(R * 4);
-        hist = (int*)w; w += al256(2 * R * kBanTMax * 4);
-    }
-    static const bool hist_env = [] { const char* v = getenv("SAT_BEAM_HISTORY"); return !(v && v[0] == '0'); }();
-    if (!(c && c->no_repeat_ngram >= 1 && hist_env)) hist = nullptr;      // only n-gram blocking reads the whole prefix
-    void* lin_split = w;                                       // [V128][H] x 3 bf16, fragment ordered (sat_gemm_f32x3_pack)
-    hipError_t e = hipMemsetAsync(hc, 0, (size_t)(4 * (int64_t)num_layers * R * H * 4), s);      // h = c = 0
-    if (e != hipSuccess) return (int)e;
-    // WIDE steps (round 5): with one LSTM layer and >= 128 rows the step's gates are ONE LDS-tiled exact-f32 MFMA GEMM over the
-    // concatenated row [x | h] (sat_gemm_f32: ~0.5 of the f32 peak) + a pointwise launch, instead of the few-rows kernel, which
-    // re-reads the 6 MB of weights once per 64-row chunk (34 -> ~17 us per step at 320 rows)
-    const bool wide = num_layers == 1 && R >= 128 && !(H & 3);
-    const long ldx = E + H;
-    // the gate GEMM of a step is small ([R][E + H] x [E + H][4H]: 160 tiles of 64 x 64 at 320 rows): its K axis is dealt over enough
-    // slices to fill the chip's ~512 workgroup slots, the pointwise launch sums the slices in order (measured at 320 rows, 20 steps:
-    // 1 slice 1.82 ms, 2 1.76, 3 1.685, 4 1.73, 6 1.75, 8 1.85 -- profiles/r05_decode_loop.txt); SAT_BEAM_KSPLIT overrides
-    static const int ks_env = [] { const char* e = getenv("SAT_BEAM_KSPLIT"); return e ? atoi(e) : 0; }();
-    int ksplit = 1;
-    if (wide) {
-        const long tiles = (long)sat_cdiv((int)R, 64) * sat_cdiv(4 * H, 64);
-        ksplit = (int)(512 / (tiles > 0 ? tiles : 1));
-        const int nk = sat_cdiv((int)ldx, 32);                 // K-steps of the f32 kernel
-        if (ksplit > nk / 4) ksplit = nk / 4;
-        if (ksplit > kBeamKSplitMax) ksplit = kBeamKSplitMax;
-        if (ksplit < 1) ksplit = 1;
-        if (ks_env >= 1 && ks_env <= kBeamKSplitMax) ksplit = ks_env;
-    }
-    // WIDE projection (round 5): with >= 128 rows the vocab projection -- half of a step on the exact-f32 pipe -- runs on the bf16
-    // pipe from a three-way split of both operands (sat_gemm_x3.hip: f32 accuracy, not the f32 pipe's bit pattern; the weights are
-    // split once per call).  SAT_BEAM_X3=0: the exact-f32 pipe
-    static const bool x3_env = [] { const char* v = getenv("SAT_BEAM_X3"); return !(v && v[0] == '0'); }();
-    const bool x3 = wide && x3_env && sat_gemm_f32x3_packed_bytes(V, H) > 0 && !(V & 3);
-    if (x3) SAT_TRY(sat_gemm_f32x3_pack(lin_w, V, H, lin_split, stream));
-    if (wide) {
-        e = hipMemsetAsync(xh[0], 0, (size_t)(R * ldx * 4), s);                                  // h_{-1} = 0
-        if (e != hipSuccess) return (int)e;
-        const long total = 4L * H * ldx;
-        int grid = sat_cdiv(total, 256);
-        if (grid > 2048) grid = 2048;
-        hipLaunchKernelGGL(beam_wcat_kernel, dim3(grid), dim3(256), 0, s, lstm_w[0], lstm_w[1], E, H, total, wcat);
-        SAT_LAUNCH_CHECK();
-    }
-    if (ldl > V) {                                             // pad columns of the logits rows: read by nobody, but keep them defined
-        e = hipMemsetAsync(logits, 0, (size_t)(R * ldl * 4), s);
-        if (e != hipSuccess) return (int)e;
-    }
-    {
-        const long total = R * E;                              // (>= R: the scores, one per thread, are covered by the same grid)
-        int grid = sat_cdiv(total, 256);
-        if (grid > 2048) grid = 2048;
-        if ((long)grid * 256 < R) grid = sat_cdiv(R, 256);
-        hipLaunchKernelGGL(beam_init_kernel, dim3(grid), dim3(256), 0, s, features, K, E, total, wide ? xh[0] : x0, wide ? ldx : (long)E,
-                           sc[0], (int)R, Kg);
-        SAT_LAUNCH_CHECK();
-    }
-    float* cand_val = (float*)cand;
-    int* cand_idx = (int*)(cand_val + (long)B * K * K);
-    int cur_h[8] = {0}, cur_c[8] = {0};                        // which of the two buffers holds a layer's live h / c
-    if (num_layers > 8) return SAT_ERR_UNSUPPORTED;
-    const float* x = x0;
-    int si = 0, xi = 0;
-    for (int i = 0; i < steps; ++i) {
-        const float* inp = x;
-        if (wide) {
-            float* c = hc + (long)(2 + cur_c[0]) * R * H;
-            float* h_new = hc + (long)cur_h[0] * R * H;
-            SAT_TRY(sat_gemm_f32_splitk(0, 0, xh[xi], ldx, wcat, ldx, gates, 4L * H, lstm_w[2], lstm_w[3], (int)R, 4 * H, (int)ldx, ksplit,
-                                        R * 4L * H, stream));
-            {
-                const long total = R * H;
-                int grid = sat_cdiv(total, 256);
-                if (grid > 2048) grid = 2048;
-                hipLaunchKernelGGL(beam_lstm_point_kernel, dim3(grid), dim3(256), 0, s, gates, c, h_new, H, total, ksplit, R * 4L * H);
-                SAT_LAUNCH_CHECK();
-            }
-            inp = h_new;
-        }
-        for (int l = 0; l < num_layers && !wide; ++l) {
-            float* base = hc + (long)l * 4 * R * H;
-            float* h_in = base + (long)cur_h[l] * R * H;
-            float* h_out = base + (long)(1 - cur_h[l]) * R * H;
-            float* c = base + (long)(2 + cur_c[l]) * R * H;
-            const int In = l == 0 ? E : H;
-            SAT_TRY(sat_lstm_step(inp, h_in, c, lstm_w[4 * l], lstm_w[4 * l + 1], lstm_w[4 * l + 2], lstm_w[4 * l + 3], (int)R, In, H,
-                                  h_out, stream));
-            cur_h[l] = 1 - cur_h[l];
-            inp = h_out;
-        }
-        if (x3) SAT_TRY(sat_gemm_f32x3(inp, H, lin_split, lin_b, logits, ldl, (int)R, V, H, stream));
-        else SAT_TRY(sat_vocab_logits_fwd(inp, lin_w, lin_b, (int)R, H, V, logits, ldl, stream));
-        int32_t* par = parents + (long)i * R;
-        int64_t* tok = tokens + (long)i * R;
-        const int64_t* last = (i > 0 && end_id >= 0) ? tok - R : (const int64_t*)nullptr;
-        beam_row_launch(s, logits, (long)ldl, sc[si], last, (long)end_id, (int)R, K, V, cand_val, cand_idx, c, parents, tokens, i, hist);
-        SAT_LAUNCH_CHECK();
-        if (wide) {
-            // ... the merge wave also moves (h, c) by parent: h straight into the next input row's h half (one launch fewer per step)
-            beam_merge_launch(s, B, cand_val, cand_idx, K, V, Kg, lambda, last, (long)end_id, par, tok, sc[1 - si], embed, E, xh[1 - xi], ldx,
-                              hc + (long)cur_h[0] * R * H, hc + (long)(2 + cur_c[0]) * R * H, H, xh[1 - xi] + E, ldx,
-                              hc + (long)(2 + 1 - cur_c[0]) * R * H);
-            SAT_LAUNCH_CHECK();
-            si = 1 - si;
-            cur_c[0] = 1 - cur_c[0];
-            xi = 1 - xi;
-            x = xe;
-            continue;
-        }
-        beam_merge_launch(s, B, cand_val, cand_idx, K, V, Kg, lambda, last, (long)end_id, par, tok, sc[1 - si], embed, E, xe, (long)E, nullptr,
-                          nullptr, 0, nullptr, 0L, nullptr);
-        SAT_LAUNCH_CHECK();
-        si = 1 - si;
-        if (K > 1) {
-            for (int l = 0; l < num_layers; ++l) {
-                float* base = hc + (long)l * 4 * R * H;
-                const long total = R * H;
-                int grid = sat_cdiv(2 * total, 256);
-                if (grid > 2048) grid = 2048;
-                hipLaunchKernelGGL(beam_gather2_kernel, dim3(grid), dim3(256), 0, s, base + (long)cur_h[l] * R * H,
-                                   base + (long)(2 + cur_c[l]) * R * H, par, K, H, total, base + (long)(1 - cur_h[l]) * R * H, (long)H,
-                                   base + (long)(2 + 1 - cur_c[l]) * R * H);
-                SAT_LAUNCH_CHECK();
-                cur_h[l] = 1 - cur_h[l];
-                cur_c[l] = 1 - cur_c[l];
-            }
-        }
-        x = xe;
-    }
-    hipLaunchKernelGGL(beam_backtrack_kernel, dim3(sat_cdiv(R, 256)), dim3(256), 0, s, parents, tokens, steps, (int)R, K,
-                       rerank ? ids_search : ids);
-    SAT_LAUNCH_CHECK();
-    if (rerank) {                                              // (ex) the K hypotheses of an image re-ordered by score / L^alpha
-        hipLaunchKernelGGL(beam_rerank_kernel, dim3(B), dim3(64), 0, s, (const int64_t*)ids_search, (const float*)sc[si], K, steps, end_id,
-                           c_length_penalty, ids, scores_out ? scores_out : sc_ranked, norm_scores ? norm_scores : norm_tmp,
-                           order ? order : order_tmp);
-        SAT_LAUNCH_CHECK();
-        return SAT_OK;
-    }
-    if (scores_out) {
-        e = hipMemcpyAsync(scores_out, sc[si], (size_t)(R * 4), hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (norm_scores) {                                         // no penalty: the norm is the score, the order the identity
-        e = hipMemcpyAsync(norm_scores, sc[si], (size_t)(R * 4), hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (order) {
-        hipLaunchKernelGGL(beam_iota_kernel, dim3(sat_cdiv(R, 256)), dim3(256), 0, s, order, (int)R, K);
-        SAT_LAUNCH_CHECK();
-    }
-    return SAT_OK;
-}
-
-extern "C" int sat_beam_decode(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
-                               const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
-                               int64_t end_id, int64_t* ids, float* scores_out, void* workspace, int64_t ws_bytes,
-                               sat_stream_t stream) {
-    return beam_decode_impl(features, embed, lstm_w, num_layers, lin_w, lin_b, B, K, E, H, V, steps, end_id, false, nullptr, 1, 0.0f, ids,
-                            scores_out, nullptr, nullptr, workspace, ws_bytes, stream);
-}
-
-extern "C" int sat_beam_decode_ex(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
-                                  const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
-                                  int64_t end_id, const sat_beam_constraints* c, int64_t* ids, float* scores_out, float* norm_scores,
-                                  int32_t* order, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
-    return beam_decode_impl(features, embed, lstm_w, num_layers, lin_w, lin_b, B, K, E, H, V, steps, end_id, true, c, 1, 0.0f, ids,
-                            scores_out, norm_scores, order, workspace, ws_bytes, stream);
-}
-
-extern "C" int64_t sat_beam_decode_groups_ws_bytes(int B, int K, int E, int H, int V, int num_layers, int steps) {
-    return sat_beam_decode_ex_ws_bytes(B, K, E, H, V, num_layers, steps);
-}
-
-extern "C" int sat_beam_decode_groups(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
-                                      const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
-                                      int64_t end_id, const sat_beam_constraints* c, int num_groups, float diversity_penalty,
-                                      int64_t* ids, float* scores_out, float* norm_scores, int32_t* order, void* workspace,
-                                      int64_t ws_bytes, sat_stream_t stream) {
-    return beam_decode_impl(features, embed, lstm_w, num_layers, lin_w, lin_b, B, K, E, H, V, steps, end_id, true, c, num_groups,
-                            diversity_penalty, ids, scores_out, norm_scores, order, workspace, ws_bytes, stream);
 }
 
 extern "C" int sat_beam_gather_rows(const float* src, const int32_t* parent, int B, int K, int width, float* dst,
@@ -1348,11 +1080,6 @@ extern "C" int sat_ensemble_logprobs(const float* const* logits, int M, int64_t 
     return SAT_OK;
 }
 
-// ---- the beam decode of an ENSEMBLE of DecoderRNN models as ONE call: beam_decode_impl's loop with M decoder states in lock step.
-//      Per step and model: the LSTM stack step and the vocab projection into the model's own [R][pad4(V)] matrix (narrow: sat_lstm_step
-//      per layer and the exact-f32 projection; wide: see ensemble_wide); then ONE combine launch, the row launch and the merge launch
-//      on the combined matrix -- the plain, ban and group variants as beam_decode_impl chooses them -- and per model the embedding
-//      rows of the chosen tokens and the (h, c) re-ordering.  Which kernels run is a function of the shapes alone. ----
 static int ensemble_models_check(const sat_decoder_model* models, int M) {
     if (!models || M < 1 || M > kEnsMax) return SAT_ERR_ARG;
     bool unsupported = false;                                  // (an argument error anywhere comes in front of it)
@@ -1364,33 +1091,6 @@ static int ensemble_models_check(const sat_decoder_model* models, int M) {
             if (!d.lstm_w[i]) return SAT_ERR_ARG;
     }
     return unsupported ? SAT_ERR_UNSUPPORTED : SAT_OK;
-}
-
-// A member takes beam_decode_impl's WIDE step where that loop does -- one LSTM layer and >= 128 rows: the gates as ONE split-K
-// exact-f32 GEMM over [x | h] plus the pointwise launch, and the projection on the bf16 pipe from a three-way split where V % 4 == 0
-// (measured at 320 rows, E 256, H 512, V 10 000, 20 steps: 1.7 ms per member on the narrow path, ~1.0 on this one;
-// profiles/ensemble_bench.txt).  A function of the member's shape and the row count alone.
-static bool ensemble_wide(const sat_decoder_model& d, int64_t R) { return d.num_layers == 1 && R >= 128; }
-static bool ensemble_x3(const sat_decoder_model& d, int64_t R, int V) {
-    return ensemble_wide(d, R) && !(V & 3) && sat_gemm_f32x3_packed_bytes(V, d.H) > 0;
-}
-// the K-split of the wide gate GEMM: beam_decode_impl's rule (enough slices to fill the chip's ~512 workgroup slots)
-static int ensemble_ksplit(int64_t R, int H, long ldx) {
-    const long tiles = (long)sat_cdiv((int)R, 64) * sat_cdiv(4 * H, 64);
-    int ksplit = (int)(512 / (tiles > 0 ? tiles : 1));
-    const int nk = sat_cdiv((int)ldx, 32);
-    if (ksplit > nk / 4) ksplit = nk / 4;
-    if (ksplit > kBeamKSplitMax) ksplit = kBeamKSplitMax;
-    return ksplit < 1 ? 1 : ksplit;
-}
-
-// a model's own part of the workspace: (h, c) of every layer twice and its logits matrix; narrow: the step-0 input rows and the
-// embedding rows; wide: two [R][E + H] input rows, W_cat, the gate slabs and the split projection weights
-static int64_t ensemble_model_bytes(const sat_decoder_model& d, int64_t R, int64_t ldl, int V) {
-    int64_t n = al256(4 * (int64_t)d.num_layers * R * d.H * 4) + al256(R * ldl * 4);
-    if (!ensemble_wide(d, R)) return n + 2 * al256(R * d.E * 4);
-    n += 2 * al256(R * (int64_t)(d.E + d.H) * 4) + al256(4 * (int64_t)d.H * (d.E + d.H) * 4) + al256(kBeamKSplitMax * R * 4 * (int64_t)d.H * 4);
-    return n + (ensemble_x3(d, R, V) ? al256(sat_gemm_f32x3_packed_bytes(V, d.H)) : 0);
 }
 
 // what beam_merge_kernel's second half does for the model whose rows it moves, for ANY model of an ensemble: one workgroup per image
@@ -1408,14 +1108,380 @@ __global__ __launch_bounds__(256) void ensemble_move_rows_kernel(const int* __re
     beam_move_rows(s_par, s_tok, b, K, lane, wave, embed, E, x_next, ldx, h_src, c_src, H, h_dst, ldh, c_dst);
 }
 
+// ---- the whole beam decode of one batch as ONE call (eval.py:99's `model.sample` loop, models.py:56-67, widened to a beam; the
+//      reference's own sample_beam is a stub, model2.py:113-114): the host enqueues every step from C with no Python in between.
+//      Two parts carry it.  BeamMember is ONE decoder's state in a beam of R = B*K rows: its plan (which kernels its shape takes),
+//      its slice of the workspace, its setup, its step into its own logits matrix, and the two ways its rows follow a selection.
+//      BeamSearch is everything that is not per model: scores, candidates, the (parent, token) records, the row and merge launches,
+//      the backtrack and the rerank.  beam_decode_impl (sat_beam_decode, _ex, _groups) drives one member, with the member's row
+//      moves fused into the merge launch: 5 launches per step at one wide layer.  sat_beam_decode_ensemble drives M members in lock
+//      step, with the combine launch between their steps and the selection.  Same kernels, same arithmetic as the step-by-step
+//      entry points: bit-identical ids and scores. ----
+constexpr int kBeamKSplitMax = 8;      // K-split slices of the wide step's gate GEMM (a wide member's workspace holds that many [R][4H] slabs)
+
+static int beam_grid(long total) { return total > 2048L * 256 ? 2048 : sat_cdiv(total, 256); }
+
+struct BeamMember {
+    sat_decoder_model d = {};
+    int B = 0, K = 0, V = 0, ksplit = 1;
+    int64_t R = 0, ldl = 0;
+    bool wide = false, x3 = false;
+    float *hc = nullptr, *logits = nullptr;                    // [layer][h0, h1, c0, c1][R][H]; [R][ldl]
+    float *x0 = nullptr, *xe = nullptr;                        // narrow: the step-0 input rows and the embedding rows, [R][E]
+    float *xh[2] = {}, *wcat = nullptr, *gates = nullptr;      // wide: two [R][E + H] input rows, W_cat [4H][E + H], the gate slabs
+    void* lin_split = nullptr;                                 // x3: [V128][H] x 3 bf16, fragment ordered (sat_gemm_f32x3_pack)
+    int cur_h[8] = {}, cur_c[8] = {}, xi = 0;                  // which of the two buffers holds a layer's live h / c, the live [x | h]
+
+    BeamMember() = default;
+    explicit BeamMember(const sat_decoder_model& d_) : d(d_) {}
+
+    // Which kernels the member's shape takes, decided here and nowhere else.
+    // WIDE step: with one LSTM layer and >= 128 rows the gates are ONE LDS-tiled exact-f32 MFMA GEMM over the concatenated row
+    // [x | h] (sat_gemm_f32: ~0.5 of the f32 peak) + a pointwise launch, instead of the few-rows kernel, which re-reads the weights
+    // once per 64-row chunk (34 -> ~17 us per step at 320 rows; 1.7 -> ~1.0 ms per member of an ensemble, profiles/ensemble_bench.txt).
+    // That GEMM is small (160 tiles of 64 x 64 at 320 rows): its K axis is dealt over enough slices to fill the chip's ~512
+    // workgroup slots, the pointwise launch sums the slices in order (measured at 320 rows, 20 steps: 1 slice 1.82 ms, 2 1.76,
+    // 3 1.685, 4 1.73, 6 1.75, 8 1.85 -- profiles/r05_decode_loop.txt).
+    // X3 projection: on the wide path with V % 4 == 0 the vocab projection -- half of a step on the exact-f32 pipe -- runs on the
+    // bf16 pipe from a three-way split of both operands (sat_gemm_x3.hip: f32 accuracy, not the f32 pipe's bit pattern).
+    // honour_env (the single-model entry points): SAT_BEAM_KSPLIT in 1..8 overrides the slices, SAT_BEAM_X3=0 keeps the exact-f32
+    // pipe.  An ensemble's kernels are a function of the shapes alone.
+    void plan(int B_, int K_, int V_, bool honour_env) {
+        static const int ks_env = [] { const char* e = getenv("SAT_BEAM_KSPLIT"); return e ? atoi(e) : 0; }();
+        static const bool x3_env = [] { const char* v = getenv("SAT_BEAM_X3"); return !(v && v[0] == '0'); }();
+        B = B_, K = K_, V = V_;
+        R = (int64_t)B * K, ldl = (V + 3) / 4 * 4;
+        wide = d.num_layers == 1 && R >= 128 && !(d.H & 3);
+        x3 = wide && (x3_env || !honour_env) && sat_gemm_f32x3_packed_bytes(V, d.H) > 0 && !(V & 3);
+        ksplit = 1;
+        if (!wide) return;
+        const long tiles = (long)sat_cdiv((int)R, 64) * sat_cdiv(4 * d.H, 64);
+        ksplit = (int)(512 / (tiles > 0 ? tiles : 1));
+        const int nk = sat_cdiv(d.E + d.H, 32);                // K-steps of the f32 kernel
+        if (ksplit > nk / 4) ksplit = nk / 4;
+        if (ksplit > kBeamKSplitMax) ksplit = kBeamKSplitMax;
+        if (ksplit < 1) ksplit = 1;
+        if (honour_env && ks_env >= 1 && ks_env <= kBeamKSplitMax) ksplit = ks_env;
+    }
+
+    // the member's slice of the workspace, as carve() takes it
+    int64_t bytes() const {
+        const int64_t ldx = d.E + d.H;
+        const int64_t n = al256(4 * (int64_t)d.num_layers * R * d.H * 4) + al256(R * ldl * 4);
+        if (!wide) return n + 2 * al256(R * d.E * 4);
+        return n + 2 * al256(R * ldx * 4) + al256(4 * (int64_t)d.H * ldx * 4) + al256(kBeamKSplitMax * R * 4 * (int64_t)d.H * 4) +
+               (x3 ? al256(sat_gemm_f32x3_packed_bytes(V, d.H)) : 0);
+    }
+    void carve(char*& w) {
+        const int64_t ldx = d.E + d.H;
+        hc = (float*)w; w += al256(4 * (int64_t)d.num_layers * R * d.H * 4);
+        logits = (float*)w; w += al256(R * ldl * 4);
+        if (!wide) {
+            x0 = (float*)w; w += al256(R * d.E * 4);
+            xe = (float*)w; w += al256(R * d.E * 4);
+            return;
+        }
+        xh[0] = (float*)w; w += al256(R * ldx * 4);
+        xh[1] = (float*)w; w += al256(R * ldx * 4);
+        wcat = (float*)w; w += al256(4 * (int64_t)d.H * ldx * 4);
+        gates = (float*)w; w += al256(kBeamKSplitMax * R * 4 * (int64_t)d.H * 4);
+        if (x3) { lin_split = w; w += al256(sat_gemm_f32x3_packed_bytes(V, d.H)); }
+    }
+
+    float* h_buf(int l, int which) const { return hc + ((long)l * 4 + which) * R * d.H; }
+    float* c_buf(int l, int which) const { return hc + ((long)l * 4 + 2 + which) * R * d.H; }
+
+    // before step 0: h = c = 0, the weights in the forms the plan needs, the features as every row's first input, and the start
+    // scores sc0 (every member of an ensemble writes the same ones)
+    int setup(sat_stream_t stream, int Kg, float* sc0) {
+        hipStream_t s = (hipStream_t)stream;
+        const long ldx = d.E + d.H;
+        hipError_t e = hipMemsetAsync(hc, 0, (size_t)(4 * (int64_t)d.num_layers * R * d.H * 4), s);
+        if (e != hipSuccess) return (int)e;
+        if (x3) SAT_TRY(sat_gemm_f32x3_pack(d.lin_w, V, d.H, lin_split, stream));      // (the weights are split once per call)
+        if (wide) {
+            e = hipMemsetAsync(xh[0], 0, (size_t)(R * ldx * 4), s);                     // h_{-1} = 0
+            if (e != hipSuccess) return (int)e;
+            const long total = 4L * d.H * ldx;
+            hipLaunchKernelGGL(beam_wcat_kernel, dim3(beam_grid(total)), dim3(256), 0, s, d.lstm_w[0], d.lstm_w[1], d.E, d.H, total, wcat);
+            SAT_LAUNCH_CHECK();
+        }
+        if (ldl > V) {                                         // pad columns of the logits rows: read by nobody, but keep them defined
+            e = hipMemsetAsync(logits, 0, (size_t)(R * ldl * 4), s);
+            if (e != hipSuccess) return (int)e;
+        }
+        const long total = R * d.E;                            // (the scores, one per thread, are covered by the same grid)
+        int grid = beam_grid(total);
+        if ((long)grid * 256 < R) grid = sat_cdiv(R, 256);
+        hipLaunchKernelGGL(beam_init_kernel, dim3(grid), dim3(256), 0, s, d.features, K, d.E, total, wide ? xh[0] : x0,
+                           wide ? ldx : (long)d.E, sc0, (int)R, Kg);
+        SAT_LAUNCH_CHECK();
+        return SAT_OK;
+    }
+
+    // step i: the LSTM stack on the live input rows, then the vocab projection of the top h into `logits`
+    int forward(sat_stream_t stream, int i) {
+        const int H = d.H;
+        const float* inp = i == 0 ? x0 : xe;
+        if (wide) {
+            const long ldx = d.E + H, total = R * H;
+            float* h_new = h_buf(0, 0);                        // (a wide h never ping-pongs: the row move puts it into the next [x | h])
+            SAT_TRY(sat_gemm_f32_splitk(0, 0, xh[xi], ldx, wcat, ldx, gates, 4L * H, d.lstm_w[2], d.lstm_w[3], (int)R, 4 * H, (int)ldx,
+                                        ksplit, R * 4L * H, stream));
+            hipLaunchKernelGGL(beam_lstm_point_kernel, dim3(beam_grid(total)), dim3(256), 0, (hipStream_t)stream, gates,
+                               c_buf(0, cur_c[0]), h_new, H, total, ksplit, R * 4L * H);
+            SAT_LAUNCH_CHECK();
+            inp = h_new;
+        }
+        for (int l = 0; l < d.num_layers && !wide; ++l) {
+            float* h_out = h_buf(l, 1 - cur_h[l]);
+            SAT_TRY(sat_lstm_step(inp, h_buf(l, cur_h[l]), c_buf(l, cur_c[l]), d.lstm_w[4 * l], d.lstm_w[4 * l + 1], d.lstm_w[4 * l + 2],
+                                  d.lstm_w[4 * l + 3], (int)R, l == 0 ? d.E : H, H, h_out, stream));
+            cur_h[l] = 1 - cur_h[l];
+            inp = h_out;
+        }
+        if (x3) return sat_gemm_f32x3(inp, H, lin_split, d.lin_b, logits, ldl, (int)R, V, H, stream);
+        return sat_vocab_logits_fwd(inp, d.lin_w, d.lin_b, (int)R, H, V, logits, ldl, stream);
+    }
+
+    // The rows follow a selection in one of two ways.
+    // FUSED (one model): the merge wave itself moves them -- wide: the embedding rows and (h, c) by parent, h straight into the next
+    // input row's h half (one launch fewer per step); narrow: the embedding rows only, then gather() per layer.
+    BeamMove fused_move() const {
+        if (!wide) return BeamMove{d.embed, d.E, xe, (long)d.E, nullptr, nullptr, 0, nullptr, 0L, nullptr};
+        const long ldx = d.E + d.H;
+        float* xn = xh[1 - xi];
+        return BeamMove{d.embed, d.E, xn, ldx, h_buf(0, 0), c_buf(0, cur_c[0]), d.H, xn + d.E, ldx, c_buf(0, 1 - cur_c[0])};
+    }
+    void after_fused_merge() {
+        if (!wide) return;
+        cur_c[0] = 1 - cur_c[0];
+        xi = 1 - xi;
+    }
+    // a narrow member's (h, c) of every layer re-ordered by parent: one launch per layer (K == 1: every row is its own parent)
+    int gather(sat_stream_t stream, const int32_t* par) {
+        const long total = R * d.H;
+        for (int l = 0; l < d.num_layers && !wide && K > 1; ++l) {
+            hipLaunchKernelGGL(beam_gather2_kernel, dim3(beam_grid(2 * total)), dim3(256), 0, (hipStream_t)stream,
+                               (const float*)h_buf(l, cur_h[l]), (const float*)c_buf(l, cur_c[l]), par, K, d.H, total,
+                               h_buf(l, 1 - cur_h[l]), (long)d.H, c_buf(l, 1 - cur_c[l]));
+            SAT_LAUNCH_CHECK();
+            cur_h[l] = 1 - cur_h[l];
+            cur_c[l] = 1 - cur_c[l];
+        }
+        return SAT_OK;
+    }
+    // ON ITS OWN (any member of an ensemble), from the step's records -- wide: ONE launch that does what the fused merge does;
+    // narrow: the embedding rows, then gather()
+    int move_rows(sat_stream_t stream, const int32_t* par, const int64_t* tok) {
+        if (!wide) {
+            SAT_TRY(sat_embed_rows(d.embed, tok, 1, (int)R, d.E, V, xe, stream));
+            return gather(stream, par);
+        }
+        const BeamMove m = fused_move();
+        hipLaunchKernelGGL(ensemble_move_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const int*)par, tok, K, m.embed, m.E,
+                           m.x_next, m.ldx, m.h_src, m.c_src, m.H, m.h_dst, m.ldh, m.c_dst);
+        SAT_LAUNCH_CHECK();
+        after_fused_merge();
+        return SAT_OK;
+    }
+};
+
+struct BeamSearch {
+    int B = 0, K = 0, V = 0, steps = 0, Kg = 0, si = 0;
+    int64_t R = 0, end_id = -1;
+    float lambda = 0.0f, length_penalty = 0.0f;
+    bool ex = false, rerank = false;
+    const sat_beam_constraints* c = nullptr;                   // NULL unless a step constraint is on
+    float *sc[2] = {}, *cand_val = nullptr;                    // the scores before / after a selection (sc[si]: live), [R][K] candidates
+    int* cand_idx = nullptr;
+    int32_t* parents = nullptr;                                // records [steps][R]
+    int64_t* tokens = nullptr;
+    int64_t* ids_search = nullptr;                             // ex: the ids in search order (the rerank writes the caller's), and its
+    float *sc_ranked = nullptr, *norm_tmp = nullptr;           //   outputs where the caller passes NULL
+    int32_t* order_tmp = nullptr;
+    int* hist = nullptr;                                       // ex: the two planes of the per-slot prefix history (beam_row_launch)
+    int32_t* par = nullptr;                                    // the step's records, and the tokens of the step before (NULL: no row is
+    int64_t* tok = nullptr;                                    //   finished)
+    const int64_t* last = nullptr;
+
+    // the checks every whole decode makes before anything is enqueued, in the order of their return codes; sizes_ok / models_ok:
+    // what the driver found for its own sizes (SAT_ERR_ARG) and its models' shapes (SAT_ERR_UNSUPPORTED).  ex: with the rerank's
+    // buffers and the history planes (every entry point but sat_beam_decode)
+    int init(int B_, int K_, int V_, int steps_, int64_t end_id_, const sat_beam_constraints* c_, int G, float lambda_, bool ex_,
+             bool sizes_ok, bool models_ok) {
+        SAT_TRY(beam_groups_check(K_, G, lambda_));
+        if (!sizes_ok) return SAT_ERR_ARG;
+        bool active = false;
+        SAT_TRY(beam_constraints_check(c_, end_id_, &active));
+        if (!models_ok || (long)K_ * V_ > INT_MAX - 1) return SAT_ERR_UNSUPPORTED;
+        if (active && (steps_ > kBanTMax || V_ > kBanVMax)) return SAT_ERR_UNSUPPORTED;
+        B = B_, K = K_, V = V_, steps = steps_, Kg = K_ / G, end_id = end_id_, lambda = lambda_, ex = ex_;
+        R = (int64_t)B * K;
+        rerank = (c_ && c_->length_penalty > 0.0f) || G > 1;   // (groups: the results leave in (norm desc, slot asc) order)
+        length_penalty = c_ ? c_->length_penalty : 0.0f;
+        c = active ? c_ : nullptr;
+        return SAT_OK;
+    }
+
+    static int64_t bytes(int B, int K, int steps, bool ex) {
+        const int64_t R = (int64_t)B * K;
+        const int64_t n = 2 * al256(R * 4) + al256(sat_beam_step_ws_bytes(B, K)) + al256((int64_t)steps * R * 4) + al256((int64_t)steps * R * 8);
+        return ex ? n + al256(R * steps * 8) + 3 * al256(R * 4) + al256(2 * R * kBanTMax * 4) : n;
+    }
+    void carve(char*& w) {
+        sc[0] = (float*)w; w += al256(R * 4);
+        sc[1] = (float*)w; w += al256(R * 4);
+        cand_val = (float*)w; w += al256(sat_beam_step_ws_bytes(B, K));
+        cand_idx = (int*)(cand_val + (long)B * K * K);
+        parents = (int32_t*)w; w += al256((int64_t)steps * R * 4);
+        tokens = (int64_t*)w; w += al256((int64_t)steps * R * 8);
+        if (!ex) return;
+        ids_search = (int64_t*)w; w += al256(R * steps * 8);
+        sc_ranked = (float*)w; w += al256(R * 4);
+        norm_tmp = (float*)w; w += al256(R * 4);
+        order_tmp = (int32_t*)w; w += al256(R * 4);
+        static const bool hist_env = [] { const char* v = getenv("SAT_BEAM_HISTORY"); return !(v && v[0] == '0'); }();
+        if (c && c->no_repeat_ngram >= 1 && hist_env) hist = (int*)w;      // only n-gram blocking reads the whole prefix
+        w += al256(2 * R * kBanTMax * 4);
+    }
+
+    // step i on a matrix of logits (or of combined log-probabilities): every row's K best continuations ...
+    int select(sat_stream_t stream, const float* logits, long ldl, int i) {
+        par = parents + (long)i * R;
+        tok = tokens + (long)i * R;
+        last = (i > 0 && end_id >= 0) ? tok - R : (const int64_t*)nullptr;
+        beam_row_launch((hipStream_t)stream, logits, ldl, sc[si], last, (long)end_id, (int)R, K, V, cand_val, cand_idx, c, parents, tokens, i,
+                        hist);
+        SAT_LAUNCH_CHECK();
+        return SAT_OK;
+    }
+    // ... and every image's K best of those into the step's records; the merge wave then moves the rows of `move`
+    int merge(sat_stream_t stream, const BeamMove& move) {
+        beam_merge_launch((hipStream_t)stream, B, cand_val, cand_idx, K, V, Kg, lambda, last, (long)end_id, par, tok, sc[1 - si], move);
+        SAT_LAUNCH_CHECK();
+        si = 1 - si;
+        return SAT_OK;
+    }
+
+    // behind the last step: the sequences by walking the records back, then the K hypotheses of an image re-ordered by
+    // score / L^alpha -- or, with no rerank, the norm is the score and the order the identity
+    int finish(sat_stream_t stream, int64_t* ids, float* scores_out, float* norm_scores, int32_t* order) {
+        hipStream_t s = (hipStream_t)stream;
+        hipLaunchKernelGGL(beam_backtrack_kernel, dim3(sat_cdiv(R, 256)), dim3(256), 0, s, parents, tokens, steps, (int)R, K,
+                           rerank ? ids_search : ids);
+        SAT_LAUNCH_CHECK();
+        if (rerank) {
+            hipLaunchKernelGGL(beam_rerank_kernel, dim3(B), dim3(64), 0, s, (const int64_t*)ids_search, (const float*)sc[si], K, steps,
+                               end_id, length_penalty, ids, scores_out ? scores_out : sc_ranked, norm_scores ? norm_scores : norm_tmp,
+                               order ? order : order_tmp);
+            SAT_LAUNCH_CHECK();
+            return SAT_OK;
+        }
+        for (float* out : {scores_out, norm_scores}) {
+            if (!out) continue;
+            hipError_t e = hipMemcpyAsync(out, sc[si], (size_t)(R * 4), hipMemcpyDeviceToDevice, s);
+            if (e != hipSuccess) return (int)e;
+        }
+        if (order) {
+            hipLaunchKernelGGL(beam_iota_kernel, dim3(sat_cdiv(R, 256)), dim3(256), 0, s, order, (int)R, K);
+            SAT_LAUNCH_CHECK();
+        }
+        return SAT_OK;
+    }
+};
+
+// the workspace of a single-model decode: the search's buffers and the member's, as its plan sizes them
+static int64_t beam_decode_bytes(int B, int K, int E, int H, int V, int num_layers, int steps, bool ex) {
+    if (B <= 0 || K <= 0 || K > KMAX || E <= 0 || H <= 0 || V <= 0 || num_layers < 1 || steps < 1) return 0;
+    BeamMember m(sat_decoder_model{nullptr, nullptr, nullptr, num_layers, nullptr, nullptr, E, H});
+    m.plan(B, K, V, true);
+    return BeamSearch::bytes(B, K, steps, ex) + m.bytes();
+}
+
+extern "C" int64_t sat_beam_decode_ws_bytes(int B, int K, int E, int H, int V, int num_layers, int steps) {
+    return beam_decode_bytes(B, K, E, H, V, num_layers, steps, false);
+}
+extern "C" int64_t sat_beam_decode_ex_ws_bytes(int B, int K, int E, int H, int V, int num_layers, int steps) {
+    return beam_decode_bytes(B, K, E, H, V, num_layers, steps, true);
+}
+extern "C" int64_t sat_beam_decode_groups_ws_bytes(int B, int K, int E, int H, int V, int num_layers, int steps) {
+    return beam_decode_bytes(B, K, E, H, V, num_layers, steps, true);
+}
+
+// ONE driver for sat_beam_decode (ex false, c NULL), sat_beam_decode_ex and sat_beam_decode_groups: with constraints the row launch of
+// a step that bans something is the constrained kernel; with G > 1 groups the first slot of every group starts live and the merge
+// launch of every step is the grouped one; with a length penalty or with groups the rerank runs behind the backtrack
+static int beam_decode_impl(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
+                            const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
+                            int64_t end_id, bool ex, const sat_beam_constraints* c, int G, float lambda, int64_t* ids, float* scores_out,
+                            float* norm_scores, int32_t* order, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    if (!features || !embed || !lstm_w || !lin_w || !lin_b || !ids || !workspace) return SAT_ERR_ARG;
+    const int64_t need = beam_decode_bytes(B, K, E, H, V, num_layers, steps, ex);
+    BeamSearch search;
+    SAT_TRY(search.init(B, K, V, steps, end_id, c, G, lambda, ex, need > 0, !(E & 3)));
+    if (ws_bytes < need || (((uintptr_t)workspace) & 255)) return SAT_ERR_WORKSPACE;
+    for (int i = 0; i < 4 * num_layers; ++i)
+        if (!lstm_w[i]) return SAT_ERR_ARG;
+    if (num_layers > 8) return SAT_ERR_UNSUPPORTED;
+    BeamMember m(sat_decoder_model{features, embed, lstm_w, num_layers, lin_w, lin_b, E, H});
+    m.plan(B, K, V, true);
+    char* w = (char*)workspace;
+    search.carve(w);
+    m.carve(w);
+    SAT_TRY(m.setup(stream, search.Kg, search.sc[0]));
+    for (int i = 0; i < steps; ++i) {
+        SAT_TRY(m.forward(stream, i));
+        SAT_TRY(search.select(stream, m.logits, (long)m.ldl, i));
+        SAT_TRY(search.merge(stream, m.fused_move()));
+        m.after_fused_merge();
+        if (i + 1 < steps) SAT_TRY(m.gather(stream, search.par));      // (nothing reads the state behind the last selection)
+    }
+    return search.finish(stream, ids, scores_out, norm_scores, order);
+}
+
+extern "C" int sat_beam_decode(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
+                               const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
+                               int64_t end_id, int64_t* ids, float* scores_out, void* workspace, int64_t ws_bytes,
+                               sat_stream_t stream) {
+    return beam_decode_impl(features, embed, lstm_w, num_layers, lin_w, lin_b, B, K, E, H, V, steps, end_id, false, nullptr, 1, 0.0f, ids,
+                            scores_out, nullptr, nullptr, workspace, ws_bytes, stream);
+}
+
+extern "C" int sat_beam_decode_ex(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
+                                  const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
+                                  int64_t end_id, const sat_beam_constraints* c, int64_t* ids, float* scores_out, float* norm_scores,
+                                  int32_t* order, void* workspace, int64_t ws_bytes, sat_stream_t stream) {
+    return beam_decode_impl(features, embed, lstm_w, num_layers, lin_w, lin_b, B, K, E, H, V, steps, end_id, true, c, 1, 0.0f, ids,
+                            scores_out, norm_scores, order, workspace, ws_bytes, stream);
+}
+
+extern "C" int sat_beam_decode_groups(const float* features, const float* embed, const float* const* lstm_w, int num_layers,
+                                      const float* lin_w, const float* lin_b, int B, int K, int E, int H, int V, int steps,
+                                      int64_t end_id, const sat_beam_constraints* c, int num_groups, float diversity_penalty,
+                                      int64_t* ids, float* scores_out, float* norm_scores, int32_t* order, void* workspace,
+                                      int64_t ws_bytes, sat_stream_t stream) {
+    return beam_decode_impl(features, embed, lstm_w, num_layers, lin_w, lin_b, B, K, E, H, V, steps, end_id, true, c, num_groups,
+                            diversity_penalty, ids, scores_out, norm_scores, order, workspace, ws_bytes, stream);
+}
+
+// ---- the beam decode of an ENSEMBLE of DecoderRNN models as ONE call: M members in lock step.  Per step: every member's forward
+//      into its own [R][pad4(V)] matrix; ONE combine launch; the search's row and merge launches on the combined matrix; then every
+//      member moves its own rows by the step's records. ----
+static int64_t ensemble_bytes(const sat_decoder_model* models, int M, int B, int K, int V, int steps) {
+    int64_t n = al256((int64_t)B * K * ((V + 3) / 4 * 4) * 4) + BeamSearch::bytes(B, K, steps, true);      // the combined matrix, the search
+    for (int j = 0; j < M; ++j) {
+        BeamMember m(models[j]);
+        m.plan(B, K, V, false);
+        n += m.bytes();
+    }
+    return n;
+}
+
 extern "C" int64_t sat_beam_decode_ensemble_ws_bytes(const sat_decoder_model* models, int M, int B, int K, int V, int steps) {
     if (ensemble_models_check(models, M) != SAT_OK) return 0;
     if (B <= 0 || K <= 0 || K > KMAX || V <= 0 || steps < 1) return 0;
-    const int64_t R = (int64_t)B * K, ldl = (V + 3) / 4 * 4;
-    int64_t n = al256(R * ldl * 4) + 2 * al256(R * 4) + al256(sat_beam_step_ws_bytes(B, K)) + al256((int64_t)steps * R * 4) +
-                al256((int64_t)steps * R * 8) + beam_decode_ex_extra(R, steps);
-    for (int j = 0; j < M; ++j) n += ensemble_model_bytes(models[j], R, ldl, V);
-    return n;
+    return ensemble_bytes(models, M, B, K, V, steps);
 }
 
 extern "C" int sat_beam_decode_ensemble(const sat_decoder_model* models, int M, const float* weights, int mode, int B, int K, int V,
@@ -1427,190 +1493,36 @@ extern "C" int sat_beam_decode_ensemble(const sat_decoder_model* models, int M, 
     SAT_TRY(ensemble_weights(M, weights, mode, &ens));
     const int models_rc = ensemble_models_check(models, M);
     if (models_rc == SAT_ERR_ARG) return models_rc;
-    SAT_TRY(beam_groups_check(K, num_groups, diversity_penalty));
-    if (B <= 0 || K > KMAX || V <= 0 || steps < 1) return SAT_ERR_ARG;
-    const int G = num_groups, Kg = K / G;
-    const float lambda = diversity_penalty;
-    bool active = false;
-    SAT_TRY(beam_constraints_check(c, end_id, &active));
-    if (models_rc != SAT_OK || (long)K * V > INT_MAX - 1) return SAT_ERR_UNSUPPORTED;
-    if (active && (steps > kBanTMax || V > kBanVMax)) return SAT_ERR_UNSUPPORTED;
-    const bool rerank = (c && c->length_penalty > 0.0f) || G > 1;
-    const float c_length_penalty = c ? c->length_penalty : 0.0f;
-    if (!active) c = nullptr;
-    const int64_t need = sat_beam_decode_ensemble_ws_bytes(models, M, B, K, V, steps);
-    if (need <= 0) return SAT_ERR_ARG;
-    if (ws_bytes < need || (((uintptr_t)workspace) & 255)) return SAT_ERR_WORKSPACE;
+    BeamSearch search;
+    SAT_TRY(search.init(B, K, V, steps, end_id, c, num_groups, diversity_penalty, true, B > 0 && K <= KMAX && V > 0 && steps >= 1,
+                        models_rc == SAT_OK));
+    if (ws_bytes < ensemble_bytes(models, M, B, K, V, steps) || (((uintptr_t)workspace) & 255)) return SAT_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t R = (int64_t)B * K, ldl = (V + 3) / 4 * 4;
+    const int64_t R = search.R, ldl = (V + 3) / 4 * 4;
     char* w = (char*)workspace;
     float* comb = (float*)w; w += al256(R * ldl * 4);
-    float* sc[2];
-    sc[0] = (float*)w; w += al256(R * 4);
-    sc[1] = (float*)w; w += al256(R * 4);
-    float* cand_val = (float*)w; w += al256(sat_beam_step_ws_bytes(B, K));
-    int* cand_idx = (int*)(cand_val + (long)B * K * K);
-    int32_t* parents = (int32_t*)w; w += al256((int64_t)steps * R * 4);
-    int64_t* tokens = (int64_t*)w; w += al256((int64_t)steps * R * 8);
-    int64_t* ids_search = (int64_t*)w; w += al256(R * steps * 8);
-    float* sc_ranked = (float*)w; w += al256(R * 4);
-    float* norm_tmp = (float*)w; w += al256(R * 4);
-    int32_t* order_tmp = (int32_t*)w; w += al256(R * 4);
-    int* hist = (int*)w; w += al256(2 * R * kBanTMax * 4);
-    static const bool hist_env = [] { const char* v = getenv("SAT_BEAM_HISTORY"); return !(v && v[0] == '0'); }();
-    if (!(c && c->no_repeat_ngram >= 1 && hist_env)) hist = nullptr;
-    float *hc[kEnsMax], *logits[kEnsMax], *x0[kEnsMax] = {}, *xe[kEnsMax] = {};
-    float *xh[kEnsMax][2] = {}, *wcat[kEnsMax] = {}, *gates[kEnsMax] = {};      // the wide members' buffers
-    void* lin_split[kEnsMax] = {};
-    bool wide[kEnsMax] = {}, x3[kEnsMax] = {};
-    int ksplit[kEnsMax] = {}, xi[kEnsMax] = {};
-    for (int j = 0; j < M; ++j) {
-        const sat_decoder_model& d = models[j];
-        const int64_t ldx = d.E + d.H;
-        wide[j] = ensemble_wide(d, R);
-        x3[j] = ensemble_x3(d, R, V);
-        hc[j] = (float*)w; w += al256(4 * (int64_t)d.num_layers * R * d.H * 4);
-        logits[j] = (float*)w; w += al256(R * ldl * 4);
-        if (!wide[j]) {
-            x0[j] = (float*)w; w += al256(R * d.E * 4);
-            xe[j] = (float*)w; w += al256(R * d.E * 4);
-        } else {
-            xh[j][0] = (float*)w; w += al256(R * ldx * 4);
-            xh[j][1] = (float*)w; w += al256(R * ldx * 4);
-            wcat[j] = (float*)w; w += al256(4 * (int64_t)d.H * ldx * 4);
-            gates[j] = (float*)w; w += al256(kBeamKSplitMax * R * 4 * (int64_t)d.H * 4);
-            if (x3[j]) { lin_split[j] = w; w += al256(sat_gemm_f32x3_packed_bytes(V, d.H)); }
-            ksplit[j] = ensemble_ksplit(R, d.H, (long)ldx);
-        }
-        ens.x[j] = logits[j];
-    }
-    hipError_t e;
+    search.carve(w);
     if (ldl > V) {                                             // pad columns: read by nobody, but keep them defined
-        e = hipMemsetAsync(comb, 0, (size_t)(R * ldl * 4), s);
+        hipError_t e = hipMemsetAsync(comb, 0, (size_t)(R * ldl * 4), s);
         if (e != hipSuccess) return (int)e;
     }
+    BeamMember members[kEnsMax];
     for (int j = 0; j < M; ++j) {
-        const sat_decoder_model& d = models[j];
-        e = hipMemsetAsync(hc[j], 0, (size_t)(4 * (int64_t)d.num_layers * R * d.H * 4), s);       // h = c = 0
-        if (e != hipSuccess) return (int)e;
-        if (ldl > V) {
-            e = hipMemsetAsync(logits[j], 0, (size_t)(R * ldl * 4), s);
-            if (e != hipSuccess) return (int)e;
-        }
-        const long ldx = d.E + d.H;
-        if (wide[j]) {
-            if (x3[j]) SAT_TRY(sat_gemm_f32x3_pack(d.lin_w, V, d.H, lin_split[j], stream));
-            e = hipMemsetAsync(xh[j][0], 0, (size_t)(R * ldx * 4), s);                            // h_{-1} = 0
-            if (e != hipSuccess) return (int)e;
-            const long wtotal = 4L * d.H * ldx;
-            int wgrid = sat_cdiv(wtotal, 256);
-            if (wgrid > 2048) wgrid = 2048;
-            hipLaunchKernelGGL(beam_wcat_kernel, dim3(wgrid), dim3(256), 0, s, d.lstm_w[0], d.lstm_w[1], d.E, d.H, wtotal, wcat[j]);
-            SAT_LAUNCH_CHECK();
-        }
-        const long total = R * d.E;
-        int grid = sat_cdiv(total, 256);
-        if (grid > 2048) grid = 2048;
-        if ((long)grid * 256 < R) grid = sat_cdiv(R, 256);
-        hipLaunchKernelGGL(beam_init_kernel, dim3(grid), dim3(256), 0, s, d.features, K, d.E, total, wide[j] ? xh[j][0] : x0[j],
-                           wide[j] ? ldx : (long)d.E, sc[0], (int)R, Kg);
-        SAT_LAUNCH_CHECK();                                    // (every model writes the same start scores)
+        BeamMember& m = members[j] = BeamMember(models[j]);
+        m.plan(B, K, V, false);
+        m.carve(w);
+        SAT_TRY(m.setup(stream, search.Kg, search.sc[0]));
+        ens.x[j] = m.logits;
     }
-    int cur_h[kEnsMax][8] = {}, cur_c[kEnsMax][8] = {};        // which of the two buffers holds a layer's live h / c
-    int si = 0;
     for (int i = 0; i < steps; ++i) {
-        for (int j = 0; j < M; ++j) {
-            const sat_decoder_model& d = models[j];
-            const float* inp = i == 0 ? x0[j] : xe[j];
-            if (wide[j]) {
-                const long ldx = d.E + d.H;
-                float* cc = hc[j] + (long)(2 + cur_c[j][0]) * R * d.H;
-                float* h_new = hc[j];
-                SAT_TRY(sat_gemm_f32_splitk(0, 0, xh[j][xi[j]], ldx, wcat[j], ldx, gates[j], 4L * d.H, d.lstm_w[2], d.lstm_w[3], (int)R,
-                                            4 * d.H, (int)ldx, ksplit[j], R * 4L * d.H, stream));
-                const long total = R * d.H;
-                int grid = sat_cdiv(total, 256);
-                if (grid > 2048) grid = 2048;
-                hipLaunchKernelGGL(beam_lstm_point_kernel, dim3(grid), dim3(256), 0, s, gates[j], cc, h_new, d.H, total, ksplit[j],
-                                   R * 4L * d.H);
-                SAT_LAUNCH_CHECK();
-                if (x3[j]) SAT_TRY(sat_gemm_f32x3(h_new, d.H, lin_split[j], d.lin_b, logits[j], ldl, (int)R, V, d.H, stream));
-                else SAT_TRY(sat_vocab_logits_fwd(h_new, d.lin_w, d.lin_b, (int)R, d.H, V, logits[j], ldl, stream));
-                continue;
-            }
-            for (int l = 0; l < d.num_layers; ++l) {
-                float* base = hc[j] + (long)l * 4 * R * d.H;
-                float* h_in = base + (long)cur_h[j][l] * R * d.H;
-                float* h_out = base + (long)(1 - cur_h[j][l]) * R * d.H;
-                float* cc = base + (long)(2 + cur_c[j][l]) * R * d.H;
-                SAT_TRY(sat_lstm_step(inp, h_in, cc, d.lstm_w[4 * l], d.lstm_w[4 * l + 1], d.lstm_w[4 * l + 2], d.lstm_w[4 * l + 3], (int)R,
-                                      l == 0 ? d.E : d.H, d.H, h_out, stream));
-                cur_h[j][l] = 1 - cur_h[j][l];
-                inp = h_out;
-            }
-            SAT_TRY(sat_vocab_logits_fwd(inp, d.lin_w, d.lin_b, (int)R, d.H, V, logits[j], ldl, stream));
-        }
+        for (int j = 0; j < M; ++j) SAT_TRY(members[j].forward(stream, i));
         ensemble_launch(s, ens, M, (long)ldl, mode, (int)R, V, comb, (long)ldl);
         SAT_LAUNCH_CHECK();
-        int32_t* par = parents + (long)i * R;
-        int64_t* tok = tokens + (long)i * R;
-        const int64_t* last = (i > 0 && end_id >= 0) ? tok - R : (const int64_t*)nullptr;
-        beam_row_launch(s, comb, (long)ldl, sc[si], last, (long)end_id, (int)R, K, V, cand_val, cand_idx, c, parents, tokens, i, hist);
-        SAT_LAUNCH_CHECK();
-        beam_merge_launch(s, B, cand_val, cand_idx, K, V, Kg, lambda, last, (long)end_id, par, tok, sc[1 - si], nullptr, 0, nullptr, 0L,
-                          nullptr, nullptr, 0, nullptr, 0L, nullptr);
-        SAT_LAUNCH_CHECK();
-        si = 1 - si;
+        SAT_TRY(search.select(stream, comb, (long)ldl, i));
+        SAT_TRY(search.merge(stream, BeamMove{}));
         if (i + 1 == steps) break;                             // nothing reads the state behind the last selection
-        for (int j = 0; j < M; ++j) {
-            const sat_decoder_model& d = models[j];
-            if (wide[j]) {                                     // embedding rows and (h, c) by parent in ONE launch, h into the next [x | h]
-                const long ldx = d.E + d.H;
-                float* xn = xh[j][1 - xi[j]];
-                hipLaunchKernelGGL(ensemble_move_rows_kernel, dim3(B), dim3(256), 0, s, (const int*)par, (const int64_t*)tok, K, d.embed, d.E,
-                                   xn, ldx, (const float*)hc[j], (const float*)(hc[j] + (long)(2 + cur_c[j][0]) * R * d.H), d.H, xn + d.E, ldx,
-                                   hc[j] + (long)(2 + 1 - cur_c[j][0]) * R * d.H);
-                SAT_LAUNCH_CHECK();
-                cur_c[j][0] = 1 - cur_c[j][0];
-                xi[j] = 1 - xi[j];
-                continue;
-            }
-            SAT_TRY(sat_embed_rows(d.embed, tok, 1, (int)R, d.E, V, xe[j], stream));
-            for (int l = 0; l < d.num_layers && K > 1; ++l) {
-                float* base = hc[j] + (long)l * 4 * R * d.H;
-                const long total = R * d.H;
-                int grid = sat_cdiv(2 * total, 256);
-                if (grid > 2048) grid = 2048;
-                hipLaunchKernelGGL(beam_gather2_kernel, dim3(grid), dim3(256), 0, s, base + (long)cur_h[j][l] * R * d.H,
-                                   base + (long)(2 + cur_c[j][l]) * R * d.H, par, K, d.H, total, base + (long)(1 - cur_h[j][l]) * R * d.H,
-                                   (long)d.H, base + (long)(2 + 1 - cur_c[j][l]) * R * d.H);
-                SAT_LAUNCH_CHECK();
-                cur_h[j][l] = 1 - cur_h[j][l];
-                cur_c[j][l] = 1 - cur_c[j][l];
-            }
-        }
+        for (int j = 0; j < M; ++j) SAT_TRY(members[j].move_rows(stream, search.par, search.tok));
     }
-    hipLaunchKernelGGL(beam_backtrack_kernel, dim3(sat_cdiv(R, 256)), dim3(256), 0, s, parents, tokens, steps, (int)R, K,
-                       rerank ? ids_search : ids);
-    SAT_LAUNCH_CHECK();
-    if (rerank) {
-        hipLaunchKernelGGL(beam_rerank_kernel, dim3(B), dim3(64), 0, s, (const int64_t*)ids_search, (const float*)sc[si], K, steps, end_id,
-                           c_length_penalty, ids, scores_out ? scores_out : sc_ranked, norm_scores ? norm_scores : norm_tmp,
-                           order ? order : order_tmp);
-        SAT_LAUNCH_CHECK();
-        return SAT_OK;
-    }
-    if (scores_out) {
-        e = hipMemcpyAsync(scores_out, sc[si], (size_t)(R * 4), hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (norm_scores) {
-        e = hipMemcpyAsync(norm_scores, sc[si], (size_t)(R * 4), hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (order) {
-        hipLaunchKernelGGL(beam_iota_kernel, dim3(sat_cdiv(R, 256)), dim3(256), 0, s, order, (int)R, K);
-        SAT_LAUNCH_CHECK();
-    }
-    return SAT_OK;
+    return search.finish(stream, ids, scores_out, norm_scores, order);
 }
+
