@@ -19,9 +19,7 @@ from . import _lib as L
 from .criterion import MAX_UL_STEPS, _check_smoothing, _check_unlikelihood
 from .decoder import LSTMWorkspaces, VocabCE, decoder_backward, decoder_forward, rollout_forward
 from .models import ShowAndTell, draw_ss_seed, fc_bn1d_backward, fc_bn1d_forward
-from .optim import (AVERAGED_NOTE, check_accumulate_weight, check_ema_decay, check_ema_entry, check_ema_warmup, check_max_norm,
-                    check_weight_decay, ema_decay_at, ema_entry, ema_update, exempt_array, grad_accumulate, group_weight_decay,
-                    merge_ranges, swapped_in)
+from .optim import AVERAGED_NOTE, FlatAdam, check_accumulate_weight, check_max_norm, delegated, grad_accumulate, is_number
 from .pack import PackInfo
 from .scst import SelfCritical, ce_rows_weighted, check_group, group_sum_rows, scst_weights, scst_weights_group
 from .watch import ResidencyWatch, StatusRing
@@ -50,9 +48,13 @@ def ss_prob_for_epoch(epoch, start=-1, increase_every=5, increase_prob=0.05, max
     return 0.0
 
 
-class FlatParams:
-    """Trainable parameters re-homed into one flat f32 buffer, in gradient-completion order:
-    bucket 0 = vocab projection, bucket 1 = LSTM (top layer first), bucket 2 = encoder head + embedding."""
+class FlatParams(FlatAdam):
+    """The `FlatAdam` of a ShowAndTell model: the trainable parameters re-homed into its flat buffer in gradient-completion order
+    (bucket 0 = vocab projection, bucket 1 = LSTM (top layer first), bucket 2 = encoder head + embedding), `slices` by name, the
+    loss / fault slots behind the gradients, and `acc`, the accumulated twin of `grads`.  `names` / `layout` / `tensors` are in the
+    order train.py:55 hands the parameters to optim.Adam (model.parameters() with requires_grad): the order of a state dict."""
+
+    WORDS = ("max_grad_norm", "model has %d trainable", "load_optimizer_state_dict()")
 
     def __init__(self, model):
         dec, enc = model.decoder, model.encoder
@@ -63,7 +65,6 @@ class FlatParams:
         groups[2] = [("encoder.resnet.fc.weight", enc.resnet.fc.weight), ("encoder.resnet.fc.bias", enc.resnet.fc.bias),
                      ("encoder.bn.weight", enc.bn.weight), ("encoder.bn.bias", enc.bn.bias),
                      ("decoder.embed.weight", dec.embed.weight)]
-        dev = dec.linear.weight.device
         self.slices, self.buckets = {}, []
         off = 0
         for g in groups:
@@ -72,23 +73,16 @@ class FlatParams:
                 self.slices[name] = (off, p.numel(), tuple(p.shape))
                 off += L.pad4(p.numel())
             self.buckets.append((start, off))
-        self.n = off
         # 4 trailing floats: slot 0 carries this rank's loss term through the last bucket's all-reduce, slot 1 the step's fault
         # flag (TrainStep._fault_flag: non-zero on EVERY rank after the reduction when any rank's persistent LSTM launch gave up)
         self.loss_slot = off
         self.buckets[-1] = (self.buckets[-1][0], off + 4)
-        self.params = torch.zeros(off, device=dev)
-        self.grads = torch.zeros(off + 4, device=dev)
-        self.m = torch.zeros(off, device=dev)
-        self.v = torch.zeros(off, device=dev)
-        self.ema = None          # the averaged weights, a twin of `params`: made when TrainStep.ema_decay first becomes non-zero
+        named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+        assert {n for n, _ in named} == set(self.slices), "the trainable parameters are those of the three buckets"
+        super().__init__([self.slices[n] for n, _ in named], dec.linear.weight.device, tail=4)
+        self.names = [n for n, _ in named]
         self.acc = None          # the accumulated gradient, a twin of `grads` (4 B/param): made by the first TrainStep.accumulate()
-        for g in groups:
-            for name, p in g:
-                o, n, shape = self.slices[name]
-                self.params[o:o + n].copy_(p.data.reshape(-1))
-                p.data = self.params[o:o + n].view(shape)
-                p.grad = self.grads[o:o + n].view(shape)
+        self.rehome([p for _, p in named])
 
     def grad(self, name):
         o, n, shape = self.slices[name]
@@ -118,19 +112,18 @@ class TrainStep:
         if not isinstance(model, ShowAndTell):
             raise TypeError("TrainStep drives a ShowAndTell model")
         L.require_gpu(model.decoder.linear.weight, "model")
-        self.lib = L.load()
+        lib = L.load()                       # (before the parameters are re-homed: a missing library leaves the model as it was)
         self.model = model
         self.flat = FlatParams(model)
+        self.lib = lib
         self.lr, self.grad_clip, self.betas, self.eps = lr, grad_clip, betas, eps
         self.label_smoothing = label_smoothing
         self.last_nll = self.last_ul = None
-        self.step_count = 0
         self.buckets = self.flat.buckets
         self.flat_grad = self.flat.grads
         self._bufs = {}
         # "bf16": vocab projection + its gradient GEMMs on the bf16 matrix pipe (the throughput mode); "f32": exact-f32 MFMA
         self.decoder_gemm_dtype = "bf16" if (_DECODER_BF16 and model.encoder.compute_dtype == "bf16") else "f32"
-        self._params_list = [p for _, p in self._trainable()]
         # sticky device-side fault word of this engine (sat_step_fault_flag): set by a step whose persistent LSTM recurrence gave
         # up, cleared by the host once it has raised for it; while it is set every clamp + Adam launch drops its update
         self._fault_sticky = torch.zeros(1, device=self.flat.params.device)
@@ -157,36 +150,28 @@ class TrainStep:
     def unlikelihood(self, value):
         self._unlikelihood = _check_unlikelihood(value)
 
-    # -- global-norm clipping and decoupled weight decay (attributes, not constructor arguments) ---------------------------------
-    # max_grad_norm: torch.nn.utils.clip_grad_norm_'s max_norm over the whole flat gradient (after the bucket all-reduces in a
-    #   data-parallel step, after the elementwise clamp when grad_clip is set); 0.0 = off, float("inf") = measure only.
-    # weight_decay: torch.optim.AdamW's (p *= 1 - lr * weight_decay in front of the Adam arithmetic); 0.0 = off.
-    # no_decay: NAMES from `flat.slices` that do not decay (`no_decay_names(model)`: biases, BatchNorm weight / bias); None decays
-    #   every parameter, which is what torch does with one param group.
-    # last_grad_norm: 2-element f64 DEVICE tensor {norm, number of Inf / NaN gradient elements} of the last step with max_grad_norm
-    #   set, None before.  A step with a non-finite gradient is dropped on the device with no host read, like a faulted one:
-    #   parameters, moments and gradient stay what they were.  step_count still advances -- the bias correction of the following
-    #   steps sees one step more -- and `last_grad_norm[1] > 0`, read whenever the loop likes, is how it finds out.
-    # With max_grad_norm and weight_decay both off `optimizer_step` makes exactly the call it makes without them.
-    _max_grad_norm, _weight_decay, _no_decay, _exempt = 0.0, 0.0, None, None
-    last_grad_norm = None
+    # -- the optimizer: `flat` (a `FlatAdam`: its docstring has the launch sequence and the drop rules) holds the state and these -----
+    # settings, attributes here, not constructor arguments.  What is TrainStep's own:
+    # max_grad_norm: `flat.max_norm` with 0.0 for "off"; taken over the whole flat gradient after the bucket all-reduces of a
+    #   data-parallel step.  no_decay: NAMES from `flat.slices` that do not decay (`no_decay_names(model)`: biases, BatchNorm weight /
+    #   bias); None decays every parameter, which is what torch does with one param group.
+    # The skip word of every update is the step's fault word, so a faulted step moves neither parameters nor moments nor the
+    #   average; its step_count is rolled back (`_on_fault`), and the EMA warm-up schedule follows the rollback.  `scst_step` and
+    #   `DataParallelStep` come through `optimizer_step`; every rank computes the same bits from the same parameters, so the
+    #   average is not exchanged.
+    lib, lr, betas, eps, grad_clip = (delegated(k, "flat") for k in ("lib", "lr", "betas", "eps", "clip"))
+    step_count, last_grad_norm, weight_decay = (delegated(k, "flat") for k in ("step_count", "last_grad_norm", "weight_decay"))
+    ema_decay, ema_warmup, _averaged = (delegated(k, "flat") for k in ("ema_decay", "ema_warmup", "averaged"))
+    _exempt, _params_list = delegated("exempt", "flat"), delegated("tensors", "flat")
+    _no_decay = None
 
     @property
     def max_grad_norm(self):
-        return self._max_grad_norm
+        return self.flat.max_norm or 0.0
 
     @max_grad_norm.setter
     def max_grad_norm(self, value):
-        off = not isinstance(value, bool) and isinstance(value, (int, float)) and value == 0
-        self._max_grad_norm = 0.0 if off else check_max_norm(value, "max_grad_norm")
-
-    @property
-    def weight_decay(self):
-        return self._weight_decay
-
-    @weight_decay.setter
-    def weight_decay(self, value):
-        self._weight_decay = check_weight_decay(value)
+        self.flat.max_norm = None if (is_number(value) and value == 0) else check_max_norm(value, "max_grad_norm")
 
     @property
     def no_decay(self):
@@ -200,63 +185,16 @@ class TrainStep:
             names = tuple(names)
             if not all(isinstance(n, str) for n in names):
                 raise ValueError("no_decay takes parameter NAMES (an iterable of str), or None")
-        # an engine made without __init__ has no flat buffer yet: the names are then checked by the first optimizer_step
-        exempt = self._ranges_of(names) if getattr(self, "flat", None) is not None else None
-        self._no_decay, self._exempt = names, exempt
-
-    def _ranges_of(self, names):
-        """the flat buffer's ranges of `names`, merged and checked against the kernel's table (ValueError)"""
         slices = self.flat.slices
         unknown = [n for n in names or () if n not in slices]
         if unknown:
             raise ValueError("no_decay: %s are not parameters of the flat buffer (%s)" % (unknown, sorted(slices)))
-        return merge_ranges([(slices[n][0], slices[n][0] + slices[n][1]) for n in set(names or ())])
-
-    # -- averaged weights (Polyak / exponential moving average of the trained parameters; attributes, not constructor arguments) --
-    # ema_decay: 0.0 = off, otherwise a float in (0, 1).  `flat.ema` is None until the attribute first becomes non-zero; it then
-    #   starts as a copy of `flat.params` (`reset_ema()` copies again), and every `optimizer_step` launches sat_ema_update behind the
-    #   update on the same stream: ema += (1 - d) (params - ema), d = `ema_decay_at(ema_decay, step_count, ema_warmup)`.  The launch
-    #   reads the step's fault word and, with max_grad_norm set, `last_grad_norm`: an update dropped on the device for a fault or a
-    #   non-finite gradient does not move the average either, and nothing is read back.  Setting 0 again stops the updates and
-    #   keeps the buffer.  `scst_step` and `DataParallelStep` come through `optimizer_step`; every rank computes the same bits
-    #   from the same parameters, so nothing is exchanged.  With 0 `optimizer_step` makes exactly the calls it makes without it.
-    # ema_warmup (bool): the decay of step t is min(ema_decay, (1 + t) / (10 + t)), t = `step_count` after this step's increment --
-    #   which a fault rolls back, so the schedule follows the rollback.
-    _ema_decay, _ema_warmup, _averaged = 0.0, False, False
-
-    @property
-    def ema_decay(self):
-        return self._ema_decay
-
-    @ema_decay.setter
-    def ema_decay(self, value):
-        self._ema_decay = check_ema_decay(value)
-        # an engine made without __init__ has no flat buffer yet: the first optimizer_step then copies, before its update
-        if self._ema_decay > 0 and getattr(self, "flat", None) is not None:
-            self._start_ema()
-
-    @property
-    def ema_warmup(self):
-        return self._ema_warmup
-
-    @ema_warmup.setter
-    def ema_warmup(self, value):
-        self._ema_warmup = check_ema_warmup(value)
-
-    def _ema(self):
-        return getattr(self.flat, "ema", None)
-
-    def _start_ema(self):
-        if self._ema() is None:
-            self.flat.ema = self.flat.params.clone()
+        self.flat.set_exempt([slices[n] for n in set(names or ())])
+        self._no_decay = names
 
     def reset_ema(self):
         """the average starts again from the parameters as they are now"""
-        if self._ema() is None:
-            raise RuntimeError("reset_ema(): no average is kept (ema_decay has never been set)")
-        if self._averaged:
-            raise RuntimeError(AVERAGED_NOTE % "reset_ema()")
-        self.flat.ema.copy_(self.flat.params)
+        self.flat.reset_ema()
 
     def averaged_weights(self):
         """`with step.averaged_weights():` -- `flat.params` and `flat.ema` change places (sat_swap_f32, in place, no third buffer)
@@ -265,19 +203,15 @@ class TrainStep:
         averaged weights.  On the way out (also by an exception) they change places again.  Inside the block `optimizer_step`,
         `step`, `scst_step`, `forward_backward` and a nested entry raise RuntimeError; so does the entry when no average is kept.
         BatchNorm running statistics and the frozen stack are the live model's: they are not averaged."""
-        return swapped_in(self, self.flat.params, self._ema(), self.flat.n, self._params_list)
+        return self.flat.averaged_weights(self)
 
     def averaged_state_dict(self):
         """`model.state_dict()` with the trainable entries taken from the average and everything else -- the frozen conv weights,
         every BatchNorm buffer, num_batches_tracked -- cloned from the live model: what to save as `model-best.pth`.  It loads into
         a fresh ShowAndTell, and so into a member of `sat.Ensemble`."""
-        if self._ema() is None:
-            raise RuntimeError("averaged_state_dict(): no average is kept (ema_decay has never been set)")
-        src = self.flat.params if self._averaged else self.flat.ema       # (inside averaged_weights() they have changed places)
+        averages = self.flat.views(self.flat.averages("averaged_state_dict()"))
         sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        for name, _ in self._trainable():
-            o, n, shape = self.flat.slices[name]
-            sd[name] = src[o:o + n].view(shape).clone()
+        sd.update((name, t.clone()) for name, t in zip(self.flat.names, averages))
         return sd
 
     # -- gradient accumulation: K backwards, ONE update ------------------------------------------------------------------------
@@ -305,7 +239,7 @@ class TrainStep:
             raise RuntimeError(AVERAGED_NOTE % "accumulate()")
         weight = check_accumulate_weight(weight)
         f = self.flat
-        if getattr(f, "acc", None) is None:
+        if f.acc is None:
             f.acc = torch.zeros_like(f.grads)
         grad_accumulate(self.lib, f.acc, f.grads, f.n, weight, first=self._accumulated == 0)
         self._accumulated += 1
@@ -318,7 +252,7 @@ class TrainStep:
     @property
     def acc_grad(self):
         """`flat.acc` (None before the first fold): what a data-parallel step all-reduces bucket by bucket"""
-        return getattr(self.flat, "acc", None)
+        return self.flat.acc
 
     # -- encoder look-ahead ---------------------------------------------------------------------------
     def prefetch_encoder(self, images):
@@ -614,121 +548,37 @@ class TrainStep:
         every later one until the host has seen the flag (sticky), raised RuntimeError (at the latest on the next submit;
         `check_ids()` at once) and rolled the step count back.  fixed_lag (data-parallel steps): look at the flag of the step
         submitted `fixed_lag` steps ago, blocking, instead of polling (`_watch_fixed_lag`)."""
-        if self._averaged:
-            raise RuntimeError(AVERAGED_NOTE % "optimizer_step()")
-        before = self.step_count
-        self.step_count += 1
         f = self.flat
+        if f.averaged:
+            raise RuntimeError(AVERAGED_NOTE % "optimizer_step()")
+        before = f.step_count
         # an open accumulation: the same sequence on `flat.acc` and ITS fault word (the OR over the micro-batches), closed here
         grads, fault_slot = f.grads, self.fault_slot
         if self._accumulated > 0:
             grads, fault_slot = f.acc, f.acc[f.loss_slot + 1:f.loss_slot + 2]
             self._accumulated = 0
-        if self._ema_decay > 0:
-            self._start_ema()                # (only an engine that had no flat buffer when the attribute was set copies here)
-        if self._max_grad_norm == 0 and self._weight_decay == 0:
-            L.check(self.lib.sat_clamp_adam_step_guarded(L.ptr(f.params), L.ptr(grads), L.ptr(f.m), L.ptr(f.v), f.n,
-                                                         float(self.lr if lr is None else lr), self.betas[0], self.betas[1],
-                                                         self.eps, float(self.grad_clip), self.step_count, L.ptr(fault_slot),
-                                                         L.stream()), "sat_clamp_adam_step_guarded")
-        else:
-            self._adamw_step(float(self.lr if lr is None else lr), grads, fault_slot)
-        if self._ema_decay > 0:
-            # behind the update on its stream, behind the same two words: the fault slot (neither update kernel writes it: it lies
-            # past the n elements they cover) and, with a norm, the {norm, non-finite} pair sat_adamw_step has just written
-            ema_update(self.lib, f.ema, f.params, f.n, ema_decay_at(self._ema_decay, self.step_count, self._ema_warmup),
-                       skip=fault_slot, norm_state=self.last_grad_norm if self._max_grad_norm > 0 else None)
-        torch.autograd.graph.increment_version(self._params_list)     # written through raw pointers: bump `_version` like torch would
+        f.update(grads, None, fault_slot, lr)       # (no update kernel writes the fault word: it lies past the n elements they cover)
         if fixed_lag is not None:
             self._watch_fixed_lag(before, int(fixed_lag), fault_slot)
             return
         ResidencyWatch.get(f.params.device).submit(fault_slot.view(torch.int32), "a persistent LSTM recurrence of a training step",
                                                    lambda: self._on_fault(before), note=self.FAULT_NOTE)
 
-    def _adamw_step(self, lr, grads, fault_slot):
-        """the update with a global norm and / or weight decay: the sum of squares over the n parameter gradients -- the loss and
-        fault slots behind them are no gradients and stay out --, then sat_adamw_step behind the same fault word; it drops the
-        update by itself when the gradient holds an Inf or NaN (see `last_grad_norm`).  grads, fault_slot: `flat.grads` and the
-        step's word, or `flat.acc` and its word"""
-        f, lib, st = self.flat, self.lib, L.stream()
-        if self._exempt is None:
-            self._exempt = self._ranges_of(self._no_decay)
-        partials, count, norm_out = None, 0, None
-        if self._max_grad_norm > 0:
-            if getattr(self, "_norm_ws", None) is None:
-                self._norm_ws = torch.empty(lib.sat_grad_sumsq_ws_bytes(f.n) // 8, dtype=torch.float64, device=f.params.device)
-                self.last_grad_norm = torch.zeros(2, dtype=torch.float64, device=f.params.device)
-            partials, count, norm_out = L.ptr(self._norm_ws), lib.sat_grad_sumsq_partials(f.n), L.ptr(self.last_grad_norm)
-            L.check(lib.sat_grad_sumsq(L.ptr(grads), f.n, float(self.grad_clip), partials, 0, count, st), "sat_grad_sumsq")
-        ex, nex = exempt_array(self._exempt) if self._weight_decay > 0 else (None, 0)
-        L.check(lib.sat_adamw_step(L.ptr(f.params), L.ptr(grads), L.ptr(f.m), L.ptr(f.v), f.n, lr, self.betas[0], self.betas[1],
-                                   self.eps, float(self.grad_clip), self.step_count, self._weight_decay, ex, nex,
-                                   self._max_grad_norm, partials, count, norm_out, L.ptr(fault_slot), st), "sat_adamw_step")
-
     # -- optimizer checkpoint interchange (SURVEY 8f.4; the reference's load_optimizer is an empty stub, ------
     #    train.py:60-64, and only model.state_dict() is saved, train.py:191-193) ---------------------------
     def _trainable(self):
         """(name, param) in the order train.py:55 hands them to optim.Adam: model.parameters() with requires_grad"""
-        return [(n, p) for n, p in self.model.named_parameters() if p.requires_grad]
+        return list(zip(self.flat.names, self.flat.tensors))
 
     def optimizer_state_dict(self):
         """The flat Adam state in `torch.optim.Adam.state_dict()` layout (loads into a torch Adam built over
-        `filter(requires_grad, model.parameters())` and back)."""
-        f, state, names = self.flat, {}, []
-        for i, (name, p) in enumerate(self._trainable()):
-            o, n, shape = f.slices[name]
-            names.append(name)
-            if self.step_count > 0:
-                state[i] = {"step": torch.tensor(float(self.step_count)),
-                            "exp_avg": f.m[o:o + n].view(shape).clone(),
-                            "exp_avg_sq": f.v[o:o + n].view(shape).clone()}
-        wd = self._weight_decay
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": wd if wd > 0 else 0, "amsgrad": False,
-                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-                 "decoupled_weight_decay": wd > 0, "params": list(range(len(names)))}
-        sd = {"state": state, "param_groups": [group], "param_names": names, "grad_clip": self.grad_clip,
-              "max_grad_norm": self._max_grad_norm}
-        if getattr(f, "ema", None) is not None:      # the averaged weights, one tensor per parameter in `param_names` order
-            src = f.params if self._averaged else f.ema
-            sd["ema"] = ema_entry(self._ema_decay, self._ema_warmup,
-                                  [src[f.slices[n][0]:f.slices[n][0] + f.slices[n][1]].view(f.slices[n][2]).clone() for n in names])
+        `filter(requires_grad, model.parameters())` and back), with "param_names" and 0.0 for no "max_grad_norm"."""
+        sd = self.flat.state_dict(self.flat.names)
+        sd["max_grad_norm"] = self.max_grad_norm
         return sd
 
     def load_optimizer_state_dict(self, sd):
-        f, trainable = self.flat, self._trainable()
-        group = sd["param_groups"][0]
-        if len(group["params"]) != len(trainable):
-            raise ValueError("optimizer state has %d parameters, model has %d trainable"
-                             % (len(group["params"]), len(trainable)))
-        self.lr, self.betas, self.eps = float(group["lr"]), tuple(group["betas"]), float(group["eps"])
-        self.weight_decay = group_weight_decay(group)
-        if "max_grad_norm" in sd:
-            self.max_grad_norm = 0.0 if sd["max_grad_norm"] is None else sd["max_grad_norm"]     # (None: FusedClampAdam's "off")
-        if "ema" in sd:                              # (absent: the averaging state stays what it is)
-            if self._averaged:
-                raise RuntimeError(AVERAGED_NOTE % "load_optimizer_state_dict() with averaged weights")
-            decay, warmup, tensors = check_ema_entry(sd["ema"], [f.slices[name][2] for name, _ in trainable])
-            self._start_ema()
-            for t, (name, _) in zip(tensors, trainable):
-                o, n, _ = f.slices[name]
-                f.ema[o:o + n].copy_(t.reshape(-1))
-            self._ema_decay, self._ema_warmup = decay, warmup
-        steps = set()
-        f.m.zero_()
-        f.v.zero_()
-        for i, (name, p) in enumerate(trainable):
-            st = sd["state"].get(group["params"][i])
-            if st is None:
-                continue
-            o, n, shape = f.slices[name]
-            if tuple(st["exp_avg"].shape) != shape:
-                raise ValueError("optimizer state of %s has shape %s, expected %s" % (name, tuple(st["exp_avg"].shape), shape))
-            f.m[o:o + n].copy_(st["exp_avg"].reshape(-1))
-            f.v[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
-            steps.add(int(st["step"]))
-        if len(steps) > 1:
-            raise ValueError("per-parameter Adam step counts differ (%s): one flat step count is kept" % sorted(steps))
-        self.step_count = steps.pop() if steps else 0
+        self.flat.load_state_dict(sd, self.flat.names)
 
     # -- single-GPU convenience ----------------------------------------------------------------------
     def step(self, images, captions, lengths, lr=None, next_images=None):

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import ema_reference as E
+from flat_adam_host import bare
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sat = importlib.import_module("show-and-tell_amd")
@@ -121,7 +122,7 @@ def test_ema_decay_at():
 
 @pytest.mark.parametrize("cls", [sat.TrainStep, sat.FusedClampAdam], ids=["TrainStep", "FusedClampAdam"])
 def test_attributes_refuse_and_default(cls):
-    obj = object.__new__(cls)
+    obj = bare(cls)
     assert obj.ema_decay == 0.0 and obj.ema_warmup is False
     for bad in (True, False, NAN, 1.0, 1, -0.1, 1.5, INF, -INF, "0.9", None, [0.9]):
         with pytest.raises(ValueError, match="ema_decay"):
@@ -130,7 +131,7 @@ def test_attributes_refuse_and_default(cls):
         with pytest.raises(ValueError, match="ema_warmup"):
             obj.ema_warmup = bad
     assert obj.ema_decay == 0.0 and obj.ema_warmup is False, "a refused value changes nothing"
-    obj.ema_decay, obj.ema_warmup = 0.999, True             # no buffers yet: the first step copies
+    obj.ema_decay, obj.ema_warmup = 0.999, True             # (copies the host buffer)
     assert obj.ema_decay == 0.999 and obj.ema_warmup is True
     obj.ema_decay = 0
     assert obj.ema_decay == 0.0 and isinstance(obj.ema_decay, float)
@@ -142,7 +143,7 @@ def test_without_an_average_the_entry_points_raise():
     for call in (ts.reset_ema, ts.averaged_state_dict, lambda: ts.averaged_weights().__enter__()):
         with pytest.raises(RuntimeError, match="ema_decay has never been set"):
             call()
-    opt = object.__new__(sat.FusedClampAdam)
+    opt = bare(sat.FusedClampAdam)
     for call in (opt.reset_ema, opt.ema_params):
         with pytest.raises(RuntimeError, match="ema_decay has never been set"):
             call()
@@ -158,21 +159,10 @@ def test_constructor_signatures_are_unchanged():
 # ---------------------------------------------------------------------------------------------- 6. state dicts, feature off
 
 def host_engine():
-    """the flat engine without a device, as test_optim_host.py builds it"""
-    ts = object.__new__(sat.TrainStep)
-    w, b = torch.nn.Parameter(torch.randn(2, 3)), torch.nn.Parameter(torch.randn(3))
-
-    class Flat:
-        slices = {"w": (0, 6, (2, 3)), "b": (8, 3, (3,))}
-        m, v, params = torch.rand(12), torch.rand(12), torch.rand(12)
-        n = 12
-
-    class Model:
-        @staticmethod
-        def named_parameters():
-            return [("w", w), ("b", b)]
-
-    ts.flat, ts.model = Flat(), Model()
+    """the flat engine without a device, as test_optim_host.py builds it: parameters w [2, 3] at 0 and b [3] at 8 of 12 floats"""
+    ts = bare(sat.TrainStep)
+    for t in (ts.flat.m, ts.flat.v, ts.flat.params):
+        t.copy_(torch.rand(12))
     ts.lr, ts.grad_clip, ts.betas, ts.eps, ts.step_count = 1e-3, 0.1, (0.9, 0.999), 1e-8, 3
     return ts
 

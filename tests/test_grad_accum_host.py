@@ -15,6 +15,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 import grad_accum_reference as A
+from flat_adam_host import bare
 from oracle import decoder as OD
 from oracle import train_step as OT
 
@@ -88,7 +89,7 @@ def test_argument_errors_come_back_before_any_launch():
 # ---------------------------------------------------------------------------------------------- 3. argument checks
 
 def test_accumulate_refuses_a_weight_that_is_not_a_finite_number():
-    ts = object.__new__(sat.TrainStep)
+    ts = bare(sat.TrainStep)
     assert ts.accumulated == 0
     for bad in (NAN, INF, -INF, True, None, "1", [1.0]):
         with pytest.raises(ValueError, match="weight"):

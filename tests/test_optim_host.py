@@ -15,6 +15,7 @@ import torch
 
 import elementwise_reference as R
 import optim_reference as O
+from flat_adam_host import bare, host_flat
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sat = importlib.import_module("show-and-tell_amd")
@@ -247,7 +248,7 @@ def test_adjacent_no_decay_slices_merge_into_one_range():
 
 
 def test_train_step_properties_refuse_and_default():
-    ts = object.__new__(sat.TrainStep)
+    ts = bare(sat.TrainStep, {"decoder.linear.bias": (0, 3, (3,))})
     assert ts.max_grad_norm == 0.0 and ts.weight_decay == 0.0 and ts.no_decay is None and ts.last_grad_norm is None
     assert sat.TrainStep.max_grad_norm.fset is not None and sat.TrainStep.weight_decay.fset is not None
     for bad in (-1.0, NAN, "1", None, True):
@@ -265,10 +266,7 @@ def test_train_step_properties_refuse_and_default():
     ts.max_grad_norm, ts.no_decay = 0, None
     assert ts.max_grad_norm == 0.0 and ts.no_decay is None
 
-    class Flat:
-        slices = {"a.weight": (0, 6, (2, 3)), "a.bias": (8, 3, (3,)), "b.bias": (12, 2, (2,))}
-
-    ts.flat = Flat()
+    ts.flat = host_flat({"a.weight": (0, 6, (2, 3)), "a.bias": (8, 3, (3,)), "b.bias": (12, 2, (2,))})
     with pytest.raises(ValueError, match="nope"):
         ts.no_decay = ["a.bias", "nope"]
     ts.no_decay = ["b.bias", "a.bias"]
@@ -286,20 +284,12 @@ def test_train_step_signature_is_unchanged():
 
 
 def test_optimizer_state_dict_carries_the_new_keys_and_loads_into_torch_adamw():
-    """the flat engine's state dict without a device: an object made without __init__ and a stand-in flat buffer on the host"""
-    ts = object.__new__(sat.TrainStep)
+    """the flat engine's state dict without a device: an object made without __init__ around a real FlatAdam on the host"""
     w, b = torch.nn.Parameter(torch.randn(2, 3)), torch.nn.Parameter(torch.randn(3))
-
-    class Flat:
-        slices = {"w": (0, 6, (2, 3)), "b": (8, 3, (3,))}
-        m, v = torch.rand(12), torch.rand(12)
-
-    class Model:
-        @staticmethod
-        def named_parameters():
-            return [("w", w), ("b", b)]
-
-    ts.flat, ts.model = Flat(), Model()
+    ts, Flat = object.__new__(sat.TrainStep), host_flat({"w": (0, 6, (2, 3)), "b": (8, 3, (3,))})
+    Flat.m.copy_(torch.rand(12))
+    Flat.v.copy_(torch.rand(12))
+    ts.flat = Flat
     ts.lr, ts.grad_clip, ts.betas, ts.eps, ts.step_count = 1e-3, 0.1, (0.9, 0.999), 1e-8, 3
     sd = ts.optimizer_state_dict()
     assert sd["param_groups"][0]["weight_decay"] == 0 and sd["param_groups"][0]["decoupled_weight_decay"] is False
@@ -312,8 +302,7 @@ def test_optimizer_state_dict_carries_the_new_keys_and_loads_into_torch_adamw():
     opt = torch.optim.AdamW([w, b])
     opt.load_state_dict(sd)
     assert opt.param_groups[0]["weight_decay"] == 0.01 and torch.equal(opt.state[b]["exp_avg"], Flat.m[8:11])
-    other = object.__new__(sat.TrainStep)
-    other.flat, other.model = Flat(), Model()
+    other = bare(sat.TrainStep)
     other.load_optimizer_state_dict(sd)
     assert other.weight_decay == 0.01 and other.max_grad_norm == 5.0 and other.step_count == 3
     old = {k: v for k, v in sd.items() if k != "max_grad_norm"}          # a checkpoint from before the key existed
